@@ -1,6 +1,6 @@
 """Benchmark of the candidate-scoring hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Metric (BASELINE.json): precursors scored / s on the 1e6-precursor predicted library (3 candidates
 per precursor = 3e6 candidates) against the 2 h synthetic DIA run (4800 cycles x 61 spectra, 4.9e8
@@ -19,7 +19,13 @@ through ONE C-ABI call (adh_score_candidates: chunked, H2D / kernels / D2H overl
 streams).  The run and the fragment library are staged in HBM once (reported, excluded).  No torch
 anywhere in this file: device memory, streams and the communicator live behind the C ABI.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, ms_per_step, the
+workload).  ``--dump-outputs DIR`` writes what the last timed step handed its caller as DIR/<name>.npy (float32 /
+float64): a fixed, seeded sample of the rows of every OutputPsmDF table, and ``row.npy`` with the rows taken.  The
+files hold finite numbers only: undefined features (NaN) are written as 0 and marked in ``<name>_nonfinite.npy``.
+The inputs depend on the arguments only, so two builds can be compared file by file.
+
+With ``--full`` the run goes on after the headline, and the JSON line also carries
   resident      - the same step with the candidate table and its plan already resident in HBM and
                   the tables left in HBM (kernels + zero fill only)
   roofline      - algorithmic bytes (SURVEY.md section 8d formula) / kernel time per step (HIP
@@ -30,6 +36,8 @@ The JSON line also carries
                   Checker code is used here only as the thing timed beside the GPU.
   small_batches - host -> host latency at the batch sizes of the reference's optimisation loop
                   (optimization_lock.py:72-108: 8 000 elution groups, doubling)
+  compact, shard_8way, extras - the compact entry point, the shards of an eight-GPU run and the legs of the other
+                  kernel families (see below); on N > 1 GPUs, the check of the all-gathered tables
 """
 
 from __future__ import annotations
@@ -171,6 +179,45 @@ def release_shared_case(local_rank: int, world: int, n_prec: int, n_cycles: int)
                 pass
 
 
+DUMP_ROWS = 32768  # rows of the --dump-outputs sample
+DUMP_BYTES = 64_000_000  # cap of the files one --dump-outputs run writes
+DUMP_SEED = 20240917
+
+
+def dump_outputs(out_dir: str, host: dict, n_rows: int, prefix: str = "") -> int:
+    """The OutputPsmDF tables of the last timed step, one ``<prefix><name>.npy`` per table: float tables as float32,
+    integer ones as float64 (exact), on a fixed, seeded sample of rows (``<prefix>row.npy``).  Every file holds finite
+    numbers only: a feature the scoring leaves undefined is NaN (as in the reference), so each float table comes with
+    ``<name>_nonfinite.npy`` (0 finite, 1 NaN, 2 +inf, 3 -inf) and holds 0 at those places.  Returns the bytes written."""
+    from alphadia_amd import _abi
+
+    os.makedirs(out_dir, exist_ok=True)
+    cols = {name: host[name][:n_rows] for name, _, _ in _abi.OUTPUT_FIELDS}
+    # bytes per sampled row: 8 per value either way (float32 value + float32 code, or one float64), + the row number
+    per_row = 8 + sum(8 * int(np.prod(v.shape[1:], dtype=np.int64)) for v in cols.values())
+    n_files = 1 + len(cols) + sum(v.dtype == np.float32 for v in cols.values())
+    take = min(n_rows, DUMP_ROWS, (DUMP_BYTES - 4096 * n_files) // per_row)
+    rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n_rows, size=take, replace=False))
+    out = {"row": rows.astype(np.float64)}
+    for name, v in cols.items():
+        if v.dtype != np.float32:
+            out[name] = v[rows].astype(np.float64)
+            continue
+        vals = v[rows].astype(np.float32)
+        code = np.zeros(vals.shape, np.float32)
+        code[np.isnan(vals)] = 1
+        code[np.isposinf(vals)] = 2
+        code[np.isneginf(vals)] = 3
+        vals[code != 0] = 0.0
+        out[name], out[name + "_nonfinite"] = vals, code
+    written = 0
+    for name, arr in out.items():
+        assert np.isfinite(arr).all(), name
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), arr)
+        written += arr.nbytes
+    return written
+
+
 PRIME = 4  # untimed calls before the warm-up steps (see below)
 
 
@@ -190,7 +237,14 @@ def main():
     ap.add_argument("--extras-seconds", type=float, default=400.0,
                     help="wall-clock budget of the legs under `extras`; a leg that would start past it is skipped")
     ap.add_argument("--pageable", action="store_true", help="host buffers in pageable memory (for comparison)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a fixed, seeded row sample of the tables the last timed step returned as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything beside it: resident and compact "
+                         "steps, roofline, the all-gather check (N > 1), CPU baseline and the legs of `extras`")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -285,14 +339,67 @@ def main():
     fence()
     elapsed = time.perf_counter() - t0
     elapsed = ctx.all_reduce_max(elapsed)
+    value = n_prec_total * args.steps / elapsed
+
+    # ---------------- results of the last step ----------------
+    valid = host["valid"][:n_local].astype(bool)
+    print(f"[bench] rank {rank}: {int(valid.sum())}/{n_local} candidates valid", file=sys.stderr, flush=True)
+    if args.dump_outputs:
+        written = dump_outputs(args.dump_outputs, host, n_local, prefix="" if world == 1 else f"rank{rank}_")
+        print(f"[bench] rank {rank}: {written / 1e6:.1f} MB of outputs written to {args.dump_outputs}",
+              file=sys.stderr, flush=True)
+
+    result = {
+        "metric": "precursors scored/sec",
+        "value": value,
+        "unit": "precursors/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f32/f64",
+        "data": "synthetic",
+        "config": {
+            "workload": f"{n_prec_total}-precursor predicted library x 3 candidates vs "
+                        f"{'2h ' if args.cycles == 4800 else ''}synthetic Thermo-style DIA run "
+                        f"({args.cycles} cycles x 61 spectra); BASELINE configs[2] "
+                        f"{'on one GPU' if world == 1 else f'sharded over {world} GPUs'}",
+            "timed_region": "host candidate SoA -> H2D -> device plan -> gather + feature kernels -> "
+                            + ("RCCL all-gather of the computed tables -> " if world > 1 else "")
+                            + "D2H -> host OutputPsmDF SoA (one adh_score_candidates call per step)",
+            "host_buffers": "pageable" if args.pageable else "page-locked (adh_host_alloc)",
+            "precursors_total": n_prec_total,
+            "candidates_total": int(n_all),
+            "candidates_per_gpu": int(n_local),
+            "cycles": args.cycles,
+            "peaks": int(case.dia.mz_values.size),
+            "parallelism": (f"score-group shards x{world}, computed tables all-gathered over RCCL "
+                            f"(overlaps the D2H of the same step and the next step)") if world > 1 else "single GPU",
+            "rccl_ranks_seen": ranks_seen[1] if ranks_seen[0] == ranks_seen[1] else ranks_seen,
+            "valid_fraction": float(valid.mean()) if n_local else 0.0,
+            "priming_steps_before_warmup": PRIME,
+            "candidates_per_s": float(n_all * args.steps / elapsed),
+            "stage_seconds": t_stage,
+        },
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(result))
+        if with_comm:
+            ctx.comm_wait()
+            ctx.comm_destroy()
+        return
+
+    # ---------------- --full: everything beside the headline ----------------
     gather_ms, feature_ms, launches = ctx.kernel_time_ms(reset=True)
     per_step = launches / max(args.steps, 1)
     gather_ms, feature_ms = gather_ms * per_step, feature_ms * per_step
     kernel_ms = gather_ms + feature_ms
 
     # ---------------- results of the last step (sanity + roofline inputs) ----------------
-    valid = host["valid"][:n_local].astype(bool)
-    print(f"[bench] rank {rank}: {int(valid.sum())}/{n_local} candidates valid", file=sys.stderr, flush=True)
     matched = ctx.device_tables_to_host(names=["stat_matched_peaks"])["stat_matched_peaks"][:n_local]
     features_last = host["features"].copy() if world == 1 else None
     if with_comm:
@@ -360,42 +467,7 @@ def main():
         except runtime.HipBackendError as exc:
             log(f"[bench] compact leg skipped: {exc}")
 
-    value = n_prec_total * args.steps / elapsed
-    result = {
-        "metric": "precursors scored/sec",
-        "value": value,
-        "unit": "precursors/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": "f32/f64",
-        "data": "synthetic",
-        "config": {
-            "workload": f"{n_prec_total}-precursor predicted library x 3 candidates vs "
-                        f"{'2h ' if args.cycles == 4800 else ''}synthetic Thermo-style DIA run "
-                        f"({args.cycles} cycles x 61 spectra); BASELINE configs[2] "
-                        f"{'on one GPU' if world == 1 else f'sharded over {world} GPUs'}",
-            "timed_region": "host candidate SoA -> H2D -> device plan -> gather + feature kernels -> "
-                            + ("RCCL all-gather of the computed tables -> " if world > 1 else "")
-                            + "D2H -> host OutputPsmDF SoA (one adh_score_candidates call per step)",
-            "host_buffers": "pageable" if args.pageable else "page-locked (adh_host_alloc)",
-            "precursors_total": n_prec_total,
-            "candidates_total": int(n_all),
-            "candidates_per_gpu": int(n_local),
-            "cycles": args.cycles,
-            "peaks": int(case.dia.mz_values.size),
-            "parallelism": (f"score-group shards x{world}, computed tables all-gathered over RCCL "
-                            f"(overlaps the D2H of the same step and the next step)") if world > 1 else "single GPU",
-            "rccl_ranks_seen": ranks_seen[1] if ranks_seen[0] == ranks_seen[1] else ranks_seen,
-            "valid_fraction": float(valid.mean()) if n_local else 0.0,
-            "priming_steps_before_warmup": PRIME,
-            "candidates_per_s": float(n_all * args.steps / elapsed),
-            "stage_seconds": t_stage,
-        },
+    result.update({
         "compact": compact,
         "resident": None if resident_ms is None else {
             "ms_per_step": resident_ms,
@@ -419,7 +491,7 @@ def main():
             "algorithmic_bytes_per_launch": bytes_per_launch,
             "algorithmic_bytes_per_candidate": bytes_per_launch / max(n_local, 1),
         },
-    }
+    })
     # HBM traffic: PMC counters need rocprofv3 passes of their own (tools/profile_r4.sh), so the line carries the
     # figure of the committed profile of this workload - and says so, with the commit it was measured at
     traffic_file = os.path.join(ROOT, "profiles", "pmc_traffic.json")

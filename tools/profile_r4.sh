@@ -2,7 +2,7 @@
 # (tools/rocpd_summary.py reads a database as kernel statistics when its path holds "stats", as counters otherwise)
 # Profiling recipe of the committed profiles/r04_* files (GPU box, from the repo root via gpurun).  Every PMC pass is a
 # run of its own, never together with a trace domain other than --kernel-trace.
-#   headline  : kernel-trace statistics + PMC passes of `bench.py --steps 5 --warmup 3 --no-cpu-baseline --no-extras`
+#   headline  : kernel-trace statistics + PMC passes of `bench.py --full --steps 5 --warmup 3 --no-cpu-baseline --no-extras`
 #               -> r04_final_kernel_stats.csv, r04_final_pmc.csv, pmc_traffic.json (stamped with the commit)
 #   configs[3]: kernel trace + FETCH_SIZE / WRITE_SIZE of tools/bench_timstof.py at full size
 #               -> r04_timstof_kernel_stats.csv, r04_timstof_pmc.csv, timstof_traffic.json
@@ -16,7 +16,7 @@ HEAD_ID=${GIT_HEAD:-unknown}
 mkdir -p $OUT
 cd /tmp
 rm -rf /tmp/p4_*
-CMD="python $REPO/bench.py --steps 5 --warmup 3 --no-cpu-baseline --no-extras"
+CMD="python $REPO/bench.py --full --steps 5 --warmup 3 --no-cpu-baseline --no-extras"
 rocprofv3 --kernel-trace --stats -d /tmp/p4_stats -o r4 -- $CMD > $OUT/p4_stats.log 2>&1
 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_SMEM -d /tmp/p4_pmc1 -o r4 -- $CMD > $OUT/p4_pmc1.log 2>&1
 rocprofv3 --pmc SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_SCA -d /tmp/p4_pmc2 -o r4 -- $CMD > $OUT/p4_pmc2.log 2>&1
@@ -70,7 +70,7 @@ rm -rf /tmp/p4_*
 # ---- the bench line itself (driver style), with the traffic files of this run in place
 cd $REPO
 cp $OUT/timstof_traffic.json profiles/timstof_traffic.json
-python bench.py --steps 20 --warmup 5 > $OUT/r04_final_bench.json 2> $OUT/r04_final_bench.log
+python bench.py --full --steps 20 --warmup 5 > $OUT/r04_final_bench.json 2> $OUT/r04_final_bench.log
 tail -1 $OUT/r04_final_bench.json | cut -c1-400
 grep -v "at::native\|rocprim\|rocclr" $OUT/r04_final_kernel_stats.csv | sed 's/(DevRun[^)]*)//; s/void //' | cut -c1-130 | head -14
 head -8 $OUT/r04_timstof_kernel_stats.csv | cut -c1-130

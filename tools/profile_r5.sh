@@ -1,7 +1,7 @@
 #!/bin/bash
 # Profiling recipe of the committed profiles/r05_* files (GPU box, from the repo root via gpurun; GIT_HEAD=<commit>).
 # Every PMC pass is a run of its own, never together with a trace domain other than --kernel-trace.
-#   headline  : kernel-trace statistics + PMC passes of `bench.py --steps 5 --warmup 3 --no-cpu-baseline --no-extras`
+#   headline  : kernel-trace statistics + PMC passes of `bench.py --full --steps 5 --warmup 3 --no-cpu-baseline --no-extras`
 #               -> r05_final_kernel_stats.csv, r05_final_pmc.csv, pmc_traffic.json, r05_valu_busy.json
 #   MFMA      : SQ_INSTS_VALU_MFMA_MOPS_F32 / SQ_VALU_MFMA_BUSY_CYCLES of the ion-mobility profile kernel (configs[3])
 #               and of the classifier fit (tools/bench_fdr.py) -> r05_mfma_pmc.csv, r05_mfma.json
@@ -17,7 +17,7 @@ mkdir -p $OUT
 cd /tmp
 rm -rf /tmp/p5_*
 S="python $REPO/tools/rocpd_summary.py"
-CMD="python $REPO/bench.py --steps 5 --warmup 3 --no-cpu-baseline --no-extras"
+CMD="python $REPO/bench.py --full --steps 5 --warmup 3 --no-cpu-baseline --no-extras"
 rocprofv3 --kernel-trace --stats -d /tmp/p5_stats -o r5 -- $CMD > $OUT/p5_stats.log 2>&1
 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_SMEM -d /tmp/p5_pmc1 -o r5 -- $CMD > $OUT/p5_pmc1.log 2>&1
 rocprofv3 --pmc SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_SCA -d /tmp/p5_pmc2 -o r5 -- $CMD > $OUT/p5_pmc2.log 2>&1
@@ -109,7 +109,7 @@ rm -rf /tmp/p5_*
 cd $REPO
 cp $OUT/timstof_traffic.json profiles/timstof_traffic.json
 cp $OUT/legs_traffic.json profiles/legs_traffic.json
-python bench.py --steps 20 --warmup 5 > $OUT/r05_final_bench.json 2> $OUT/r05_final_bench.log
+python bench.py --full --steps 20 --warmup 5 > $OUT/r05_final_bench.json 2> $OUT/r05_final_bench.log
 tail -1 $OUT/r05_final_bench.json | cut -c1-400
 grep -v "at::native\|rocprim\|rocclr" $OUT/r05_final_kernel_stats.csv | sed 's/(DevRun[^)]*)//; s/void //' | cut -c1-130 | head -10
 cat $OUT/r05_valu_busy.json | head -40
