@@ -617,3 +617,41 @@ def pack_mlp_arch(input_dim: int, layers, output_dim: int, bn_eps: float = 1e-5,
     a.bn_eps = bn_eps
     a.bn_momentum = bn_momentum
     return a
+
+
+LOESS_MAX_KERNELS = 32
+LOESS_MAX_DEGREE = 4
+CALIBRATION_CHUNK_ROWS = 1 << 20
+
+
+class LoessModel(C.Structure):
+    _fields_ = [
+        ("n_kernels", C.c_int32),
+        ("degree", C.c_int32),
+        ("scale_mean", C.c_double * LOESS_MAX_KERNELS),
+        ("scale_max", C.c_double * LOESS_MAX_KERNELS),
+        ("beta", C.c_double * ((LOESS_MAX_DEGREE + 1) * LOESS_MAX_KERNELS)),
+    ]
+
+
+def pack_loess_model(scale_mean, scale_max, beta) -> LoessModel:
+    """``adh_loess_model_t`` from fitted LOESSRegression parameters: ``beta`` is NumPy's ``beta[d, k]``
+    of shape (degree + 1, n_kernels)."""
+    beta = np.asarray(beta, dtype=np.float64)
+    mean = np.asarray(scale_mean, dtype=np.float64).ravel()
+    smax = np.asarray(scale_max, dtype=np.float64).ravel()
+    if beta.ndim != 2:
+        raise ValueError("beta must have shape (degree + 1, n_kernels)")
+    d1, k = beta.shape
+    if not 1 <= k <= LOESS_MAX_KERNELS or not 1 <= d1 <= LOESS_MAX_DEGREE + 1:
+        raise ValueError(f"LOESS model with {k} kernels and degree {d1 - 1}: at most {LOESS_MAX_KERNELS} kernels "
+                         f"and degree {LOESS_MAX_DEGREE} are supported")
+    if mean.shape[0] != k or smax.shape[0] != k:
+        raise ValueError("scale_mean / scale_max must have one entry per kernel (column of beta)")
+    m = LoessModel()
+    m.n_kernels = k
+    m.degree = d1 - 1
+    m.scale_mean[:k] = mean.tolist()
+    m.scale_max[:k] = smax.tolist()
+    m.beta[: d1 * k] = beta.ravel().tolist()
+    return m

@@ -409,6 +409,14 @@ struct adh_handle {
         hipStream_t st = nullptr;
     };
     std::vector<UpLane> up_lanes;
+    // adh_calibration_predict (adh_calibration.hip): per pipeline slot page-locked and device staging of one chunk
+    // ([inputs | outputs], allocated on first use), the event of its last copy, the events around its kernel
+    struct CalibSlot {
+        void *host = nullptr, *dev = nullptr;
+        hipEvent_t done = nullptr, k0 = nullptr, k1 = nullptr;
+    };
+    CalibSlot calib[2];
+    double calib_kernel_ms = 0.0;
 };
 
 namespace {
@@ -636,6 +644,12 @@ int adh_destroy(adh_handle_t *h) {
             if (l.ev[k]) (void)hipEventDestroy(l.ev[k]);
         }
         if (l.st) (void)hipStreamDestroy(l.st);
+    }
+    for (adh_handle::CalibSlot &s : h->calib) {
+        if (s.host) (void)hipHostFree(s.host);
+        if (s.dev) (void)hipFree(s.dev);
+        for (hipEvent_t e : {s.done, s.k0, s.k1})
+            if (e) (void)hipEventDestroy(e);
     }
     if (h->cop_scan) (void)hipFree(h->cop_scan);
     if (h->cmp_dev) (void)hipFree(h->cmp_dev);
@@ -1907,3 +1921,4 @@ int adh_fragcomp_stats(adh_handle_t *h, double *kernel_ms, int64_t *pairs, int64
 #include "adh_fdr.hip"
 #include "adh_mlp.hip"
 #include "adh_fdr_device.hip"
+#include "adh_calibration.hip"

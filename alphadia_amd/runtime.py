@@ -73,6 +73,8 @@ EXPORTED_SYMBOLS = [
     "adh_comm_info",
     "adh_table_layout",
     "adh_device_synchronize",
+    "adh_calibration_predict",
+    "adh_calibration_time_ms",
 ]
 
 
@@ -936,6 +938,31 @@ class Context:
             "adh_fdr_keep_best",
         )
         return keep.view(np.bool_)
+
+    # -- library calibration ---------------------------------------------
+    def calibration_predict(self, model, x) -> np.ndarray:
+        """``adh_calibration_predict``: ``LOESSRegression.predict`` (alphadia/calibration/models.py:276-300) of a
+        fitted model - anything with ``scale_mean``, ``scale_max`` and ``beta[d, k]`` - over a float32 or float64
+        column, host -> host.  Other dtypes are taken as float64.  Returns float64."""
+        packed = _abi.pack_loess_model(model.scale_mean, model.scale_max, model.beta)
+        xa = np.asarray(x)
+        if xa.ndim == 2 and xa.shape[1] == 1:
+            xa = xa[:, 0]
+        if xa.ndim != 1:
+            raise ValueError("calibration_predict takes one input column")
+        xa = np.ascontiguousarray(xa, dtype=np.float32 if xa.dtype == np.float32 else np.float64)
+        y = np.empty(xa.shape[0], dtype=np.float64)
+        _check(lib.adh_calibration_predict(self._h, C.byref(packed), C.c_void_p(xa.ctypes.data),
+                                           C.c_int32(int(xa.dtype == np.float64)), C.c_int64(xa.shape[0]),
+                                           y.ctypes.data_as(C.POINTER(C.c_double))),
+               "adh_calibration_predict")
+        return y
+
+    def calibration_time_ms(self) -> float:
+        """HIP-event time of the kernels of the last ``calibration_predict`` call."""
+        ms = C.c_double(0.0)
+        _check(lib.adh_calibration_time_ms(self._h, C.byref(ms)), "adh_calibration_time_ms")
+        return float(ms.value)
 
 
 class DeviceMlp:

@@ -648,6 +648,41 @@ int adh_fdr_resident(adh_handle_t *handle, adh_mlp_t *mlp, const int64_t *group_
 /* bytes this library has copied device -> host on the handle's GPU since the last reset */
 int adh_transfer_counters(adh_handle_t *handle, uint64_t *d2h_bytes, int reset);
 
+/* ------------------------------------------------------------------------------------------
+ * Calibration of the spectral library (alphadia/workflow/managers/calibration_manager.py:34-297):
+ * the prediction of a fitted LOESS model over a library column.  The fit stays on the host
+ * (alphadia_amd/calibration.py): it sees a few thousand rows.
+ * ------------------------------------------------------------------------------------------ */
+
+#define ADH_LOESS_MAX_KERNELS 32
+#define ADH_LOESS_MAX_DEGREE 4
+#define ADH_CALIBRATION_CHUNK_ROWS (1 << 20) /* rows per pipeline chunk of adh_calibration_predict */
+
+/* The fitted parameters of LOESSRegression (alphadia/calibration/models.py:24-366). */
+typedef struct adh_loess_model {
+    int32_t n_kernels;                       /* 1 .. ADH_LOESS_MAX_KERNELS */
+    int32_t degree;                          /* polynomial_degree, 0 .. ADH_LOESS_MAX_DEGREE */
+    double scale_mean[ADH_LOESS_MAX_KERNELS];  /* [n_kernels] kernel centres */
+    double scale_max[ADH_LOESS_MAX_KERNELS];   /* [n_kernels] kernel half widths */
+    double beta[(ADH_LOESS_MAX_DEGREE + 1) * ADH_LOESS_MAX_KERNELS];  /* beta[d * n_kernels + k] = NumPy's beta[d, k] */
+} adh_loess_model_t;
+
+/*
+ * y[i] = LOESSRegression.predict(x)[i] (models.py:276-300, weights :302-366) for n rows of a float32
+ * (x_is_f64 = 0) or float64 column: tricubic kernel weights of (x - scale_mean) / scale_max, the first kernel
+ * left-open, the last right-open, normalised by their sum; y = sum_k w_k sum_d x^d beta[d, k].  The design row x^d
+ * is built in the input's dtype as sklearn's PolynomialFeatures does, all else in float64.  NaN inputs and rows
+ * whose weights sum to 0 give NaN, as in NumPy.  Host -> host: chunks of ADH_CALIBRATION_CHUNK_ROWS rows go
+ * through two page-locked slots of the handle on two of its streams, so that the host copies of one chunk overlap
+ * the transfers and kernel of the other.  Replaces the prediction the reference runs on the host for the batch
+ * library of every optimisation step (workflow/managers/optimization_lock.py:148-163) and for the whole library
+ * afterwards (workflow/peptidecentric/peptidecentric.py:175-180).  n may be 0.
+ */
+int adh_calibration_predict(adh_handle_t *handle, const adh_loess_model_t *model, const void *x, int32_t x_is_f64,
+                            int64_t n, double *y);
+/* Summed HIP-event duration (ms) of the kernels of the last adh_calibration_predict call. */
+int adh_calibration_time_ms(adh_handle_t *handle, double *kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif
