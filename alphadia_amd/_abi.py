@@ -655,3 +655,18 @@ def pack_loess_model(scale_mean, scale_max, beta) -> LoessModel:
     m.scale_max[:k] = smax.tolist()
     m.beta[: d1 * k] = beta.ravel().tolist()
     return m
+
+
+# ctypes prototypes of the resident-extraction entries (include/alphadia_hip.h); tests/ compares them with the header
+RESIDENT_PROTOTYPES = {
+    "adh_score_candidates_resident": [C.c_void_p, C.c_void_p, C.c_void_p],
+    "adh_take_rows": [C.c_void_p, C.POINTER(C.c_int64), C.c_int64, C.POINTER(CompactOutput)],
+}
+
+
+def declare(lib) -> None:
+    """Argument types of the entries listed in RESIDENT_PROTOTYPES (the others are called with explicit casts)."""
+    for name, argtypes in RESIDENT_PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.argtypes = argtypes
+        fn.restype = C.c_int

@@ -386,6 +386,9 @@ struct adh_handle {
     DevTables tables[2];            // slot 1 only with a communicator (double-buffered all-gather)
     int table_slot = 1, last_tables = -1;
     int64_t last_rows = 0;
+    // the last scoring call's tables still belong to the staged run and library (adh_take_rows): staging either
+    // ends that, although the tables themselves stay readable (materialise_tables)
+    bool tables_current = false;
     CandSlab cs;
     PlanSlot slots[2];
     Plan plan;                      // plan of the resident table (adh_upload_candidates / adh_score_uploaded)
@@ -822,6 +825,7 @@ int adh_stage_alpharaw(adh_handle_t *h, const adh_alpharaw_t *d) {
     {
         const int rc_m = materialise_tables(h);  // while the candidate table the last call scored is still the resident one
         if (rc_m != ADH_OK) return rc_m;
+        h->tables_current = false;
     }
     HIP_TRY(hipDeviceSynchronize());
     h->run_buf.release();
@@ -1058,6 +1062,7 @@ int adh_stage_timstof(adh_handle_t *h, const adh_timstof_t *d) {
     {
         const int rc_m = materialise_tables(h);  // while the candidate table the last call scored is still the resident one
         if (rc_m != ADH_OK) return rc_m;
+        h->tables_current = false;
     }
     HIP_TRY(hipDeviceSynchronize());
     h->run_buf.release();
@@ -1179,6 +1184,7 @@ int adh_stage_fragments(adh_handle_t *h, const adh_fragments_t *f) {
     {
         const int rc_m = materialise_tables(h);  // the last call's tables refer to the library that goes away
         if (rc_m != ADH_OK) return rc_m;
+        h->tables_current = false;
     }
     HIP_TRY(hipDeviceSynchronize());
     h->lib_buf.release();
@@ -1922,3 +1928,4 @@ int adh_fragcomp_stats(adh_handle_t *h, double *kernel_ms, int64_t *pairs, int64
 #include "adh_mlp.hip"
 #include "adh_fdr_device.hip"
 #include "adh_calibration.hip"
+#include "adh_take_rows.hip"

@@ -1419,15 +1419,16 @@ bool host_rebuild_pays() {
 
 namespace {
 // the host -> host pipeline behind adh_score_candidates (padded tables into `out`) and adh_score_candidates_compact
-// (`cop` set: `out` only carries n and top_k, the compacted columns go to `cop`)
+// (`cop` set: `out` only carries n and top_k, the compacted columns go to `cop`) and adh_score_candidates_resident
+// (`resident`: `out` only carries n and top_k, nothing is copied back)
 int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring_config_t *cfg, adh_output_t *out,
-                   adh_compact_output_t *cop) {
+                   adh_compact_output_t *cop, bool resident = false) {
     if (!h || !c || !cfg || !out) return fail(ADH_ERR_INVALID_ARGUMENT, "NULL argument");
     if (out->n != c->n) return fail(ADH_ERR_INVALID_ARGUMENT, "output rows != candidates");
     int rc = check_candidate_args(h, c);
     if (rc == ADH_OK) rc = check_score_args(h, cfg, out);
     if (rc != ADH_OK) return rc;
-    for (int i = 0; i < kNumOutFields && !cop; ++i)
+    for (int i = 0; i < kNumOutFields && !cop && !resident; ++i)
         if (!kOutFields[i].optional && *out_member(out, kOutFields[i]) == nullptr)
             return fail(ADH_ERR_INVALID_ARGUMENT, "output buffer is NULL");
     HIP_TRY(hipSetDevice(h->device));
@@ -1462,7 +1463,12 @@ int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring
         if (timing && was) fprintf(stderr, "[adh] copy path settled in %.1f ms\n", now() - t_s);
     }
     if (cop) cop->n_rows = cop->n_slots = 0;
-    if (n == 0) return comm_gather_slot(h, slot);
+    h->tables_current = false;
+    if (n == 0) {
+        rc = comm_gather_slot(h, slot);
+        h->tables_current = rc == ADH_OK;
+        return rc;
+    }
     std::vector<hipEvent_t> chunk_done;
     // a call that fails half way leaves no tables behind (a reader would rebuild columns of a half-filled
     // table), and its events go back to the pool
@@ -1527,7 +1533,7 @@ int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring
     // rebuildable columns: not copied back, rebuilt on the host from fragment_lib_slot (see kOutFields)
     if (cop)  // (a chunk's slot offsets are 32-bit words of the packed count)
         chunk = std::min<int64_t>(chunk, std::max<int64_t>((int64_t)(0xFFFFFFFFull / (uint64_t)top_k) - 1, 1));
-    const bool rebuild = !cop && h->h_lib.size() == (size_t)h->n_lib && !getenv("ADH_DEBUG_COPY_ALL") && host_rebuild_pays();
+    const bool rebuild = !cop && !resident && h->h_lib.size() == (size_t)h->n_lib && !getenv("ADH_DEBUG_COPY_ALL") && host_rebuild_pays();
     uint16_t *slot_host = out->fragment_lib_slot;
     if (rebuild && !slot_host) {
         const size_t need = (size_t)n * (size_t)top_k * sizeof(uint16_t);
@@ -1541,7 +1547,7 @@ int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring
         slot_host = static_cast<uint16_t *>(h->slot_stage);
     }
     adh_output_t dev_k = dev;  // what the kernels write
-    if ((rebuild || cop) && !getenv("ADH_DEBUG_WRITE_ALL")) {
+    if ((rebuild || cop || resident) && !getenv("ADH_DEBUG_WRITE_ALL")) {
         // ... and the kernels need not write them either: nobody on the host waits for them, and a reader of the
         // device tables (adh_get_device_tables, the resident FDR stage) gets them filled in on demand
         for (int i = 0; i < kNumOutFields; ++i) {
@@ -1882,7 +1888,7 @@ int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring
         // (A chunk is up to nine copies and the engine idles ~10 us between two of them - a 47 000-row chunk, 21 MB, takes
         // 0.46 ms = 46 GB/s where each copy runs at 55, `rocprofv3 --memory-copy-trace` - but a second copy-out stream for
         // the feature table does not fill the gaps: measured in round 5, same times to the 0.01 ms, and taken out again.)
-        for (int i = 0; i < kNumOutFields && !cop; ++i) {
+        for (int i = 0; i < kNumOutFields && !cop && !resident; ++i) {
             const OutFieldDesc &f = kOutFields[i];
             void *host = *out_member(out, f);
             const bool is_slot = f.member == offsetof(adh_output_t, fragment_lib_slot);
@@ -1941,6 +1947,7 @@ int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring
             (void)hipStreamSynchronize(sk);
             (void)hipStreamSynchronize(so);
             unwind.ok = true;  // (the device tables are complete)
+            h->tables_current = true;
             return fail(ADH_ERR_INVALID_ARGUMENT, "compact output: rows_capacity / slots_capacity too small (n_rows / n_slots say what is needed)");
         }
     }
@@ -2016,6 +2023,7 @@ int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring
         for (hipEvent_t e : dbg) (void)hipEventDestroy(e);
     }
     unwind.ok = true;
+    h->tables_current = true;
     return ADH_OK;
 }
 }  // namespace

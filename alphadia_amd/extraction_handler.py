@@ -12,15 +12,25 @@ SURVEY.md section 8f-1), scoring and quantification all run on the GPU, for runs
 with and without ion mobility; an optional ``selection_handler`` (e.g. the
 reference's own ``ClassicExtractionHandler``) can take over the selection step.
 
+``extract`` is the whole per-file extraction of ``PeptideCentricWorkflow.extraction``
+(alphadia/workflow/peptidecentric/peptidecentric.py:183-263) on one GPU: the scores and the FDR stage stay in
+HBM and only the surviving PSMs and their fragments cross PCIe.
+
 INTEGRATION.md shows the three-line patch that registers the backend.
 """
 
 from __future__ import annotations
 
+import logging
+import time
+
 import pandas as pd
 
+from alphadia_amd.fragcomp import candidate_hash
 from alphadia_amd.scoring import CandidateScoringConfig, HipCandidateScoring
 from alphadia_amd.selection import CandidateSelectionConfig, HipCandidateSelection
+
+logger = logging.getLogger(__name__)
 
 
 class HipExtractionHandler:
@@ -47,6 +57,7 @@ class HipExtractionHandler:
         self._column_name_handler = column_name_handler
         self._selection_handler = selection_handler
         self._device = device
+        self._fallbacks_logged: set[str] = set()
         # extraction_handler.py:390-398
         self._selection_config = CandidateSelectionConfig()
         search = config["search"]
@@ -106,11 +117,20 @@ class HipExtractionHandler:
     def score_and_quantify_candidates(self, candidates_df, dia_data, spectral_library,
                                       top_k_fragments: int | None = None):
         """extraction_handler.py:449-486 with ``CandidateScoring`` replaced by the GPU operator."""
+        candidate_scoring = self._candidate_scoring(dia_data, spectral_library, top_k_fragments)
+        return candidate_scoring(
+            candidates_df,
+            thread_count=self._config["general"]["thread_count"],
+            include_decoy_fragment_features=True,
+        )
+
+    def _candidate_scoring(self, dia_data, spectral_library, top_k_fragments: int | None = None) -> HipCandidateScoring:
+        """The scoring operator of extraction_handler.py:449-486, configured by the optimisation manager."""
         om = self._optimization_manager
         k = top_k_fragments if top_k_fragments is not None else self._config["search"]["top_k_fragments_scoring"]
         self._scoring_config.update(dict(precursor_mz_tolerance=om.ms1_error, fragment_mz_tolerance=om.ms2_error,
                                          top_k_fragments=k))
-        candidate_scoring = HipCandidateScoring(
+        return HipCandidateScoring(
             dia_data=dia_data,
             precursors_flat=spectral_library.precursor_df,
             fragments_flat=spectral_library.fragment_df,
@@ -121,11 +141,94 @@ class HipExtractionHandler:
             fragment_mz_column=self._column_name_handler.get_fragment_mz_column(),
             device=self._device,
         )
-        return candidate_scoring(
-            candidates_df,
-            thread_count=self._config["general"]["thread_count"],
-            include_decoy_fragment_features=True,
+
+    def resident_refusal(self) -> str | None:
+        """Why ``extract`` cannot keep the tables in HBM for this run (it then takes the chained calls), or None."""
+        return resident_refusal(self._config, self._fdr_manager, self._comm_attached)
+
+    def _comm_attached(self) -> bool:
+        from alphadia_amd import runtime
+
+        return bool(getattr(runtime.get_context(self._device), "_comm_attached", False))
+
+    def extract(self, dia_data, spectral_library) -> tuple[pd.DataFrame, pd.DataFrame]:
+        """``PeptideCentricWorkflow.extraction`` (peptidecentric.py:196-246, the python branch) on one GPU:
+        candidates -> scores in HBM -> FDR stage on the tables in HBM -> ``qval <= fdr`` -> the survivors' rows and
+        their fragments, copied back as the only transfer of the tables.  Returns ``(precursor_df, fragments_df)`` as
+        that branch builds them - the features frame's columns, ``_decoy``, ``proba``, ``qval`` (``_candidate_idx``
+        and ``valid`` when fragments competed), ``candidate_idx``; the PSMs in the FDR output order, the fragments in
+        candidate / slot order - each with a fresh RangeIndex.  Channel-wise FDR, an FDR manager that is not a
+        ``HipFDRManager`` and an attached communicator take the chained calls instead (the reason is logged once)."""
+        t_0 = time.perf_counter()
+        candidates_df = self.select_candidates(dia_data, spectral_library, apply_cutoff=True)
+        reason = self.resident_refusal()
+        if reason is not None:
+            if reason not in self._fallbacks_logged:
+                self._fallbacks_logged.add(reason)
+                self._reporter.log_string(f"Resident extraction not used: {reason}", verbosity="info")
+                logger.info("resident extraction not used: %s", reason)
+            return self._extract_chained(candidates_df, dia_data, spectral_library, t_0)
+        fdr_config = self._config["fdr"]
+        t_1 = time.perf_counter()
+        resident = self._candidate_scoring(dia_data, spectral_library).score_resident(candidates_df)
+        t_2 = time.perf_counter()
+        psm_df = self._fdr_manager.fit_predict_resident(
+            resident, competitive=fdr_config["competitive_scoring"],
+            version=getattr(self._optimization_manager, "classifier_version", -1))
+        too_few = bool(psm_df.attrs.get("too_few_psms", False))
+        competed = bool(psm_df.attrs.get("fragment_competition", False))
+        t_3 = time.perf_counter()
+        psm_df = psm_df[psm_df["qval"].to_numpy() <= fdr_config["fdr"]]
+        self._reporter.log_string("Removing fragments below FDR threshold")
+        precursor_df, fragments_df = resident.frames(psm_df["table_row"].to_numpy())
+        if len(precursor_df) != len(psm_df):
+            raise RuntimeError("the FDR stage kept rows the scoring call marked invalid")
+        if too_few:  # perform_fdr's answer for too few PSMs (fdr.py:125-137): qval, then proba, no _decoy
+            precursor_df["qval"] = 1.0
+            precursor_df["proba"] = 1.0
+        else:
+            precursor_df["_decoy"] = psm_df["_decoy"].to_numpy()
+            precursor_df["proba"] = psm_df["proba"].to_numpy()
+            precursor_df["qval"] = psm_df["qval"].to_numpy()
+            if competed:  # the columns FragmentCompetition leaves behind (fragcomp.py:291-299)
+                precursor_df["_candidate_idx"] = candidate_hash(precursor_df["precursor_idx"].to_numpy(),
+                                                                precursor_df["rank"].to_numpy())
+                precursor_df["valid"] = True
+        precursor_df["candidate_idx"] = candidate_hash(precursor_df["precursor_idx"].to_numpy(),
+                                                       precursor_df["rank"].to_numpy())
+        fragments_df["candidate_idx"] = candidate_hash(fragments_df["precursor_idx"].to_numpy(),
+                                                       fragments_df["rank"].to_numpy())
+        t_4 = time.perf_counter()
+        # wall time of the stages of the last call, in ms (select includes the cutoff)
+        self.last_timings = {"path": "resident", "select_ms": (t_1 - t_0) * 1e3, "score_ms": (t_2 - t_1) * 1e3,
+                             "fdr_ms": (t_3 - t_2) * 1e3, "filter_ms": (t_4 - t_3) * 1e3, "total_ms": (t_4 - t_0) * 1e3}
+        return precursor_df, fragments_df
+
+    def _extract_chained(self, candidates_df, dia_data, spectral_library, t_0=None) -> tuple[pd.DataFrame, pd.DataFrame]:
+        """peptidecentric.py:202-246 as written: the frames go through the host between the stages."""
+        fdr_config = self._config["fdr"]
+        t_1 = time.perf_counter()
+        features_df, fragments_df = self.score_and_quantify_candidates(candidates_df, dia_data, spectral_library)
+        t_2 = time.perf_counter()
+        precursor_df = self._fdr_manager.fit_predict(
+            features_df,
+            decoy_strategy="precursor_channel_wise" if fdr_config["channel_wise_fdr"] else "precursor",
+            competitive=fdr_config["competitive_scoring"],
+            df_fragments=fragments_df,
+            version=getattr(self._optimization_manager, "classifier_version", -1),
         )
+        t_3 = time.perf_counter()
+        precursor_df = precursor_df[precursor_df["qval"] <= fdr_config["fdr"]].copy()
+        self._reporter.log_string("Removing fragments below FDR threshold")
+        fragments_df["candidate_idx"] = candidate_hash(fragments_df["precursor_idx"].values, fragments_df["rank"].values)
+        precursor_df["candidate_idx"] = candidate_hash(precursor_df["precursor_idx"].values, precursor_df["rank"].values)
+        fragments_df = fragments_df[fragments_df["candidate_idx"].isin(precursor_df["candidate_idx"])]
+        precursor_df, fragments_df = precursor_df.reset_index(drop=True), fragments_df.reset_index(drop=True)
+        t_4 = time.perf_counter()
+        t_0 = t_1 if t_0 is None else t_0
+        self.last_timings = {"path": "chained", "select_ms": (t_1 - t_0) * 1e3, "score_ms": (t_2 - t_1) * 1e3,
+                             "fdr_ms": (t_3 - t_2) * 1e3, "filter_ms": (t_4 - t_3) * 1e3, "total_ms": (t_4 - t_0) * 1e3}
+        return precursor_df, fragments_df
 
     def quantify_candidates(self, candidates_df, precursor_fdr_df, dia_data, spectral_library,
                             top_k_fragments: int | None = None):
@@ -135,6 +238,21 @@ class HipExtractionHandler:
             candidates_df, dia_data, spectral_library, top_k_fragments
         )
         return None, fragments_df
+
+
+def resident_refusal(config, fdr_manager, comm_attached) -> str | None:
+    """The reason the resident extraction does not apply, or None: channel-wise FDR (the device classifier stages
+    whole tables, not row subsets), an FDR manager other than ``HipFDRManager``, or a communicator on the context
+    (``comm_attached()``; any world size - the tables are then a rank's shard plus a gather)."""
+    from alphadia_amd.fdr import HipFDRManager
+
+    if config["fdr"]["channel_wise_fdr"]:
+        return "channel-wise FDR needs row subsets in the device classifier's staging"
+    if not isinstance(fdr_manager, HipFDRManager):
+        return f"the FDR manager is a {type(fdr_manager).__name__}, not a HipFDRManager"
+    if comm_attached():
+        return "a communicator is attached: the device tables are a rank's shard plus a gather"
+    return None
 
 
 def create_handler(config, optimization_manager, fdr_manager, reporter, column_name_handler,

@@ -513,6 +513,7 @@ def perform_fdr_resident(classifier, available_columns: list[str], candidates: p
         out["proba"] = 1.0
         out["qval"] = 1.0
         out["table_row"] = rows
+        out.attrs["too_few_psms"] = True  # (perform_fdr's frame of this branch has other columns: callers rebuild it)
         return out
     try:
         mlp.predict_resident()
@@ -602,6 +603,47 @@ class HipFDRManager:
             psm_df.loc[psm_df["channel"] == decoy_channel, "decoy"] = 1
         else:
             raise ValueError(f"Invalid decoy_strategy: {decoy_strategy}")
+
+        self._current_version += 1
+        self.classifier_store[tuple(sorted(available))].append(classifier)
+        return psm_df
+
+    def fit_predict_resident(self, resident, competitive: bool, version: int = -1) -> pd.DataFrame:
+        """``fit_predict(features_df, "precursor", competitive, df_fragments, version=version)`` for candidates scored
+        with ``HipCandidateScoring.score_resident``: the feature and fragment tables stay in HBM
+        (:func:`perform_fdr_resident`).  The classifier sees the columns in the order ``fit_predict`` gives them (that
+        of the features frame), the seed is drawn from the same generator and the classifier is stored and versioned
+        the same way.  Returns the surviving PSMs in perform_fdr's output order as ids (``precursor_idx, rank,
+        elution_group_idx, channel, decoy``), ``_decoy``, ``proba``, ``qval`` and ``table_row``, the row of the PSM in
+        the device tables; ``attrs["too_few_psms"]`` marks perform_fdr's too-few-PSMs answer (every usable PSM with
+        qval = proba = 1, targets first)."""
+        wanted = set(self.feature_columns)
+        available = [c for c in resident.feature_columns() if c in wanted]
+        if not available:
+            raise ValueError("No feature columns found in features_df")
+        from alphadia_amd.scoring import DEFAULT_FEATURE_COLUMNS
+
+        rt_column = resident.rt_column
+        # one row per table row: the ids, and the classifier columns that are not kernel features (delta_rt is
+        # rt_observed minus the library rt, formed on the device)
+        meta = resident.metadata.copy(deep=False)
+        for c in available:
+            if c in DEFAULT_FEATURE_COLUMNS or c in meta.columns:
+                continue
+            name = rt_column if c == "delta_rt" else c
+            if name not in meta.columns:
+                meta[name] = resident.table_column(name)
+
+        classifier = self.get_classifier(available, version)
+        seed = None if self._np_rng is None else int(self._np_rng.integers(0, 1_000_000))
+        # fragment competition as fit_predict runs it: with the manager's cycle, when fragments compete at all
+        cycle = self._dia_cycle if self._compete_for_fragments else None
+        if cycle is not None and cycle.shape[2] > MAX_DIA_CYCLE_SHAPE:
+            cycle = None
+        device = self._device if self._device is not None else resident.device
+        psm_df = perform_fdr_resident(classifier, available, meta, rt_column=rt_column, competitive=competitive,
+                                      group_channels=True, dia_cycle=cycle, random_state=seed, device=device)
+        psm_df.attrs["fragment_competition"] = cycle is not None
 
         self._current_version += 1
         self.classifier_store[tuple(sorted(available))].append(classifier)

@@ -75,6 +75,8 @@ EXPORTED_SYMBOLS = [
     "adh_device_synchronize",
     "adh_calibration_predict",
     "adh_calibration_time_ms",
+    "adh_score_candidates_resident",
+    "adh_take_rows",
 ]
 
 
@@ -126,6 +128,7 @@ def _load():
     lib.adh_last_error.restype = C.c_char_p
     for name in EXPORTED_SYMBOLS[1:]:
         getattr(lib, name).restype = C.c_int
+    _abi.declare(lib)
     return lib
 
 
@@ -435,6 +438,8 @@ class Context:
         self.pinned = PinnedPool()
         self.comm_world = 1
         self.comm_rank = 0
+        # one more per scoring call that replaces the device tables (a resident result checks it is still current)
+        self.tables_serial = 0
 
     def close(self):
         if self._h:
@@ -681,6 +686,7 @@ class Context:
                                           with_stats=with_stats, zero=False, alloc=alloc,
                                           with_slots=with_stats or not reuse_buffers)
         cfg = _abi.pack_config(cfg_jit)
+        self.tables_serial += 1
         _check(
             lib.adh_score_candidates(self._h, cands.ref(), C.byref(cfg), m_out.ref()),
             "adh_score_candidates",
@@ -708,6 +714,7 @@ class Context:
         cfg = _abi.pack_config(cfg_jit)
         rows_cap = max(n, 1)
         slots_cap = max(int(n * (width if slots_per_row is None else min(float(slots_per_row), width))) + 1, 1)
+        self.tables_serial += 1
         while True:
             out = _abi.CompactOutput()
             out.rows_capacity, out.slots_capacity, out.top_k = rows_cap, slots_cap, width
@@ -732,6 +739,48 @@ class Context:
             _check(rc, "adh_score_candidates_compact")
             break
         self.n_candidates = n
+        nr, ns = int(out.n_rows), int(out.n_slots)
+        res = {name: arrays[name][:nr] for name, _ in _abi.COMPACT_ROW_FIELDS}
+        res["features"] = arrays["features"][:, :nr]
+        res.update({name: arrays[name][:ns] for name, _ in _abi.COMPACT_SLOT_FIELDS})
+        res["top_k"] = width
+        return res
+
+    def score_resident(self, cands: _abi.Marshalled, cfg_jit) -> int:
+        """``adh_score_candidates_resident``: score into this context's device tables and copy nothing back.  The
+        tables (``device_tables``, ``fdr_resident``, ``take_rows``) are those ``score_host`` leaves; returns their width
+        (fragment slots per row).  Refused while a communicator is attached."""
+        n = int(cands.struct.n)
+        cfg = _abi.pack_config(cfg_jit)
+        self.tables_serial += 1
+        _check(lib.adh_score_candidates_resident(self._h, cands.ref(), C.byref(cfg)), "adh_score_candidates_resident")
+        self.n_candidates = n
+        return _abi.output_width(cands, int(cfg_jit.top_k_fragments))
+
+    def take_rows(self, rows) -> dict:
+        """``adh_take_rows``: the valid rows among the table rows ``rows`` of the current device tables, in list order,
+        and their filled fragment slots - a dict with the keys and shapes of ``score_host_compact`` (``row`` and
+        ``fragment_row`` are table rows).  Only these rows cross PCIe."""
+        r = np.ascontiguousarray(rows, dtype=np.int64)
+        if r.ndim != 1:
+            raise ValueError("rows must be one-dimensional")
+        width = int(self.device_tables().top_k)
+        n = r.shape[0]
+        rows_cap, slots_cap = max(n, 1), max(n * width, 1)
+        while True:
+            out = _abi.CompactOutput()
+            out.rows_capacity, out.slots_capacity, out.top_k = rows_cap, slots_cap, width
+            arrays = {name: np.empty(rows_cap, dtype=dt) for name, dt in _abi.COMPACT_ROW_FIELDS}
+            arrays["features"] = np.empty((_abi.NUM_FEATURES, rows_cap), dtype=np.float32)
+            arrays.update({name: np.empty(slots_cap, dtype=dt) for name, dt in _abi.COMPACT_SLOT_FIELDS})
+            for name, a in arrays.items():
+                setattr(out, name, a.ctypes.data_as(dict(out._fields_)[name]))
+            rc = lib.adh_take_rows(self._h, r.ctypes.data_as(C.POINTER(C.c_int64)), C.c_int64(n), C.byref(out))
+            if rc != 0 and (int(out.n_rows) > rows_cap or int(out.n_slots) > slots_cap):
+                rows_cap, slots_cap = max(rows_cap, int(out.n_rows)), max(slots_cap, int(out.n_slots))
+                continue  # (cannot happen: every listed row and slot fits)
+            _check(rc, "adh_take_rows")
+            break
         nr, ns = int(out.n_rows), int(out.n_slots)
         res = {name: arrays[name][:nr] for name, _ in _abi.COMPACT_ROW_FIELDS}
         res["features"] = arrays["features"][:, :nr]

@@ -964,6 +964,101 @@ def _call_compact(self, candidates_df: pd.DataFrame, soa: dict, t_0: float, t_1:
 HipCandidateScoring._call_compact = _call_compact
 
 
+class ResidentScores:
+    """The result of ``HipCandidateScoring.score_resident``: the candidates are scored, the tables stay in HBM.
+
+    ``order`` / ``prec_row`` map every table row to its candidate row and library row (``assemble_candidates``);
+    ``metadata`` is one row per table row with the ids ``perform_fdr_resident`` groups and breaks ties by;
+    ``frames(table_rows)`` copies the listed rows back (``Context.take_rows``) and builds the two frames
+    ``HipCandidateScoring.__call__`` returns, restricted to those rows.  Valid only until the next scoring call
+    or staging call on the same GPU."""
+
+    def __init__(self, scorer: "HipCandidateScoring", candidates_df: pd.DataFrame, soa: dict, serial: int):
+        self._scorer = scorer
+        self._candidates_df = candidates_df
+        self._serial = serial
+        self.order = soa["order"]
+        self.prec_row = soa["prec_row"]
+        self.metadata = pd.DataFrame({name: np.asarray(soa[name]) for name in
+                                      ("precursor_idx", "rank", "decoy", "elution_group_idx", "channel")})
+        self._columns = None
+
+    @property
+    def n_table(self) -> int:
+        return len(self.metadata)
+
+    @property
+    def device(self):
+        return self._scorer._ctx.device
+
+    @property
+    def rt_column(self) -> str:
+        return self._scorer.rt_column
+
+    def _check_current(self):
+        from alphadia_amd.runtime import HipBackendError
+
+        if self._scorer._ctx.tables_serial != self._serial:
+            raise HipBackendError("the device tables of this scoring call were replaced by a later one")
+
+    def feature_columns(self) -> list[str]:
+        """The columns of the features frame, in its order (the frame of no rows; nothing is copied)."""
+        if self._columns is None:
+            self._columns = list(self.frames(np.zeros(0, np.int64))[0].columns)
+        return self._columns
+
+    def table_column(self, name: str) -> np.ndarray:
+        """Column ``name`` of the features frame for every table row, for the columns that do not come from the
+        kernels: the candidate and library columns and ``n_K`` / ``n_R`` / ``n_P`` (``delta_rt`` needs the kernels'
+        ``rt_observed``: ``perform_fdr_resident`` derives it from the library rt on the device)."""
+        s = self._scorer
+        if name in ("n_K", "n_R", "n_P"):
+            return np.asarray(s._sequence_counts()[("n_K", "n_R", "n_P").index(name)]).take(self.prec_row)
+        if name in ("precursor_idx", "rank", "decoy", "elution_group_idx", "channel"):
+            return self.metadata[name].to_numpy()
+        if name in self._candidates_df.columns:
+            return self._candidates_df[name].to_numpy().take(self.order)
+        if name in s.precursors_flat_df.columns:
+            return s.precursors_flat_df[name].to_numpy().take(self.prec_row)
+        raise KeyError(f"{name!r} is neither a candidate nor a library column")
+
+    def frames(self, table_rows) -> tuple[pd.DataFrame, pd.DataFrame]:
+        """``(features_df, fragments_df)`` of the valid rows among ``table_rows``: the features frame in the order of
+        ``table_rows``, the fragments frame in table-row / slot order - columns, order and dtypes as ``__call__``.
+        One ``take_rows`` copy-out of those rows (sorted) is all that crosses PCIe."""
+        self._check_current()
+        s = self._scorer
+        table_rows = np.asarray(table_rows, dtype=np.int64)
+        sorted_rows = np.unique(table_rows)
+        comp = s._ctx.take_rows(sorted_rows)
+        # the row columns in the order asked for (comp["row"] is ascending: it is sorted_rows without invalid rows)
+        pos = np.searchsorted(comp["row"], table_rows)
+        found = pos < len(comp["row"])
+        found[found] = comp["row"][pos[found]] == table_rows[found]
+        pos = pos[found]
+        rows_part = {name: comp[name][pos] for name, _ in _abi.COMPACT_ROW_FIELDS}
+        rows_part["features"] = comp["features"][:, pos]
+        features_df = collect_candidates(
+            self._candidates_df, None, s.precursors_flat_df, s.rt_column, s.mobility_column, s.precursor_mz_column,
+            row_maps=(self.order, self.prec_row), sequence_counts=s._sequence_counts(), compact=rows_part)
+        fragments_df = collect_fragments_compact(comp, s.precursors_flat_df, self.prec_row)
+        return features_df, fragments_df
+
+
+def _score_resident(self, candidates_df: pd.DataFrame) -> ResidentScores:
+    """Score ``candidates_df`` into the device tables and copy nothing back (``adh_score_candidates_resident``):
+    the FDR stage runs on the tables in HBM (``perform_fdr_resident``) and ``ResidentScores.frames`` copies back
+    the rows it keeps."""
+    soa = assemble_candidates(
+        candidates_df, self.precursors_flat_df, self.precursor_mz_column, score_grouped=self.config.score_grouped,
+        reference_channel=self.config.reference_channel)
+    self._ctx.score_resident(pack_assembled(soa), self._kernel_config())
+    return ResidentScores(self, candidates_df, soa, self._ctx.tables_serial)
+
+
+HipCandidateScoring.score_resident = _score_resident
+
+
 def calculate_score_groups(input_df: pd.DataFrame, group_channels: bool = False) -> pd.DataFrame:
     """``score_group_idx`` for every row (reference: scoring/utils.py:269-410).
 

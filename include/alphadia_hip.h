@@ -295,6 +295,29 @@ int adh_score_uploaded(adh_handle_t *handle, const adh_scoring_config_t *config,
 int adh_get_device_tables(adh_handle_t *handle, adh_output_t *device_view);
 
 /*
+ * Resident extraction (alphadia/workflow/peptidecentric/peptidecentric.py:183-263 on one GPU): score into the
+ * handle's own padded tables and copy nothing to the host (the D2H counter of adh_transfer_counters does not move).
+ * Afterwards the tables are what adh_score_candidates leaves - adh_get_device_tables, adh_fdr_resident and
+ * adh_take_rows work on them; their width is top_k_fragments clamped to the longest library slice of the table, as
+ * the callers of adh_score_candidates choose it.  Fails with ADH_ERR_UNSUPPORTED while a communicator is attached
+ * (the tables are then a rank's shard plus a gather).
+ */
+int adh_score_candidates_resident(adh_handle_t *handle, const adh_candidates_t *candidates,
+                                  const adh_scoring_config_t *config);
+
+/*
+ * The listed rows of the current device tables, in the layout of adh_score_candidates_compact: the VALID rows among
+ * rows[0, n) in list order (a row listed twice comes back twice; invalid rows are skipped), features as
+ * [46][rows_capacity], and their filled fragment slots in (list position, slot) order.  `row` and `fragment_row`
+ * are table rows.  out->top_k must be the width of the device tables.  A count kernel over the listed rows, an
+ * exclusive scan, a pack kernel writing one dense block and ONE copy of its used bytes; every column travels.
+ * Errors: a row outside [0, rows of the tables) -> ADH_ERR_INVALID_ARGUMENT; no scored tables, or a run / library
+ * staged since they were scored -> ADH_ERR_NOT_STAGED; capacities too small -> n_rows / n_slots say what is
+ * needed and the call fails with ADH_ERR_INVALID_ARGUMENT, as the compact entry does.
+ */
+int adh_take_rows(adh_handle_t *handle, const int64_t *rows, int64_t n, adh_compact_output_t *out);
+
+/*
  * Layout of the packed device buffer that holds the tables of `rows` candidates (the buffer
  * adh_get_device_tables / adh_comm_gathered give views of): one entry per OutputPsmDF column
  * (alphadia/search/scoring/output.py:17-97) in buffer order, every table 256-byte aligned.  The computed
