@@ -358,10 +358,11 @@ struct adh_handle {
                                           // tables are rebuilt from it on the host instead of crossing PCIe
     void *slot_stage = nullptr;           // page-locked fragment_lib_slot staging when the caller passes none
     size_t slot_stage_bytes = 0;
-    // compacted copy-out of the fragment tables (adh_score_host.hip): per-row offsets + the filled slots of the six
-    // wire columns, on the device and in page-locked host memory; scan scratch
+    // compacted copy-out of the fragment tables (adh_score_host.hip): a block per chunk - per-row offsets + the filled
+    // slots of the six wire columns - on the device and in page-locked host memory; scan scratch; the chunks' totals
     void *cmp_dev = nullptr, *cmp_host = nullptr, *cmp_scan = nullptr;
     size_t cmp_dev_bytes = 0, cmp_host_bytes = 0, cmp_scan_bytes = 0;
+    uint32_t *cmp_tot_pinned = nullptr;     // filled slots of up to 4096 chunks, page-locked
     // adh_score_candidates_compact: per-row counts / offsets on the device, scan scratch, page-locked staging block
     void *cop_cnt = nullptr, *cop_scan = nullptr, *cop_stage = nullptr, *cop_dev = nullptr;
     size_t cop_cnt_bytes = 0, cop_scan_bytes = 0, cop_stage_bytes = 0, cop_dev_bytes = 0;
@@ -641,6 +642,7 @@ int adh_destroy(adh_handle_t *h) {
     if (h->cop_cnt) (void)hipFree(h->cop_cnt);
     if (h->cop_dev) (void)hipFree(h->cop_dev);
     if (h->cop_tot_pinned) (void)hipHostFree(h->cop_tot_pinned);
+    if (h->cmp_tot_pinned) (void)hipHostFree(h->cmp_tot_pinned);
     for (adh_handle::UpLane &l : h->up_lanes) {
         for (int k = 0; k < 2; ++k) {
             if (l.buf[k]) (void)hipHostFree(l.buf[k]);

@@ -966,11 +966,14 @@ __global__ void adh_rebuild_columns_kernel(DevCands c, const LibRec *__restrict_
     out.fragment_loss_type[t] = l.loss_type;
 }
 
-// ---- compacted copy-out of the fragment tables (round 4).  A candidate fills the first K of its top_k fragment slots
-// (K = fragments with signal: 4.6 of 12 on the headline) and 58 % of the 264 bytes per candidate that the five
-// computed fragment tables + fragment_lib_slot put on PCIe were zeros.  Per chunk of the pipeline: K per row, an
-// exclusive scan, the filled slots of the six columns packed behind each other; the offsets travel first (the host
-// needs the total to size the six copies), the host team expands them into the caller's padded tables.
+// ---- compacted copy-out of the fragment tables of the padded path.  A candidate fills the first K of its top_k fragment
+// slots (K = fragments with signal: 4.6 of 12 on the headline) and 58 % of the 264 bytes per candidate that the five
+// computed fragment tables + fragment_lib_slot put on PCIe are zeros.  Per chunk of the pipeline, behind its scoring
+// kernels: K per row, an exclusive scan, and a pack kernel that writes the filled slots of the six columns into ONE
+// block (PadBlock) and stores the chunk's total straight into page-locked memory - the host sizes the block's single
+// copy from it without a round trip behind the copy-out backlog (see adh_cop_pack_kernel for why no copy fetches it).
+// The host team expands the block into the caller's padded tables and fills the library / id columns in the same pass
+// (fill_host_rows).
 __global__ void adh_slot_count_kernel(const uint16_t *__restrict__ lib_slot, int64_t row0, int64_t n, int top_k,
                                       uint32_t *__restrict__ cnt) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -983,27 +986,47 @@ __global__ void adh_slot_count_kernel(const uint16_t *__restrict__ lib_slot, int
     cnt[i] = k;  // (entry n: 0, so that the scan's last entry is the total)
 }
 
-struct CompactCols {
-    float *f[5];
-    uint16_t *slot;
+// a chunk's block of R rows and S filled slots: [offsets u32 x (R + 1) | fragment_lib_slot u16 x S | mz_observed, height,
+// intensity, mass_error, correlation f32 x S]; every column starts on a multiple of 16 bytes
+struct PadBlock {
+    size_t slot, f[5], total;
+    __host__ __device__ PadBlock(uint64_t R, uint64_t S) {
+        size_t o = ((R + 1) * 4 + 15) & ~(size_t)15;
+        slot = o, o += (S * 2 + 15) & ~(size_t)15;
+        for (int j = 0; j < 5; ++j) f[j] = o, o += (S * 4 + 15) & ~(size_t)15;
+        total = o;
+    }
+};
+// where the block of the chunk that starts at row a sits in the staging buffers (device and host alike): room for every
+// slot filled, and 64 bytes of slack behind the last block (the host reads a row's 12 floats unmasked)
+struct PadLayout {
+    size_t per_row, total;
+    PadLayout(int64_t n, int top_k, int64_t n_chunks)
+        : per_row(4 + (size_t)top_k * 22), total((size_t)n * per_row + (size_t)(n_chunks + 1) * 1024 + 64) {}
+    size_t base(int64_t a, int64_t ci) const { return ((size_t)a * per_row + (size_t)ci * 1024 + 255) & ~(size_t)255; }
 };
 
-__global__ void adh_compact_kernel(DevOut t, int64_t row0, int64_t n, int top_k, const uint32_t *__restrict__ off,
-                                   CompactCols c) {
+// one thread per (row, slot) of the chunk; the offsets (block + 0) are the scanned counts
+__global__ void adh_pad_pack_kernel(DevOut t, int64_t row0, int64_t n, int top_k, unsigned char *__restrict__ block,
+                                    uint32_t *__restrict__ total) {
     const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t *off = reinterpret_cast<const uint32_t *>(block);
+    const uint32_t S = off[n];
+    if (id == 0) *total = S;  // (page-locked host memory)
     if (id >= n * top_k) return;
     const int64_t i = id / top_k;
     const int j = (int)(id - i * top_k);
     const uint32_t a = off[i], k = off[i + 1] - a;
     if ((uint32_t)j >= k) return;
+    const PadBlock L(n, S);
     const int64_t src = (row0 + i) * (int64_t)top_k + j;
     const size_t dst = (size_t)a + (size_t)j;
-    c.f[0][dst] = t.fragment_mz_observed[src];
-    c.f[1][dst] = t.fragment_height[src];
-    c.f[2][dst] = t.fragment_intensity[src];
-    c.f[3][dst] = t.fragment_mass_error[src];
-    c.f[4][dst] = t.fragment_correlation[src];
-    c.slot[dst] = t.fragment_lib_slot[src];
+    reinterpret_cast<uint16_t *>(block + L.slot)[dst] = t.fragment_lib_slot[src];
+    reinterpret_cast<float *>(block + L.f[0])[dst] = t.fragment_mz_observed[src];
+    reinterpret_cast<float *>(block + L.f[1])[dst] = t.fragment_height[src];
+    reinterpret_cast<float *>(block + L.f[2])[dst] = t.fragment_intensity[src];
+    reinterpret_cast<float *>(block + L.f[3])[dst] = t.fragment_mass_error[src];
+    reinterpret_cast<float *>(block + L.f[4])[dst] = t.fragment_correlation[src];
 }
 
 // ---- compacted, column-major copy-out of the operator path (round 5, adh_score_candidates_compact).  What the
@@ -1298,89 +1321,151 @@ void rebuild_host_rows(const adh_handle *h, const adh_candidates_t *c, adh_outpu
     }
 }
 
-// Compact buffers of a call of n rows cut at `cut`: [offsets: one uint32 per row + one per chunk][5 float columns and
-// the slot column, n * top_k entries each, a chunk's packed slots starting at cut[chunk] * top_k]
-struct CompactLayout {
-    size_t off_bytes, col_elems, total;
-    size_t off_of(int64_t a, int64_t ci) const { return (size_t)(a + ci) * 4; }  // byte offset of chunk ci's offsets
-    size_t col_f(int j) const { return off_bytes + (size_t)j * col_elems * 4; }
-    size_t col_slot() const { return off_bytes + 5 * col_elems * 4; }
-    CompactLayout(int64_t n, int64_t n_chunks, int top_k) {
-        off_bytes = ((size_t)(n + n_chunks) * 4 + 255) / 256 * 256;
-        col_elems = ((size_t)n * (size_t)top_k + 63) / 64 * 64;
-        total = off_bytes + col_elems * 22;
-    }
-};
-
-// rows [a, b) of a chunk that starts at row a0: the packed slots back into the caller's padded tables (zeros behind)
-void expand_host_rows(adh_output_t *out, uint16_t *slot_host, const unsigned char *cmp, const CompactLayout &lay, int64_t a0,
-                      int64_t ci, int64_t a, int64_t b) {
+// rows [lo, hi) of the chunk that starts at row a0 and has R rows, from its packed block (host copy): ONE pass that
+// writes every host column of a row - precursor_idx and rank, the five computed fragment columns and fragment_lib_slot
+// (when the caller asked for it) from the block, the library / id columns of the row's K filled slots from the host copy
+// of the library - with zeros behind the K filled slots.  Byte for byte what the copy of the padded tables plus
+// rebuild_host_rows write (skipped rows have no filled slot: zeros everywhere).
+void fill_host_rows(const adh_handle *h, const adh_candidates_t *c, adh_output_t *out, const unsigned char *blk, int64_t R,
+                    int64_t a0, int64_t lo, int64_t hi) {
     const int top_k = out->top_k;
-    const uint32_t *off = reinterpret_cast<const uint32_t *>(cmp + lay.off_of(a0, ci));
-    float *dst[5] = {out->fragment_mz_observed, out->fragment_height, out->fragment_intensity, out->fragment_mass_error,
-                     out->fragment_correlation};
-    const size_t base = (size_t)a0 * (size_t)top_k;
+    const LibRec *lib = h->h_lib.data();
+    const uint32_t *off = reinterpret_cast<const uint32_t *>(blk);
+    const PadBlock L((uint64_t)R, (uint64_t)off[R]);
+    const uint16_t *src_s = reinterpret_cast<const uint16_t *>(blk + L.slot);
     const float *src[5];
-    for (int j = 0; j < 5; ++j) src[j] = reinterpret_cast<const float *>(cmp + lay.col_f(j)) + base;
-    const uint16_t *src_s = reinterpret_cast<const uint16_t *>(cmp + lay.col_slot()) + base;
+    for (int j = 0; j < 5; ++j) src[j] = reinterpret_cast<const float *>(blk + L.f[j]);
+    float *const dst[5] = {out->fragment_mz_observed, out->fragment_height, out->fragment_intensity, out->fragment_mass_error,
+                           out->fragment_correlation};
+    uint16_t *const slot_out = out->fragment_lib_slot;  // (NULL: the caller did not ask for the slots)
+    uint8_t *const u8col[6] = {out->fragment_rank, out->fragment_position, out->fragment_number, out->fragment_type,
+                               out->fragment_charge, out->fragment_loss_type};
     if (top_k == 12) {
-        // the usual width (default.yaml:185): a row is three 16-byte vectors; the packed source is read unmasked (the
-        // buffer has slack behind its last entry) and cut to the row's k entries with a mask; streaming stores where the
-        // destination allows - the rows are not read again on this side
+        // the usual width (default.yaml:185), in tiles of 16 rows.  A tile's rows of every column are assembled in local
+        // buffers first, then each column's part of the tile leaves as one run of streaming stores (768 bytes of a 4-byte
+        // column, 192 of a byte column: whole cache lines, as tiles start on multiples of 16 rows) - one column after the
+        // other.  (Storing a row's 14 columns side by side with streaming stores left the core's write-combining buffers
+        // to be flushed half-filled: the host team took 2x as long as the copies it replaces.)  The packed source is
+        // read unmasked (a column has slack behind its last entry, the buffer behind its last block) and cut to the
+        // row's k entries with a mask.
         alignas(16) static const uint32_t kMask[13][12] = {
 #define ADH_M(k) {k > 0 ? ~0u : 0u, k > 1 ? ~0u : 0u, k > 2 ? ~0u : 0u, k > 3 ? ~0u : 0u, k > 4 ? ~0u : 0u, k > 5 ? ~0u : 0u, \
                   k > 6 ? ~0u : 0u, k > 7 ? ~0u : 0u, k > 8 ? ~0u : 0u, k > 9 ? ~0u : 0u, k > 10 ? ~0u : 0u, k > 11 ? ~0u : 0u}
             ADH_M(0), ADH_M(1), ADH_M(2), ADH_M(3), ADH_M(4), ADH_M(5), ADH_M(6), ADH_M(7), ADH_M(8), ADH_M(9), ADH_M(10), ADH_M(11), ADH_M(12)
 #undef ADH_M
         };
-        bool aligned = true;
-        for (int j = 0; j < 5; ++j) aligned = aligned && (reinterpret_cast<uintptr_t>(dst[j]) & 15u) == 0;
-        for (int64_t i = a; i < b; ++i) {
-            const uint32_t o = off[i - a0];
-            const uint32_t k = std::min<uint32_t>(off[i - a0 + 1] - o, 12u);
-            const size_t r0 = (size_t)i * 12;
-            const __m128 m0 = _mm_load_ps(reinterpret_cast<const float *>(kMask[k]));
-            const __m128 m1 = _mm_load_ps(reinterpret_cast<const float *>(kMask[k] + 4));
-            const __m128 m2 = _mm_load_ps(reinterpret_cast<const float *>(kMask[k] + 8));
-            for (int j = 0; j < 5; ++j) {
-                const float *sp = src[j] + o;
-                float *row = dst[j] + r0;
-                const __m128 v0 = _mm_and_ps(_mm_loadu_ps(sp), m0), v1 = _mm_and_ps(_mm_loadu_ps(sp + 4), m1),
-                             v2 = _mm_and_ps(_mm_loadu_ps(sp + 8), m2);
-                if (aligned) {
-                    _mm_stream_ps(row, v0);
-                    _mm_stream_ps(row + 4, v1);
-                    _mm_stream_ps(row + 8, v2);
-                } else {
-                    _mm_storeu_ps(row, v0);
-                    _mm_storeu_ps(row + 4, v1);
-                    _mm_storeu_ps(row + 8, v2);
+        constexpr int TR = 16;
+        alignas(64) float tf[8][TR * 12];    // 5 computed columns, mz_library, mz, fragment_precursor_idx (as bits)
+        alignas(64) uint8_t tb[6][TR * 12];  // fragment_rank, position, number, type, charge, loss_type
+        alignas(64) uint16_t ts[TR * 12];
+        alignas(64) uint32_t tp[TR];
+        alignas(64) uint8_t tr[TR];
+        float *const dstf[8] = {dst[0], dst[1], dst[2], dst[3], dst[4], out->fragment_mz_library, out->fragment_mz,
+                                reinterpret_cast<float *>(out->fragment_precursor_idx)};
+        auto put = [](void *d, const void *src_, size_t bytes, bool nt) {
+            if (nt && (reinterpret_cast<uintptr_t>(d) & 15u) == 0 && bytes % 16 == 0) {
+                for (size_t q = 0; q < bytes; q += 16)
+                    _mm_stream_si128(reinterpret_cast<__m128i *>(static_cast<char *>(d) + q),
+                                     _mm_load_si128(reinterpret_cast<const __m128i *>(static_cast<const char *>(src_) + q)));
+            } else {
+                memcpy(d, src_, bytes);
+            }
+        };
+        for (int64_t t0 = lo; t0 < hi;) {
+            const int64_t t1 = std::min<int64_t>(hi, (t0 / TR + 1) * TR);
+            const int m = (int)(t1 - t0);
+            const bool full = m == TR;
+            memset(tf[5], 0, sizeof(tf[5]) * 2);
+            memset(tb, 0, sizeof(tb));
+            memset(ts, 0, sizeof(ts));
+            for (int q = 0; q < m; ++q) {
+                const int64_t i = t0 + q;
+                const bool skip = c->flags && (c->flags[i] & ADH_FLAG_SKIP);
+                const uint32_t p = skip ? 0u : c->precursor_idx[i];
+                const uint8_t r = skip ? (uint8_t)0 : c->rank[i];
+                tp[q] = p;
+                tr[q] = r;
+                const uint32_t o = off[i - a0];
+                const uint32_t k = std::min<uint32_t>(off[i - a0 + 1] - o, 12u);
+                const __m128 m0 = _mm_load_ps(reinterpret_cast<const float *>(kMask[k]));
+                const __m128 m1 = _mm_load_ps(reinterpret_cast<const float *>(kMask[k] + 4));
+                const __m128 m2 = _mm_load_ps(reinterpret_cast<const float *>(kMask[k] + 8));
+                for (int j = 0; j < 5; ++j) {
+                    const float *sp = src[j] + o;
+                    float *row = tf[j] + q * 12;
+                    _mm_store_ps(row, _mm_and_ps(_mm_loadu_ps(sp), m0));
+                    _mm_store_ps(row + 4, _mm_and_ps(_mm_loadu_ps(sp + 4), m1));
+                    _mm_store_ps(row + 8, _mm_and_ps(_mm_loadu_ps(sp + 8), m2));
+                }
+                const __m128 pv = _mm_castsi128_ps(_mm_set1_epi32((int)p));
+                _mm_store_ps(tf[7] + q * 12, _mm_and_ps(pv, m0));
+                _mm_store_ps(tf[7] + q * 12 + 4, _mm_and_ps(pv, m1));
+                _mm_store_ps(tf[7] + q * 12 + 8, _mm_and_ps(pv, m2));
+                // the library columns of the k filled slots (zeros behind: the buffers were cleared)
+                const LibRec *base = lib + c->frag_start_idx[i];
+                for (uint32_t u = 0; u < k; ++u) {
+                    const int e = q * 12 + (int)u;
+                    const uint16_t sl = src_s[o + u];
+                    const LibRec &l = base[sl - 1];
+                    ts[e] = sl;
+                    tf[5][e] = l.mz_library;
+                    tf[6][e] = l.mz;
+                    tb[0][e] = r;
+                    tb[1][e] = l.position;
+                    tb[2][e] = l.number;
+                    tb[3][e] = l.type;
+                    tb[4][e] = l.charge;
+                    tb[5][e] = l.loss_type;
                 }
             }
-            const uint16_t *sp = src_s + o;
-            uint16_t *row = slot_host + r0;
-            for (uint32_t t = 0; t < 12; ++t) row[t] = t < k ? sp[t] : (uint16_t)0;
+            const size_t r0 = (size_t)t0 * 12;
+            for (int j = 0; j < 8; ++j) put(dstf[j] + r0, tf[j], (size_t)m * 48, full);
+            for (int j = 0; j < 6; ++j) put(u8col[j] + r0, tb[j], (size_t)m * 12, full);
+            if (slot_out) put(slot_out + r0, ts, (size_t)m * 24, full);
+            put(out->precursor_idx + t0, tp, (size_t)m * 4, full);
+            put(out->rank + t0, tr, (size_t)m, false);  // (16 bytes: a quarter of a line)
+            t0 = t1;
         }
         _mm_sfence();
         return;
     }
-    // any other width: plain loops (a memcpy / memset pair per row and column would be 36 M library calls per 3 M rows)
-    for (int64_t i = a; i < b; ++i) {
+    // any other width: plain loops
+    for (int64_t i = lo; i < hi; ++i) {
+        const bool skip = c->flags && (c->flags[i] & ADH_FLAG_SKIP);
+        const uint32_t p = skip ? 0u : c->precursor_idx[i];
+        const uint8_t r = skip ? (uint8_t)0 : c->rank[i];
+        out->precursor_idx[i] = p;
+        out->rank[i] = r;
         const uint32_t o = off[i - a0];
-        const int k = (int)(off[i - a0 + 1] - o);
+        const int k = (int)std::min<uint32_t>(off[i - a0 + 1] - o, (uint32_t)top_k);
         const size_t r0 = (size_t)i * (size_t)top_k;
-        for (int j = 0; j < 5; ++j) {
-            const float *sp = src[j] + o;
-            float *row = dst[j] + r0;
-            int t = 0;
-            for (; t < k; ++t) row[t] = sp[t];
-            for (; t < top_k; ++t) row[t] = 0.0f;
-        }
-        const uint16_t *sp = src_s + o;
-        uint16_t *row = slot_host + r0;
+        const LibRec *base = lib + c->frag_start_idx[i];
         int t = 0;
-        for (; t < k; ++t) row[t] = sp[t];
-        for (; t < top_k; ++t) row[t] = 0;
+        for (; t < k; ++t) {
+            const size_t d = r0 + (size_t)t;
+            const uint16_t s = src_s[o + t];
+            const LibRec &l = base[s - 1];
+            for (int j = 0; j < 5; ++j) dst[j][d] = src[j][o + t];
+            if (slot_out) slot_out[d] = s;
+            out->fragment_precursor_idx[d] = p;
+            out->fragment_rank[d] = r;
+            out->fragment_mz_library[d] = l.mz_library;
+            out->fragment_mz[d] = l.mz;
+            out->fragment_position[d] = l.position;
+            out->fragment_number[d] = l.number;
+            out->fragment_type[d] = l.type;
+            out->fragment_charge[d] = l.charge;
+            out->fragment_loss_type[d] = l.loss_type;
+        }
+        const size_t rest = (size_t)(top_k - t);
+        if (!rest) continue;
+        const size_t d = r0 + (size_t)t;
+        for (int j = 0; j < 5; ++j) memset(dst[j] + d, 0, rest * 4);
+        if (slot_out) memset(slot_out + d, 0, rest * 2);
+        memset(out->fragment_precursor_idx + d, 0, rest * 4);
+        memset(out->fragment_mz_library + d, 0, rest * 4);
+        memset(out->fragment_mz + d, 0, rest * 4);
+        for (int j = 0; j < 6; ++j) memset(u8col[j] + d, 0, rest);
     }
 }
 
@@ -1413,6 +1498,17 @@ bool host_rebuild_pays() {
     int least = 6;
     if (const char *env = getenv("ADH_REBUILD_MIN_THREADS")) least = atoi(env);
     return host_thread_share() >= least;
+}
+
+// Does the padded path copy the fragment tables out compacted (adh_pad_pack_kernel, fill_host_rows)?  The wire drops from
+// 449 to ~290 bytes per candidate, and the host team writes the 5 computed columns it no longer gets by DMA.  That pays
+// where the call waits for the link and the team keeps pace with it: a large table (ADH_COMPACT_MIN_ROWS, default
+// 1 000 000 rows) and at least 12 threads of host.  ADH_COMPACT_COPY_OUT=1 / =0 forces it on / off.
+bool compact_copy_out_pays(int64_t n) {
+    if (const char *env = getenv("ADH_COMPACT_COPY_OUT")) return atoi(env) != 0;
+    int64_t least_rows = 1000000;
+    if (const char *env = getenv("ADH_COMPACT_MIN_ROWS")) least_rows = atoll(env);
+    return host_thread_share() >= 12 && n >= least_rows;
 }
 
 }  // namespace
@@ -1534,6 +1630,10 @@ int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring
     if (cop)  // (a chunk's slot offsets are 32-bit words of the packed count)
         chunk = std::min<int64_t>(chunk, std::max<int64_t>((int64_t)(0xFFFFFFFFull / (uint64_t)top_k) - 1, 1));
     const bool rebuild = !cop && !resident && h->h_lib.size() == (size_t)h->n_lib && !getenv("ADH_DEBUG_COPY_ALL") && host_rebuild_pays();
+    // compacted copy-out of the fragment tables (see adh_slot_count_kernel, compact_copy_out_pays)
+    const bool compact_wanted = rebuild && top_k <= 65535 && compact_copy_out_pays(n);
+    if (compact_wanted)  // (a chunk's offsets are 32-bit)
+        chunk = std::min<int64_t>(chunk, std::max<int64_t>((int64_t)(0xFFFFFFFFull / (uint64_t)top_k) - 1, 1));
     uint16_t *slot_host = out->fragment_lib_slot;
     if (rebuild && !slot_host) {
         const size_t need = (size_t)n * (size_t)top_k * sizeof(uint16_t);
@@ -1567,31 +1667,35 @@ int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring
     const int first_div = first_div_env ? first_div_env : (n >= 4 * chunk ? 2 : ((n > 3 * chunk || h->tims_staged) ? 4 : 1));
     if (n > chunk) cut.push_back(std::max<int64_t>(chunk / first_div, 1));
     while (cut.back() < n) cut.push_back(std::min(n, cut.back() + chunk));
+    if (compact_wanted && cut.size() >= 4) {
+        // a short last chunk: the host team expands a block only once it has landed, so the team's work on the last
+        // block comes after the last copy (ADH_LAST_CHUNK_DIV: the last chunk's share, 1 = no split)
+        int last_div = 4;
+        if (const char *env = getenv("ADH_LAST_CHUNK_DIV")) last_div = std::max(atoi(env), 1);
+        const int64_t last = cut.back() - cut[cut.size() - 2];
+        if (last_div > 1 && last / last_div >= 256) cut.insert(cut.end() - 1, n - last / last_div);
+    }
     const int64_t n_chunks = (int64_t)cut.size() - 1;
-    // compacted copy-out of the fragment tables (see adh_slot_count_kernel).  OFF unless ADH_COMPACT_COPY_OUT=1: it takes
-    // a third of the bytes off PCIe (1.35 -> 0.86 GB per 3 M candidates) but hands the host team 0.9 GB of padded rows
-    // to write, and on the pool's boxes - 16 cores' worth of CPU quota - that costs more than the copies it saves
-    // (40.0 against 38.3 ms per step on the same box, 37.6 with 32 threads).  A host with cores to spare can turn it on.
-    const char *cmp_env = getenv("ADH_COMPACT_COPY_OUT");
-    const bool compact = rebuild && top_k <= 65535 && cmp_env && atoi(cmp_env) != 0;
-    const CompactLayout clay(n, n_chunks, top_k);
-    std::vector<hipEvent_t> &off_ready = aux_events;  // per chunk: its offsets are on the host
+    const bool compact = compact_wanted && n_chunks <= 4096;
+    const PadLayout play(n, top_k, n_chunks);
+    std::vector<hipEvent_t> &tot_ready = aux_events;  // per chunk: its pack kernel is done, its total on the host
     if (compact) {
-        if (h->cmp_dev_bytes < clay.total) {
+        if (h->cmp_dev_bytes < play.total) {
             HIP_TRY(hipDeviceSynchronize());
             if (h->cmp_dev) (void)hipFree(h->cmp_dev);
             h->cmp_dev = nullptr;
             h->cmp_dev_bytes = 0;
-            HIP_TRY(hipMalloc(&h->cmp_dev, clay.total + clay.total / 8));
-            h->cmp_dev_bytes = clay.total + clay.total / 8;
+            HIP_TRY(hipMalloc(&h->cmp_dev, play.total + play.total / 8));
+            h->cmp_dev_bytes = play.total + play.total / 8;
         }
-        if (h->cmp_host_bytes < clay.total) {
+        if (h->cmp_host_bytes < play.total) {
             if (h->cmp_host) (void)hipHostFree(h->cmp_host);
             h->cmp_host = nullptr;
             h->cmp_host_bytes = 0;
-            HIP_TRY(hipHostMalloc(&h->cmp_host, clay.total + clay.total / 8, hipHostMallocDefault));
-            h->cmp_host_bytes = clay.total + clay.total / 8;
+            HIP_TRY(hipHostMalloc(&h->cmp_host, play.total + play.total / 8, hipHostMallocDefault));
+            h->cmp_host_bytes = play.total + play.total / 8;
         }
+        if (!h->cmp_tot_pinned) HIP_TRY(hipHostMalloc((void **)&h->cmp_tot_pinned, 4096 * 4, hipHostMallocDefault));
         int64_t longest = 0;
         for (int64_t ci = 0; ci < n_chunks; ++ci) longest = std::max(longest, cut[(size_t)ci + 1] - cut[(size_t)ci]);
         size_t scan_bytes = 0;
@@ -1760,6 +1864,61 @@ int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring
         return hipSuccess;
     };
     unsigned char *const cmp_dev = static_cast<unsigned char *>(h->cmp_dev), *const cmp_host = static_cast<unsigned char *>(h->cmp_host);
+    // compacted copy-out: the host team expands landed blocks WHILE the later chunks are enqueued and scored - the
+    // enqueue loop waits for every chunk's pack kernel, so it lasts as long as the kernels, and a team started behind
+    // it (as the padded path's rebuild team is) had all blocks but none done at that point: 3 M candidates 25 - 30 ms,
+    // the team finishing 6 ms after the last copy.  The calling thread publishes chunks as their copies complete
+    // (fill_publish); worker w takes stripe w of T of every chunk.
+    const int fill_T = compact ? host_threads_for(n) : 0;
+    int fill_started = 0;
+    int64_t fill_published = 0;
+    struct FillTeam {  // (declared behind what its threads read: it is destroyed - joined - first)
+        std::vector<std::thread> threads;
+        std::atomic<int64_t> ready{0};
+        std::atomic<bool> abort{false};
+        void join_all() {
+            for (std::thread &t : threads)
+                if (t.joinable()) t.join();
+        }
+        ~FillTeam() {
+            abort.store(true);
+            join_all();
+        }
+    } fill_team;
+    auto fill_stripe = [&](int64_t ci, int w) {
+        const int64_t a = cut[(size_t)ci], b = cut[(size_t)ci + 1];
+        const int64_t lo = a + (b - a) * w / fill_T, hi = a + (b - a) * (w + 1) / fill_T;
+        if (hi > lo) fill_host_rows(h, c, out, cmp_host + play.base(a, ci), b - a, a, lo, hi);
+    };
+    auto fill_worker = [&](int w) {
+        for (int64_t ci = 0; ci < n_chunks; ++ci) {
+            // (waiting threads back off to short sleeps: a team that spins burns the CPU quota the busy ones need)
+            for (int spin = 0; fill_team.ready.load(std::memory_order_acquire) <= ci; ++spin) {
+                if (fill_team.abort.load(std::memory_order_relaxed)) return;
+                if (spin < 64) std::this_thread::yield();
+                else std::this_thread::sleep_for(std::chrono::microseconds(20));
+            }
+            fill_stripe(ci, w);
+        }
+    };
+    for (int w = 0; w < fill_T; ++w) {
+        try {
+            fill_team.threads.emplace_back(fill_worker, w);
+            ++fill_started;
+        } catch (const std::system_error &) {
+            break;  // (the calling thread takes the stripes that have no thread, at the end)
+        }
+    }
+    auto fill_publish = [&](bool wait) -> hipError_t {
+        while (fill_published < (int64_t)chunk_done.size()) {
+            const hipEvent_t ev = chunk_done[(size_t)fill_published];
+            const hipError_t q = wait ? hipEventSynchronize(ev) : hipEventQuery(ev);
+            if (q == hipErrorNotReady) return hipSuccess;
+            if (q != hipSuccess) return q;
+            fill_team.ready.store(++fill_published, std::memory_order_release);
+        }
+        return hipSuccess;
+    };
     const double t_1 = now();
     const bool dbg_events = timing && atoi(getenv("ADH_DEBUG_TIMING")) >= 2;  // per-chunk D2H spans
     std::vector<hipEvent_t> dbg;
@@ -1770,21 +1929,16 @@ int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring
         (void)hipGetLastError();
         return code;
     };
-    // packed fragment columns of chunk ci: wait for its offsets (its kernels are done then; the next chunk's are already
-    // queued), copy the filled part of the six columns, mark the chunk complete for the host team
+    // the packed block of chunk ci: wait for its pack kernel (an event on the scoring stream - the next chunk's kernels
+    // are already queued; never a copy behind the copy-out backlog), ONE copy of its used bytes, then mark the chunk
+    // complete for the host team
     auto flush_compact = [&](int64_t ci) -> int {
         const int64_t a = cut[(size_t)ci], b = cut[(size_t)ci + 1];
-        HIP_TRY(hipEventSynchronize(off_ready[(size_t)ci]));
-        const uint32_t total = reinterpret_cast<const uint32_t *>(cmp_host + clay.off_of(a, ci))[b - a];
-        if (total > 0) {
-            const size_t e0 = (size_t)a * (size_t)top_k;
-            for (int j = 0; j < 5; ++j)
-                HIP_TRY(hipMemcpyAsync(cmp_host + clay.col_f(j) + e0 * 4, cmp_dev + clay.col_f(j) + e0 * 4, (size_t)total * 4,
-                                       hipMemcpyDeviceToHost, so));
-            HIP_TRY(hipMemcpyAsync(cmp_host + clay.col_slot() + e0 * 2, cmp_dev + clay.col_slot() + e0 * 2, (size_t)total * 2,
-                                   hipMemcpyDeviceToHost, so));
-            h->d2h_bytes += (uint64_t)total * 22;
-        }
+        HIP_TRY(hipEventSynchronize(tot_ready[(size_t)ci]));
+        const PadBlock L((uint64_t)(b - a), (uint64_t)h->cmp_tot_pinned[ci]);
+        const size_t base = play.base(a, ci);
+        HIP_TRY(hipMemcpyAsync(cmp_host + base, cmp_dev + base, L.total, hipMemcpyDeviceToHost, so));
+        h->d2h_bytes += L.total;
         hipEvent_t ev = nullptr;
         int rc_e = get_event(h, &ev);
         if (rc_e != ADH_OK) return rc_e;
@@ -1813,6 +1967,7 @@ int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring
         const int64_t a = cut[(size_t)ci], b = cut[(size_t)ci + 1];
         const int ps = (int)(ci & 1);
         if (cop && cop_publish(false) != hipSuccess) return fail_sync(fail(ADH_ERR_HIP, "scoring pipeline (compact copy-out)"));
+        if (compact && fill_publish(false) != hipSuccess) return fail_sync(fail(ADH_ERR_HIP, "scoring pipeline (compacted copy-out)"));
         if (ci + 1 < n_chunks) {
             // plan of the next chunk: the other plan slot is free once the kernels of chunk ci - 1 are done
             const int64_t a2 = b, b2 = cut[(size_t)ci + 2];
@@ -1825,19 +1980,22 @@ int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring
         rc = plan_finish(h, h->slots[ps], cfg, a, b - a, p);
         if (rc == ADH_OK) rc = launch_scoring(h, p, cfg, &dev_k, sk);
         if (rc != ADH_OK) return fail_sync(rc);
-        if (compact) {  // filled slots per row, their offsets, the packed columns: behind the chunk's kernels
-            uint32_t *d_off = reinterpret_cast<uint32_t *>(cmp_dev + clay.off_of(a, ci));
+        if (compact) {  // filled slots per row, their offsets, the packed block: behind the chunk's kernels
+            unsigned char *blk = cmp_dev + play.base(a, ci);
+            uint32_t *d_off = reinterpret_cast<uint32_t *>(blk);
             const int64_t nr = b - a;
             hipLaunchKernelGGL(adh_slot_count_kernel, dim3((unsigned)((nr + 256) / 256)), dim3(256), 0, sk, dev.fragment_lib_slot, a,
                                nr, top_k, d_off);
             size_t scan_bytes = h->cmp_scan_bytes;
             HIP_TRY(hipcub::DeviceScan::ExclusiveSum(h->cmp_scan, scan_bytes, d_off, d_off, (int)(nr + 1), sk));
-            CompactCols cc;
-            for (int j = 0; j < 5; ++j) cc.f[j] = reinterpret_cast<float *>(cmp_dev + clay.col_f(j)) + (size_t)a * top_k;
-            cc.slot = reinterpret_cast<uint16_t *>(cmp_dev + clay.col_slot()) + (size_t)a * top_k;
-            hipLaunchKernelGGL(adh_compact_kernel, dim3((unsigned)((nr * top_k + 255) / 256)), dim3(256), 0, sk, dev, a, nr, top_k,
-                               d_off, cc);
+            hipLaunchKernelGGL(adh_pad_pack_kernel, dim3((unsigned)((nr * top_k + 255) / 256)), dim3(256), 0, sk, dev, a, nr, top_k,
+                               blk, h->cmp_tot_pinned + ci);
             HIP_TRY(hipGetLastError());
+            hipEvent_t ev = nullptr;  // (when the total can be read)
+            rc = get_event(h, &ev);
+            if (rc != ADH_OK) return fail_sync(rc);
+            HIP_TRY(hipEventRecord(ev, sk));
+            tot_ready.push_back(ev);
         }
         uint64_t *cop_off = cop ? static_cast<uint64_t *>(h->cop_cnt) + a + ci : nullptr;
         if (cop) {
@@ -1866,16 +2024,6 @@ int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring
             if (rc != ADH_OK) return fail_sync(rc);
         }
         HIP_TRY(hipStreamWaitEvent(so, h->ev_k[ps], 0));
-        if (compact) {
-            const size_t ob = clay.off_of(a, ci);
-            HIP_TRY(hipMemcpyAsync(cmp_host + ob, cmp_dev + ob, (size_t)(b - a + 1) * 4, hipMemcpyDeviceToHost, so));
-            h->d2h_bytes += (uint64_t)(b - a + 1) * 4;
-            hipEvent_t ev = nullptr;
-            rc = get_event(h, &ev);
-            if (rc != ADH_OK) return fail_sync(rc);
-            HIP_TRY(hipEventRecord(ev, so));
-            off_ready.push_back(ev);
-        }
         if (dbg_events) {
             hipEvent_t e0, e1;
             (void)hipEventCreate(&e0);
@@ -1951,7 +2099,18 @@ int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring
             return fail(ADH_ERR_INVALID_ARGUMENT, "compact output: rows_capacity / slots_capacity too small (n_rows / n_slots say what is needed)");
         }
     }
-    if (rebuild) {
+    if (compact) {
+        // the blocks still on their way, then the team (it has been expanding since the first block landed)
+        hipError_t ee = fill_publish(true);
+        if (ee == hipSuccess) fill_team.join_all();
+        if (ee != hipSuccess) {
+            fail(ADH_ERR_HIP, std::string("scoring pipeline (compacted copy-out): ") + hipGetErrorString(ee));
+            return fail_sync(ADH_ERR_HIP);
+        }
+        for (int64_t ci = 0; ci < n_chunks; ++ci)  // (stripes of threads that could not be started)
+            for (int w = fill_started; w < fill_T; ++w) fill_stripe(ci, w);
+        if (timing) fprintf(stderr, "[adh]   compacted copy-out: host team done %.2f ms after the call began (%d threads)\n", now() - t_0, fill_T);
+    } else if (rebuild) {
         // host threads follow the copy-out stream chunk by chunk: thread w takes the w-th stripe of every chunk
         const int T = host_threads_for(n);
         std::atomic<int64_t> ready{0};
@@ -1964,7 +2123,6 @@ int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring
                 }
                 const int64_t a = cut[(size_t)ci], b = cut[(size_t)ci + 1];
                 const int64_t lo = a + (b - a) * w / T, hi = a + (b - a) * (w + 1) / T;
-                if (compact) expand_host_rows(out, slot_host, cmp_host, clay, a, ci, lo, hi);
                 rebuild_host_rows(h, c, out, slot_host, lo, hi);
             }
         };
@@ -1985,7 +2143,6 @@ int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring
             const int64_t a = cut[(size_t)ci], b = cut[(size_t)ci + 1];
             auto stripe = [&](int w) {
                 const int64_t lo = a + (b - a) * w / T, hi = a + (b - a) * (w + 1) / T;
-                if (compact) expand_host_rows(out, slot_host, cmp_host, clay, a, ci, lo, hi);
                 rebuild_host_rows(h, c, out, slot_host, lo, hi);
             };
             stripe(0);
