@@ -664,9 +664,18 @@ RESIDENT_PROTOTYPES = {
 }
 
 
+# ... and of the accumulated resident tables (the optimisation loop)
+APPEND_PROTOTYPES = {
+    "adh_score_candidates_resident_append": [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)],
+    "adh_resident_reset": [C.c_void_p],
+    "adh_resident_counts": [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
+}
+
+
 def declare(lib) -> None:
-    """Argument types of the entries listed in RESIDENT_PROTOTYPES (the others are called with explicit casts)."""
-    for name, argtypes in RESIDENT_PROTOTYPES.items():
+    """Argument types of the entries listed in RESIDENT_PROTOTYPES and APPEND_PROTOTYPES (the others are called with
+    explicit casts)."""
+    for name, argtypes in {**RESIDENT_PROTOTYPES, **APPEND_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = C.c_int

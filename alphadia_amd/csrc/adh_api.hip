@@ -390,6 +390,14 @@ struct adh_handle {
     // the last scoring call's tables still belong to the staged run and library (adh_take_rows): staging either
     // ends that, although the tables themselves stay readable (materialise_tables)
     bool tables_current = false;
+    // accumulated resident tables (adh_resident_append.hip): while acc_live, tables[0] holds acc_rows rows laid out
+    // for acc_cap rows of acc_top_k slots, fully materialised (no column refers to the staged library or candidates),
+    // and acc_spare is the buffer the next batch is scored into
+    DevTables acc_spare;
+    int64_t acc_rows = 0, acc_cap = 0;
+    int acc_top_k = 0;
+    bool acc_live = false;
+    void *acc_counts = nullptr;     // two u64 of adh_resident_counts
     CandSlab cs;
     PlanSlot slots[2];
     Plan plan;                      // plan of the resident table (adh_upload_candidates / adh_score_uploaded)
@@ -661,6 +669,8 @@ int adh_destroy(adh_handle_t *h) {
     if (h->cmp_scan) (void)hipFree(h->cmp_scan);
     for (DevTables &t : h->tables)
         if (t.base) (void)hipFree(t.base);
+    if (h->acc_spare.base) (void)hipFree(h->acc_spare.base);
+    if (h->acc_counts) (void)hipFree(h->acc_counts);
     if (h->cs.base) (void)hipFree(h->cs.base);
     if (h->scratch_slab) (void)hipFree(h->scratch_slab);
     if (h->sel_slab) (void)hipFree(h->sel_slab);
@@ -827,7 +837,7 @@ int adh_stage_alpharaw(adh_handle_t *h, const adh_alpharaw_t *d) {
     {
         const int rc_m = materialise_tables(h);  // while the candidate table the last call scored is still the resident one
         if (rc_m != ADH_OK) return rc_m;
-        h->tables_current = false;
+        h->tables_current = h->tables_current && h->acc_live;  // (accumulated tables hold every column themselves)
     }
     HIP_TRY(hipDeviceSynchronize());
     h->run_buf.release();
@@ -1064,7 +1074,7 @@ int adh_stage_timstof(adh_handle_t *h, const adh_timstof_t *d) {
     {
         const int rc_m = materialise_tables(h);  // while the candidate table the last call scored is still the resident one
         if (rc_m != ADH_OK) return rc_m;
-        h->tables_current = false;
+        h->tables_current = h->tables_current && h->acc_live;  // (accumulated tables hold every column themselves)
     }
     HIP_TRY(hipDeviceSynchronize());
     h->run_buf.release();
@@ -1186,7 +1196,7 @@ int adh_stage_fragments(adh_handle_t *h, const adh_fragments_t *f) {
     {
         const int rc_m = materialise_tables(h);  // the last call's tables refer to the library that goes away
         if (rc_m != ADH_OK) return rc_m;
-        h->tables_current = false;
+        h->tables_current = h->tables_current && h->acc_live;  // (accumulated tables hold every column themselves)
     }
     HIP_TRY(hipDeviceSynchronize());
     h->lib_buf.release();
@@ -1931,3 +1941,4 @@ int adh_fragcomp_stats(adh_handle_t *h, double *kernel_ms, int64_t *pairs, int64
 #include "adh_fdr_device.hip"
 #include "adh_calibration.hip"
 #include "adh_take_rows.hip"
+#include "adh_resident_append.hip"

@@ -82,8 +82,7 @@ size_t layout_tables(unsigned char *base, int64_t rows, int top_k, adh_output_t 
     return std::max<size_t>(off, 256);
 }
 
-int ensure_tables(adh_handle *h, int slot, int64_t rows, int top_k) {
-    DevTables &t = h->tables[slot];
+int ensure_tables_in(DevTables &t, int64_t rows, int top_k) {
     const size_t need = layout_tables(nullptr, rows, top_k, nullptr, nullptr);
     if (t.bytes < need) {
         if (t.base) (void)hipFree(t.base);
@@ -101,6 +100,8 @@ int ensure_tables(adh_handle *h, int slot, int64_t rows, int top_k) {
     t.top_k = top_k;
     return ADH_OK;
 }
+
+int ensure_tables(adh_handle *h, int slot, int64_t rows, int top_k) { return ensure_tables_in(h->tables[slot], rows, top_k); }
 
 // ---------------------------------------------------------------- candidate columns in HBM
 struct CandColumn {
@@ -1537,6 +1538,8 @@ int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring
     const int top_k = out->top_k;
     h->plan = Plan();            // the resident table (adh_upload_candidates) is replaced
     h->cands_uploaded = false;
+    h->acc_live = false;         // ... and so are accumulated tables (adh_score_candidates_resident_append)
+    h->acc_rows = 0;
     rc = cand_reserve(h, n, c->n_isotope_cols);
     if (rc != ADH_OK) return rc;
     // device tables: with a communicator attached the layout is padded to the largest shard and

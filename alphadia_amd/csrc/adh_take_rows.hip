@@ -102,11 +102,8 @@ __global__ void __launch_bounds__(256) pack_kernel(DevOut t, const int64_t *__re
     }
 }
 
-}  // namespace take
-
-extern "C" {
-
-int adh_score_candidates_resident(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring_config_t *cfg) {
+// the checks of a resident scoring call and the shape of its tables (rows, width) in `shape`
+int resident_shape(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring_config_t *cfg, adh_output_t &shape) {
     if (!h || !c || !cfg) return fail(ADH_ERR_INVALID_ARGUMENT, "NULL argument");
     if (h->comm_attached())
         return fail(ADH_ERR_UNSUPPORTED, "resident scoring with a communicator attached (the tables are a shard plus a gather)");
@@ -117,9 +114,20 @@ int adh_score_candidates_resident(adh_handle_t *h, const adh_candidates_t *c, co
     // to a huge length, the clamp makes that top_k and the pipeline rejects the table)
     uint32_t longest = 0;
     for (int64_t i = 0; i < c->n; ++i) longest = std::max<uint32_t>(longest, c->frag_stop_idx[i] - c->frag_start_idx[i]);
-    adh_output_t shape{};
+    shape = adh_output_t{};
     shape.n = c->n;
     shape.top_k = c->n == 0 ? 1 : (int32_t)std::max<uint32_t>(1u, std::min<uint32_t>(cfg->top_k_fragments, std::max<uint32_t>(longest, 1u)));
+    return ADH_OK;
+}
+
+}  // namespace take
+
+extern "C" {
+
+int adh_score_candidates_resident(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring_config_t *cfg) {
+    adh_output_t shape{};
+    const int rc = take::resident_shape(h, c, cfg, shape);
+    if (rc != ADH_OK) return rc;
     return score_pipeline(h, c, cfg, &shape, nullptr, true);
 }
 

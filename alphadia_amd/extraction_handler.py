@@ -24,6 +24,7 @@ from __future__ import annotations
 import logging
 import time
 
+import numpy as np
 import pandas as pd
 
 from alphadia_amd.fragcomp import candidate_hash
@@ -58,6 +59,7 @@ class HipExtractionHandler:
         self._selection_handler = selection_handler
         self._device = device
         self._fallbacks_logged: set[str] = set()
+        self._optlock = None  # the lock of the last process_optimization_batch (filter_for_calibration)
         # extraction_handler.py:390-398
         self._selection_config = CandidateSelectionConfig()
         search = config["search"]
@@ -181,19 +183,7 @@ class HipExtractionHandler:
         psm_df = psm_df[psm_df["qval"].to_numpy() <= fdr_config["fdr"]]
         self._reporter.log_string("Removing fragments below FDR threshold")
         precursor_df, fragments_df = resident.frames(psm_df["table_row"].to_numpy())
-        if len(precursor_df) != len(psm_df):
-            raise RuntimeError("the FDR stage kept rows the scoring call marked invalid")
-        if too_few:  # perform_fdr's answer for too few PSMs (fdr.py:125-137): qval, then proba, no _decoy
-            precursor_df["qval"] = 1.0
-            precursor_df["proba"] = 1.0
-        else:
-            precursor_df["_decoy"] = psm_df["_decoy"].to_numpy()
-            precursor_df["proba"] = psm_df["proba"].to_numpy()
-            precursor_df["qval"] = psm_df["qval"].to_numpy()
-            if competed:  # the columns FragmentCompetition leaves behind (fragcomp.py:291-299)
-                precursor_df["_candidate_idx"] = candidate_hash(precursor_df["precursor_idx"].to_numpy(),
-                                                                precursor_df["rank"].to_numpy())
-                precursor_df["valid"] = True
+        _attach_fdr_columns(precursor_df, psm_df, too_few, competed)
         precursor_df["candidate_idx"] = candidate_hash(precursor_df["precursor_idx"].to_numpy(),
                                                        precursor_df["rank"].to_numpy())
         fragments_df["candidate_idx"] = candidate_hash(fragments_df["precursor_idx"].to_numpy(),
@@ -230,6 +220,104 @@ class HipExtractionHandler:
                              "fdr_ms": (t_3 - t_2) * 1e3, "filter_ms": (t_4 - t_3) * 1e3, "total_ms": (t_4 - t_0) * 1e3}
         return precursor_df, fragments_df
 
+    # ------------------------------------------------------------------ the optimisation loop
+    def _log_fallback(self, reason: str, what: str, logged: set[str]) -> None:
+        key = f"{what}: {reason}"
+        if key not in logged:
+            logged.add(key)
+            self._reporter.log_string(f"{what} not used: {reason}", verbosity="info")
+            logger.info("%s not used: %s", what.lower(), reason)
+
+    def process_optimization_batch(self, dia_data, optlock) -> pd.DataFrame:
+        """The python branch of ``OptimizationHandler._process_batch`` (optimization_handler.py:381-456) for a
+        ``HipOptimizationLock``: select on the batch library, score the candidates behind the rows the lock has
+        accumulated in HBM, run the FDR stage over all of them there (``fit_predict_resident``: the classifier
+        version, seed draw and column order of ``fit_predict(optlock.features_df, ..., df_fragments=
+        optlock.fragments_df)``) and ``optlock.update_with_fdr``.  Returns one row per FDR output row - the ids,
+        ``decoy``, ``channel``, ``_decoy``, ``proba``, ``qval`` and ``table_row`` - enough for ``update_with_fdr``
+        and ``log_precursor_df``; ``filter_for_calibration`` builds ``_filter_dfs``'s frames from it.  Channel-wise
+        FDR, an FDR manager that is not a ``HipFDRManager`` and an attached communicator take the chained calls
+        instead; the frame returned is then ``fit_predict``'s.  The reason is logged once per lock (the workflow
+        creates a handler per step).  The caller logs "=== Extracting elution groups ..." before and the classifier
+        version after, as ``_process_batch`` does; this method logs the "=== Extracted ..." line."""
+        t_0 = time.perf_counter()
+        library = optlock.batch_library
+        candidates_df = self.select_candidates(dia_data, library)
+        reason = self.resident_refusal()
+        if reason is not None:
+            self._log_fallback(reason, "Resident optimisation step", getattr(optlock, "fallbacks_logged",
+                                                                             self._fallbacks_logged))
+            return self._process_optimization_batch_chained(candidates_df, dia_data, optlock, t_0)
+        t_1 = time.perf_counter()
+        optlock.append_resident(self._candidate_scoring(dia_data, library), candidates_df)
+        t_2 = time.perf_counter()
+        psm_df = self._fdr_manager.fit_predict_resident(
+            optlock.resident, competitive=self._config["fdr"]["competitive_scoring"],
+            version=getattr(self._optimization_manager, "classifier_version", -1))
+        psm_df.attrs["resident"] = True
+        t_3 = time.perf_counter()
+        self._reporter.log_string(
+            f"=== Extracted {optlock.n_features} precursors and {optlock.n_fragments} fragments ===",
+            verbosity="progress")
+        optlock.update_with_fdr(psm_df)
+        self._optlock = optlock
+        self.last_timings = {"path": "resident", "select_ms": (t_1 - t_0) * 1e3, "score_ms": (t_2 - t_1) * 1e3,
+                             "fdr_ms": (t_3 - t_2) * 1e3, "total_ms": (time.perf_counter() - t_0) * 1e3}
+        return psm_df
+
+    def _process_optimization_batch_chained(self, candidates_df, dia_data, optlock, t_0=None) -> pd.DataFrame:
+        """optimization_handler.py:405-451 as written: the lock concatenates host frames, the FDR stage stages them."""
+        fdr_config = self._config["fdr"]
+        t_1 = time.perf_counter()
+        features_df, fragments_df = self.score_and_quantify_candidates(candidates_df, dia_data, optlock.batch_library)
+        optlock.update_with_extraction(features_df, fragments_df)
+        t_2 = time.perf_counter()
+        precursor_df = self._fdr_manager.fit_predict(
+            optlock.features_df,
+            decoy_strategy="precursor_channel_wise" if fdr_config["channel_wise_fdr"] else "precursor",
+            competitive=fdr_config["competitive_scoring"],
+            df_fragments=optlock.fragments_df,
+            version=getattr(self._optimization_manager, "classifier_version", -1),
+        )
+        t_3 = time.perf_counter()
+        self._reporter.log_string(
+            f"=== Extracted {optlock.n_features} precursors and {optlock.n_fragments} fragments ===",
+            verbosity="progress")
+        optlock.update_with_fdr(precursor_df)
+        self._optlock = optlock
+        t_0 = t_1 if t_0 is None else t_0
+        self.last_timings = {"path": "chained", "select_ms": (t_1 - t_0) * 1e3, "score_ms": (t_2 - t_1) * 1e3,
+                             "fdr_ms": (t_3 - t_2) * 1e3, "total_ms": (time.perf_counter() - t_0) * 1e3}
+        return precursor_df
+
+    def filter_for_calibration(self, psm_df: pd.DataFrame, config) -> tuple[pd.DataFrame, pd.DataFrame]:
+        """``OptimizationHandler._filter_dfs(psm_df, optlock.fragments_df)`` (optimization_handler.py:518-574) for
+        the lock of the last ``process_optimization_batch``: the targets at ``qval < 0.01`` with the columns
+        ``fit_predict`` gives them, and the best fragments of their precursors for calibration.  After a resident
+        step only those precursors' rows and fragments cross PCIe, and both frames come with a fresh RangeIndex;
+        after a chained step this is ``_filter_dfs`` itself, and the frames keep the indexes it leaves them."""
+        from alphadia_amd.optimization import filter_fragments_for_calibration
+
+        calibration = config["calibration"]
+        optlock = self._optlock
+        keep = (psm_df["qval"] < 0.01) & (psm_df["decoy"] == 0)
+        if not psm_df.attrs.get("resident", False):
+            precursor_df = psm_df[keep]
+            fragments_df = filter_fragments_for_calibration(optlock.fragments_df, precursor_df["precursor_idx"],
+                                                            calibration["min_correlation"], calibration["max_fragments"])
+            return precursor_df, fragments_df
+        psm_kept = psm_df[keep]
+        resident = optlock.resident
+        pidx = psm_kept["precursor_idx"].to_numpy()
+        fragment_rows = np.flatnonzero(np.isin(resident.metadata["precursor_idx"].to_numpy(), pidx))
+        precursor_df, fragments_df = resident.frames(psm_kept["table_row"].to_numpy(), fragments_of=fragment_rows)
+        _attach_fdr_columns(precursor_df, psm_kept, bool(psm_df.attrs.get("too_few_psms", False)),
+                            bool(psm_df.attrs.get("fragment_competition", False)))
+        fragments_df = filter_fragments_for_calibration(fragments_df, pidx, calibration["min_correlation"],
+                                                        calibration["max_fragments"])
+        self._reporter.log_string(f"fragments_df: keeping {len(fragments_df)} of {optlock.n_fragments}")
+        return precursor_df, fragments_df.reset_index(drop=True)
+
     def quantify_candidates(self, candidates_df, precursor_fdr_df, dia_data, spectral_library,
                             top_k_fragments: int | None = None):
         """extraction_handler.py:488-507: scoring and quantification are one pass here too."""
@@ -238,6 +326,23 @@ class HipExtractionHandler:
             candidates_df, dia_data, spectral_library, top_k_fragments
         )
         return None, fragments_df
+
+
+def _attach_fdr_columns(precursor_df: pd.DataFrame, psm_df: pd.DataFrame, too_few: bool, competed: bool) -> None:
+    """The columns perform_fdr adds to the features frame, for the frame of ``psm_df``'s rows in its order."""
+    if len(precursor_df) != len(psm_df):
+        raise RuntimeError("the FDR stage kept rows the scoring call marked invalid")
+    if too_few:  # perform_fdr's answer for too few PSMs (fdr.py:125-137): qval, then proba, no _decoy
+        precursor_df["qval"] = 1.0
+        precursor_df["proba"] = 1.0
+    else:
+        precursor_df["_decoy"] = psm_df["_decoy"].to_numpy()
+        precursor_df["proba"] = psm_df["proba"].to_numpy()
+        precursor_df["qval"] = psm_df["qval"].to_numpy()
+        if competed:  # the columns FragmentCompetition leaves behind (fragcomp.py:291-299)
+            precursor_df["_candidate_idx"] = candidate_hash(precursor_df["precursor_idx"].to_numpy(),
+                                                            precursor_df["rank"].to_numpy())
+            precursor_df["valid"] = True
 
 
 def resident_refusal(config, fdr_manager, comm_attached) -> str | None:

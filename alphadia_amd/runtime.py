@@ -77,6 +77,9 @@ EXPORTED_SYMBOLS = [
     "adh_calibration_time_ms",
     "adh_score_candidates_resident",
     "adh_take_rows",
+    "adh_score_candidates_resident_append",
+    "adh_resident_reset",
+    "adh_resident_counts",
 ]
 
 
@@ -602,6 +605,21 @@ class Context:
     def zero_device_tables(self, stream: int = 0) -> None:
         _check(lib.adh_zero_device_tables(self._h, C.c_void_p(stream)), "adh_zero_device_tables")
 
+    def table_rows_to_host(self, name: str, start: int, stop: int) -> np.ndarray:
+        """Rows [start, stop) of the device table ``name`` (of the current tables), copied to the host."""
+        view = self.device_tables()
+        shape, dt = _abi.output_shapes(int(view.n), int(view.top_k), extras=True)[name]
+        if not 0 <= start <= stop <= int(view.n):
+            raise ValueError(f"rows [{start}, {stop}) outside the {int(view.n)} rows of the device tables")
+        row_shape = tuple(shape[1:])
+        a = np.empty((stop - start,) + row_shape, dtype=dt)
+        ptr = C.cast(getattr(view, name), C.c_void_p).value
+        if a.nbytes:
+            row_bytes = int(np.prod(row_shape, dtype=np.int64)) * np.dtype(dt).itemsize
+            _check(lib.adh_copy_to_host(self._h, a.ctypes.data_as(C.c_void_p), C.c_void_p(ptr + start * row_bytes),
+                                        C.c_uint64(a.nbytes)), "adh_copy_to_host")
+        return a
+
     def device_tables_to_host(self, names=None) -> dict:
         view = self.device_tables()
         return self._view_to_host(view, int(view.n), names)
@@ -756,6 +774,29 @@ class Context:
         _check(lib.adh_score_candidates_resident(self._h, cands.ref(), C.byref(cfg)), "adh_score_candidates_resident")
         self.n_candidates = n
         return _abi.output_width(cands, int(cfg_jit.top_k_fragments))
+
+    def score_resident_append(self, cands: _abi.Marshalled, cfg_jit) -> tuple[int, int]:
+        """``adh_score_candidates_resident_append``: score behind the rows accumulated since the last
+        ``resident_reset`` (or the last other scoring call).  Returns ``(first_row, width)``: the table row of the
+        batch's first candidate and the width of the accumulated tables."""
+        cfg = _abi.pack_config(cfg_jit)
+        first = C.c_int64(0)
+        self.tables_serial += 1
+        _check(lib.adh_score_candidates_resident_append(self._h, cands.ref(), C.byref(cfg), C.byref(first)),
+               "adh_score_candidates_resident_append")
+        self.n_candidates = int(cands.struct.n)
+        return int(first.value), int(self.device_tables().top_k)
+
+    def resident_reset(self) -> None:
+        """``adh_resident_reset``: the device tables are empty; the next append starts at row 0."""
+        self.tables_serial += 1
+        _check(lib.adh_resident_reset(self._h), "adh_resident_reset")
+
+    def resident_counts(self) -> tuple[int, int]:
+        """``adh_resident_counts``: (valid rows, their filled fragment slots) of the current device tables."""
+        rows, slots = C.c_int64(0), C.c_int64(0)
+        _check(lib.adh_resident_counts(self._h, C.byref(rows), C.byref(slots)), "adh_resident_counts")
+        return int(rows.value), int(slots.value)
 
     def take_rows(self, rows) -> dict:
         """``adh_take_rows``: the valid rows among the table rows ``rows`` of the current device tables, in list order,

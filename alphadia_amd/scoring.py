@@ -1059,6 +1059,160 @@ def _score_resident(self, candidates_df: pd.DataFrame) -> ResidentScores:
 HipCandidateScoring.score_resident = _score_resident
 
 
+class AccumulatedScores:
+    """The rows of several scoring calls accumulated in the device tables of one GPU
+    (``adh_score_candidates_resident_append``): the features and fragments frames of the optimisation lock
+    (``OptimizationLock.features_df`` / ``fragments_df``) without a copy to the host.
+
+    Each appended batch keeps its scorer (and with it the library frame as it was when the batch was scored: the
+    scorer holds its own sorted copy) and its candidate table; its rows are ``[first_row, first_row + n)`` of the
+    tables.  Has the interface ``HipFDRManager.fit_predict_resident`` reads from a ``ResidentScores`` (``metadata``,
+    ``feature_columns``, ``table_column``, ``rt_column``, ``device``) for all rows at once.  Creating it empties the
+    device tables (``adh_resident_reset``)."""
+
+    def __init__(self, device: int | None = None):
+        from alphadia_amd import runtime
+
+        self._ctx = runtime.get_context(device)
+        self._ctx.resident_reset()
+        self._serial = self._ctx.tables_serial
+        self.batches: list[ResidentScores] = []
+        self.first_rows: list[int] = []
+        self._metadata = None
+        self._columns = None
+
+    @property
+    def n_table(self) -> int:
+        return sum(b.n_table for b in self.batches)
+
+    @property
+    def device(self):
+        return self._ctx.device
+
+    @property
+    def rt_column(self) -> str:
+        return self.batches[0].rt_column
+
+    def _check_current(self):
+        from alphadia_amd.runtime import HipBackendError
+
+        if self._ctx.tables_serial != self._serial:
+            raise HipBackendError("the accumulated device tables were replaced by a later scoring call")
+
+    def append(self, scorer: "HipCandidateScoring", candidates_df: pd.DataFrame) -> int:
+        """Score ``candidates_df`` behind the rows accumulated so far; returns the table row of its first candidate."""
+        self._check_current()
+        if scorer._ctx is not self._ctx:
+            raise ValueError("the scorer runs on another GPU than the accumulated tables")
+        soa = assemble_candidates(
+            candidates_df, scorer.precursors_flat_df, scorer.precursor_mz_column,
+            score_grouped=scorer.config.score_grouped, reference_channel=scorer.config.reference_channel)
+        first, _width = self._ctx.score_resident_append(pack_assembled(soa), scorer._kernel_config())
+        if first != self.n_table:
+            from alphadia_amd.runtime import HipBackendError
+
+            raise HipBackendError(f"appended at row {first}, {self.n_table} rows were accumulated")
+        self._serial = self._ctx.tables_serial
+        self.batches.append(ResidentScores(scorer, candidates_df, soa, self._serial))
+        self.first_rows.append(first)
+        self._metadata = None
+        return first
+
+    @property
+    def metadata(self) -> pd.DataFrame:
+        """The ids of every table row (``ResidentScores.metadata`` of the batches, one after the other)."""
+        if self._metadata is None:
+            frames = [b.metadata for b in self.batches]
+            self._metadata = pd.concat(frames, ignore_index=True) if frames else pd.DataFrame(
+                {c: np.zeros(0, np.int64) for c in ("precursor_idx", "rank", "decoy", "elution_group_idx", "channel")})
+        return self._metadata
+
+    def feature_columns(self) -> list[str]:
+        """The columns of the features frame, in its order (nothing is copied)."""
+        if self._columns is None:
+            self._columns = list(self._segment_frames(np.zeros(0, np.int64), keep_empty=True)[0][0].columns)
+        return self._columns
+
+    def table_column(self, name: str) -> np.ndarray:
+        """``ResidentScores.table_column`` over every table row (each batch from its own scorer's library frame)."""
+        return np.concatenate([b.table_column(name) for b in self.batches])
+
+    def counts(self) -> tuple[int, int]:
+        """(rows of the features frame, rows of the fragments frame): the valid rows and their filled slots."""
+        self._check_current()
+        return self._ctx.resident_counts()
+
+    def valid(self, start: int = 0, stop: int | None = None) -> np.ndarray:
+        """The valid flags of table rows [start, stop) (default: all; one byte per row crosses PCIe)."""
+        self._check_current()
+        stop = self.n_table if stop is None else int(stop)
+        if not 0 <= start <= stop <= self.n_table:
+            raise ValueError(f"rows [{start}, {stop}) outside the {self.n_table} accumulated rows")
+        return self._ctx.table_rows_to_host("valid", start, stop).astype(bool)
+
+    def _segment_frames(self, sorted_rows: np.ndarray, keep_empty: bool = False) -> list[tuple]:
+        """The frames of the valid rows among ``sorted_rows`` (ascending, unique), one entry per batch - what that
+        batch's ``__call__`` returns restricted to those rows, each with its own RangeIndex - as
+        ``(features_df, fragments_df, table rows of the features rows, table rows of the fragments rows)``.  One
+        ``take_rows`` copy-out.  Batches without a row are left out unless ``keep_empty``."""
+        self._check_current()
+        if not self.batches:
+            raise ValueError("no rows accumulated")
+        comp = self._ctx.take_rows(sorted_rows)
+        crow = comp["row"].astype(np.int64)
+        frow = comp["fragment_row"].astype(np.int64)
+        out = []
+        for b, first in zip(self.batches, self.first_rows, strict=True):
+            lo, hi = np.searchsorted(crow, [first, first + b.n_table])
+            flo, fhi = np.searchsorted(frow, [first, first + b.n_table])
+            if hi == lo and not keep_empty:
+                continue
+            part = {name: comp[name][lo:hi] for name, _ in _abi.COMPACT_ROW_FIELDS}
+            part["row"] = crow[lo:hi] - first
+            part["features"] = comp["features"][:, lo:hi]
+            part.update({name: comp[name][flo:fhi] for name, _ in _abi.COMPACT_SLOT_FIELDS})
+            part["fragment_row"] = frow[flo:fhi] - first
+            s = b._scorer
+            features_df = collect_candidates(
+                b._candidates_df, None, s.precursors_flat_df, s.rt_column, s.mobility_column, s.precursor_mz_column,
+                row_maps=(b.order, b.prec_row), sequence_counts=s._sequence_counts(), compact=part)
+            out.append((features_df, collect_fragments_compact(part, s.precursors_flat_df, b.prec_row),
+                        crow[lo:hi], frow[flo:fhi]))
+        return out
+
+    def batch_frames(self) -> tuple[list[pd.DataFrame], list[pd.DataFrame]]:
+        """Every batch's ``(features_df, fragments_df)`` as its chained scoring call returns them: the lists the
+        reference's lock concatenates.  Copies every valid row back."""
+        if not self.batches:
+            return [], []
+        parts = self._segment_frames(np.arange(self.n_table, dtype=np.int64), keep_empty=True)
+        return [p[0] for p in parts], [p[1] for p in parts]
+
+    def frames(self, table_rows, fragments_of=None) -> tuple[pd.DataFrame, pd.DataFrame]:
+        """``(features_df, fragments_df)`` of the valid rows among ``table_rows``: the features frame in the order of
+        ``table_rows``, the fragments frame in table-row / slot order, both with a fresh RangeIndex.
+        ``fragments_of`` (table rows) selects the rows whose fragments come back instead of ``table_rows``.  One
+        ``take_rows`` copy-out of the rows involved."""
+        table_rows = np.asarray(table_rows, dtype=np.int64)
+        frag_rows = table_rows if fragments_of is None else np.asarray(fragments_of, dtype=np.int64)
+        parts = self._segment_frames(np.union1d(table_rows, frag_rows))
+        if not parts:  # (the frames of no rows, for their columns and dtypes)
+            parts = self._segment_frames(np.zeros(0, np.int64), keep_empty=True)[:1]
+        feats = pd.concat([p[0] for p in parts], ignore_index=True)
+        frags = pd.concat([p[1] for p in parts], ignore_index=True)
+        rows = np.concatenate([p[2] for p in parts])  # (ascending: the batches in order, each in row order)
+        pos = np.searchsorted(rows, table_rows)
+        found = pos < len(rows)
+        found[found] = rows[pos[found]] == table_rows[found]
+        pos = pos[found]
+        if not np.array_equal(pos, np.arange(len(rows))):
+            feats = feats.iloc[pos].reset_index(drop=True)
+        if fragments_of is not None and not np.isin(table_rows, frag_rows).all():
+            keep = np.isin(np.concatenate([p[3] for p in parts]), frag_rows)
+            frags = frags[keep].reset_index(drop=True)
+        return feats, frags
+
+
 def calculate_score_groups(input_df: pd.DataFrame, group_channels: bool = False) -> pd.DataFrame:
     """``score_group_idx`` for every row (reference: scoring/utils.py:269-410).
 

@@ -318,6 +318,31 @@ int adh_score_candidates_resident(adh_handle_t *handle, const adh_candidates_t *
 int adh_take_rows(adh_handle_t *handle, const int64_t *rows, int64_t n, adh_compact_output_t *out);
 
 /*
+ * Accumulated resident tables (the optimisation lock of alphadia/workflow/optimizers/optimization_lock.py: every step
+ * scores one more batch and runs the FDR stage over all rows since the last reset).  Scores `candidates` as
+ * adh_score_candidates_resident does and puts their rows behind the rows already accumulated: row i of an earlier
+ * batch stays row i, and *first_row is the row of the batch's first candidate.  Afterwards the device tables
+ * (adh_get_device_tables, adh_fdr_resident, adh_take_rows, adh_resident_counts) hold rows [0, n) of every batch since
+ * the last reset, with the width of the widest batch (narrower rows have zeroed slots behind theirs: byte for byte
+ * the tables one adh_score_candidates_resident call over all the batches leaves).  Each row keeps the library values
+ * of the time it was scored; staging another library or run afterwards leaves the accumulated tables readable.  A
+ * batch that needs more rows or wider slots moves the rows in HBM into a new layout; capacity grows geometrically.
+ * Any other scoring call, and adh_resident_reset, ends the accumulation; a failed append ends it too.  Fails with
+ * ADH_ERR_UNSUPPORTED while a communicator is attached.
+ */
+int adh_score_candidates_resident_append(adh_handle_t *handle, const adh_candidates_t *candidates,
+                                         const adh_scoring_config_t *config, int64_t *first_row);
+
+/* empty the device tables (the next adh_score_candidates_resident_append starts at row 0); keeps the memory */
+int adh_resident_reset(adh_handle_t *handle);
+
+/*
+ * The valid rows of the current device tables and their filled fragment slots: the row counts of the features and
+ * fragments frames the tables stand for.  A count kernel over rows [0, n) and a 16-byte copy.  Errors as adh_take_rows.
+ */
+int adh_resident_counts(adh_handle_t *handle, int64_t *valid_rows, int64_t *filled_slots);
+
+/*
  * Layout of the packed device buffer that holds the tables of `rows` candidates (the buffer
  * adh_get_device_tables / adh_comm_gathered give views of): one entry per OutputPsmDF column
  * (alphadia/search/scoring/output.py:17-97) in buffer order, every table 256-byte aligned.  The computed
