@@ -672,10 +672,29 @@ APPEND_PROTOTYPES = {
 }
 
 
+# ... and of the cross-run fragment quantity matrices (adh_quant_*)
+QUANT_MAX_COLUMNS = 16
+_u8p, _u32p, _f32p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_float)
+QUANT_PROTOTYPES = {
+    "adh_quant_create": [C.c_void_p, C.c_int32, _u32p, C.c_int64, C.POINTER(C.c_void_p)],
+    "adh_quant_destroy": [C.c_void_p],
+    "adh_quant_add_run": [C.c_void_p, C.c_int64, _u32p, _u8p, _u8p, _u8p, _u8p, C.POINTER(_f32p),
+                          C.POINTER(C.c_int64)],
+    "adh_quant_build": [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)],
+    "adh_quant_keys": [C.c_void_p, _i64p, _u32p],
+    "adh_quant_matrix": [C.c_void_p, C.c_int32, _f32p],
+    "adh_quant_rows": [C.c_void_p, _i64p, _u32p, _u32p, C.POINTER(_f32p)],
+    "adh_quant_set_matrix": [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(_f32p)],
+    "adh_quant_filter": [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_double, C.c_double, _f32p,
+                         C.POINTER(C.c_double), _u8p],
+    "adh_quant_time_ms": [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)],
+}
+
+
 def declare(lib) -> None:
-    """Argument types of the entries listed in RESIDENT_PROTOTYPES and APPEND_PROTOTYPES (the others are called with
-    explicit casts)."""
-    for name, argtypes in {**RESIDENT_PROTOTYPES, **APPEND_PROTOTYPES}.items():
+    """Argument types of the entries listed in RESIDENT_PROTOTYPES, APPEND_PROTOTYPES and QUANT_PROTOTYPES (the others
+    are called with explicit casts)."""
+    for name, argtypes in {**RESIDENT_PROTOTYPES, **APPEND_PROTOTYPES, **QUANT_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = C.c_int

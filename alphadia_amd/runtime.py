@@ -80,6 +80,16 @@ EXPORTED_SYMBOLS = [
     "adh_score_candidates_resident_append",
     "adh_resident_reset",
     "adh_resident_counts",
+    "adh_quant_create",
+    "adh_quant_destroy",
+    "adh_quant_add_run",
+    "adh_quant_build",
+    "adh_quant_keys",
+    "adh_quant_matrix",
+    "adh_quant_rows",
+    "adh_quant_set_matrix",
+    "adh_quant_filter",
+    "adh_quant_time_ms",
 ]
 
 
@@ -1054,6 +1064,12 @@ class Context:
         _check(lib.adh_calibration_time_ms(self._h, C.byref(ms)), "adh_calibration_time_ms")
         return float(ms.value)
 
+    # -- fragment quantity matrices (label-free quantification) -----------
+    def quant_matrices(self, n_columns: int, psm_precursor_idx) -> DeviceQuant:
+        """An empty ``adh_quant_t``: the cross-run quantity matrices of ``n_columns`` float32 columns over the frag
+        rows whose precursor is in ``psm_precursor_idx``."""
+        return DeviceQuant(self, n_columns, psm_precursor_idx)
+
 
 class DeviceMlp:
     """An ``adh_mlp_t``: the classifier network with its parameters, optimiser moments and the
@@ -1168,6 +1184,114 @@ class DeviceMlp:
     def time_ms(self):
         a, b = C.c_double(0.0), C.c_double(0.0)
         _check(lib.adh_mlp_time_ms(self._m, C.byref(a), C.byref(b)), "adh_mlp_time_ms")
+        return float(a.value), float(b.value)
+
+
+class DeviceQuant:
+    """An ``adh_quant_t``: the kept frag rows of every run, then their union of ion keys and one column-major
+    ``n_keys x n_runs`` float32 matrix per quantity column, in HBM (include/alphadia_hip.h: adh_quant_*)."""
+
+    def __init__(self, ctx: Context, n_columns: int, psm_precursor_idx):
+        self._ctx = ctx  # keeps the handle alive
+        self.n_columns = int(n_columns)
+        psm = np.ascontiguousarray(psm_precursor_idx, dtype=np.uint32)
+        self._q = C.c_void_p()
+        _check(lib.adh_quant_create(ctx._h, self.n_columns, psm.ctypes.data_as(C.POINTER(C.c_uint32)), psm.shape[0],
+                                    C.byref(self._q)), "adh_quant_create")
+        self.n_runs = 0
+        self.n_rows = 0
+        self.n_keys = 0
+        self.duplicate = False
+
+    def close(self):
+        if self._q:
+            lib.adh_quant_destroy(self._q)
+            self._q = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _cols(arrays):
+        return (C.POINTER(C.c_float) * max(len(arrays), 1))(*[a.ctypes.data_as(C.POINTER(C.c_float)) for a in arrays])
+
+    def add_run(self, precursor_idx, number, type_, charge, loss_type, columns) -> int:
+        """Append one run (uint32 precursor_idx, four uint8 columns, ``n_columns`` float32 columns); returns the rows
+        kept."""
+        p = _abi.as_c(precursor_idx, np.uint32)
+        b = [_abi.as_c(x, np.uint8) for x in (number, type_, charge, loss_type)]
+        cols = [_abi.as_c(x, np.float32) for x in columns]
+        n = p.shape[0]
+        if len(cols) != self.n_columns or any(x.shape != (n,) for x in [*b, *cols]):
+            raise ValueError("add_run: every column must hold one value per row, one array per quantity column")
+        kept = C.c_int64(0)
+        u8 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint8))  # noqa: E731
+        _check(lib.adh_quant_add_run(self._q, n, p.ctypes.data_as(C.POINTER(C.c_uint32)), *[u8(x) for x in b],
+                                     self._cols(cols), C.byref(kept)), "adh_quant_add_run")
+        self.n_runs += 1
+        self.n_rows += int(kept.value)
+        return int(kept.value)
+
+    def build(self) -> tuple[int, bool]:
+        """The union of keys and the matrices; returns ``(n_keys, duplicate)``."""
+        nk, dup = C.c_int64(0), C.c_int32(0)
+        _check(lib.adh_quant_build(self._q, C.byref(nk), C.byref(dup)), "adh_quant_build")
+        self.n_keys, self.duplicate = int(nk.value), bool(dup.value)
+        return self.n_keys, self.duplicate
+
+    def keys(self):
+        ion = np.empty(self.n_keys, dtype=np.int64)
+        pidx = np.empty(self.n_keys, dtype=np.uint32)
+        _check(lib.adh_quant_keys(self._q, ion.ctypes.data_as(C.POINTER(C.c_int64)),
+                                  pidx.ctypes.data_as(C.POINTER(C.c_uint32))), "adh_quant_keys")
+        return ion, pidx
+
+    def matrix(self, column: int) -> np.ndarray:
+        """Quantity column ``column`` as a C-ordered ``(n_runs, n_keys)`` float32 array (one row per run)."""
+        out = np.empty((self.n_runs, self.n_keys), dtype=np.float32)
+        _check(lib.adh_quant_matrix(self._q, int(column), out.ctypes.data_as(C.POINTER(C.c_float))), "adh_quant_matrix")
+        return out
+
+    def rows(self):
+        """The appended rows in run order: ``(ion, precursor_idx, run, [columns])``."""
+        n = self.n_rows
+        ion, pidx, run = np.empty(n, np.int64), np.empty(n, np.uint32), np.empty(n, np.uint32)
+        cols = [np.empty(n, np.float32) for _ in range(self.n_columns)]
+        _check(lib.adh_quant_rows(self._q, ion.ctypes.data_as(C.POINTER(C.c_int64)),
+                                  pidx.ctypes.data_as(C.POINTER(C.c_uint32)), run.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                  self._cols(cols)), "adh_quant_rows")
+        return ion, pidx, run, cols
+
+    def set_matrix(self, run_columns) -> None:
+        """A fresh one-column object takes its quality matrix from the host: one float32 array per run."""
+        cols = [_abi.as_c(x, np.float32) for x in run_columns]
+        n = cols[0].shape[0] if cols else 0
+        if any(c.shape != (n,) for c in cols):
+            raise ValueError("set_matrix: run columns differ in length")
+        _check(lib.adh_quant_set_matrix(self._q, n, len(cols), self._cols(cols)), "adh_quant_set_matrix")
+        self.n_runs, self.n_keys = len(cols), n
+
+    def filter(self, column: int, group, n_groups: int, top_n: float, threshold: float):
+        """``(total, rank, mask)`` of ``adh_quant_filter`` over matrix ``column``."""
+        g = _abi.as_c(group, np.int32)
+        if g.shape != (self.n_keys,):
+            raise ValueError("filter: one group code per key row")
+        total = np.empty(self.n_keys, np.float32)
+        rank = np.empty(self.n_keys, np.float64)
+        mask = np.empty(self.n_keys, np.uint8)
+        _check(lib.adh_quant_filter(self._q, int(column), g.ctypes.data_as(C.POINTER(C.c_int32)), int(n_groups),
+                                    float(top_n), float(threshold), total.ctypes.data_as(C.POINTER(C.c_float)),
+                                    rank.ctypes.data_as(C.POINTER(C.c_double)), mask.ctypes.data_as(C.POINTER(C.c_uint8))),
+               "adh_quant_filter")
+        return total, rank, mask.view(np.bool_)
+
+    def time_ms(self):
+        """HIP-event times (ms) of the build and of the last filter."""
+        a, b = C.c_double(0.0), C.c_double(0.0)
+        _check(lib.adh_quant_time_ms(self._q, C.byref(a), C.byref(b)), "adh_quant_time_ms")
         return float(a.value), float(b.value)
 
 

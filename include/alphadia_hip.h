@@ -731,6 +731,52 @@ int adh_calibration_predict(adh_handle_t *handle, const adh_loess_model_t *model
 /* Summed HIP-event duration (ms) of the kernels of the last adh_calibration_predict call. */
 int adh_calibration_time_ms(adh_handle_t *handle, double *kernel_ms);
 
+/* ------------------------------------------------------------------------------------------
+ * Cross-run fragment quantity matrices of label-free quantification
+ * (outputtransform/quantification/fragment_accumulator.py:51-101, quant_builder.py:52-182).
+ * The frag rows of every run whose precursor is among the PSMs are appended in HBM, the union of
+ * their ion keys over the runs is built with one stable radix sort, and each quantity column is
+ * scattered into a zero-filled column-major n_keys x n_runs float32 matrix (NaN -> 0, fillna(0)).
+ * The matrices stay in HBM for the filter calls that follow.
+ * ------------------------------------------------------------------------------------------ */
+
+#define ADH_QUANT_MAX_COLUMNS 16
+typedef struct adh_quant adh_quant_t;
+
+/* An empty accumulation of n_columns float32 quantity columns; psm_precursor_idx: the PSMs' precursors, sorted and
+ * distinct (the frag rows of other precursors are dropped). */
+int adh_quant_create(adh_handle_t *handle, int32_t n_columns, const uint32_t *psm_precursor_idx, int64_t n_psm,
+                     adh_quant_t **quant);
+int adh_quant_destroy(adh_quant_t *quant);
+/* Append one run's frag table (n rows; columns[n_columns] float32 arrays): its rows of PSM precursors, with the ion
+ * key precursor_idx + number << 32 + type << 40 + charge << 48 + loss_type << 56 in int64.  n_kept: rows kept. */
+int adh_quant_add_run(adh_quant_t *quant, int64_t n, const uint32_t *precursor_idx, const uint8_t *number,
+                      const uint8_t *type, const uint8_t *charge, const uint8_t *loss_type, const float *const *columns,
+                      int64_t *n_kept);
+/* The union of keys and the matrices.  One run: its kept rows in their order.  Two or more: the distinct keys in
+ * ascending (signed) order.  If a run holds a key twice, *duplicate = 1, no matrix is built and the rows stay
+ * readable through adh_quant_rows (the reference's merge makes a cartesian product of such keys). */
+int adh_quant_build(adh_quant_t *quant, int64_t *n_keys, int32_t *duplicate);
+/* ion[n_keys] (int64) and precursor_idx[n_keys] of the built union */
+int adh_quant_keys(adh_quant_t *quant, int64_t *ion, uint32_t *precursor_idx);
+/* quantity column `column` as n_keys x n_runs float32, column-major (run r at out + r * n_keys) */
+int adh_quant_matrix(adh_quant_t *quant, int32_t column, float *out);
+/* the appended rows in run order: ion, precursor_idx, run, columns[n_columns] (NaN as given) */
+int adh_quant_rows(adh_quant_t *quant, int64_t *ion, uint32_t *precursor_idx, uint32_t *run, float *const *columns);
+/* A fresh one-column object takes a quality matrix from the host instead (run_columns[n_runs] of n_keys floats). */
+int adh_quant_set_matrix(adh_quant_t *quant, int64_t n_keys, int32_t n_runs, const float *const *run_columns);
+/*
+ * QuantBuilder.filter_frag_df (quant_builder.py:132-182) over matrix `column`: total[i] = the float32 mean of row i
+ * over the runs, summed run after run as NumPy reduces the frame's F-ordered values; rank[i] =
+ * rank(ascending=False, method="first") of total inside group[i] (codes 0 .. n_groups - 1; a negative code or a NaN
+ * total gives NaN, as pandas does); mask[i] = rank <= top_n | total > threshold (compared in float64: pass the
+ * threshold in the precision of the comparison it stands for).
+ */
+int adh_quant_filter(adh_quant_t *quant, int32_t column, const int32_t *group, int32_t n_groups, double top_n,
+                     double threshold, float *total, double *rank, uint8_t *mask);
+/* HIP-event times (ms) of the device work of adh_quant_build and of the last adh_quant_filter */
+int adh_quant_time_ms(adh_quant_t *quant, double *build_ms, double *filter_ms);
+
 #ifdef __cplusplus
 }
 #endif
