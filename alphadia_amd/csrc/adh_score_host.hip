@@ -1512,6 +1512,79 @@ bool compact_copy_out_pays(int64_t n) {
     return host_thread_share() >= 12 && n >= least_rows;
 }
 
+// The hand-off of landed blocks to a host team (the compacted copy-outs).  The enqueue thread only appends the event
+// that follows a block's copy (append).  Whichever thread of the team runs out of work first becomes the watcher: it
+// waits on the oldest event nobody has waited for, runs `landed` for that chunk and publishes it.  So a block reaches
+// the team when its copy ends, wherever the enqueue thread happens to be (it sleeps a chunk long waiting for the next
+// pack total; a poll from there found a block either at once or one chunk - 2.6 ms - late).  Nobody spins: the watcher
+// sits in hipEventSynchronize, the others back off to short sleeps (a team that spins burns the CPU quota the busy
+// ones need; a team woken all at once from a condition variable took 3 - 8 ms over a 500 000-row block instead of
+// 1.5 - 2.5 and ended 3 - 17 ms behind the last copy: profiles/headline_pipeline.json, `condition_variable`).
+// The events live in an array sized for every chunk
+// before a thread starts: the enqueue thread writes entry `appended` and then raises the count, the watcher - one at
+// a time, the role is claimed with `watching` - reads entries below it; what `landed` writes is published with `ready`.
+struct BlockHandoff {
+    std::vector<hipEvent_t> events;
+    std::atomic<int64_t> appended{0}, ready{0};
+    std::atomic<bool> watching{false}, abort{false};
+    hipError_t error = hipSuccess;  // (written by a watcher before it raises `abort`)
+    int device = 0;
+    std::function<void(int64_t)> landed;  // once per chunk, in order, before the chunk is published
+
+    BlockHandoff(int64_t n_chunks, int device_) : events((size_t)std::max<int64_t>(n_chunks, 0), nullptr), device(device_) {}
+    int append(hipEvent_t ev) {  // (the enqueue thread only)
+        const int64_t k = appended.load(std::memory_order_relaxed);
+        if (k >= (int64_t)events.size())  // (an event nobody would ever wait for: a waiter of its chunk would hang)
+            return fail(ADH_ERR_INVALID_ARGUMENT, "scoring pipeline: more copy-out events than chunks");
+        events[(size_t)k] = ev;
+        appended.store(k + 1, std::memory_order_release);
+        return ADH_OK;
+    }
+    void stop() { abort.store(true, std::memory_order_release); }  // (an early return: whoever still waits gives up)
+    // true once chunk ci has landed; false when the call is given up or a wait has failed (`error`)
+    bool wait_for(int64_t ci) {
+        for (int spin = 0;; ++spin) {
+            if (ready.load(std::memory_order_acquire) > ci) return true;
+            if (abort.load(std::memory_order_acquire)) return false;
+            if (appended.load(std::memory_order_acquire) > ready.load(std::memory_order_relaxed) &&
+                !watching.exchange(true, std::memory_order_acq_rel)) {
+                const int64_t k = ready.load(std::memory_order_acquire);  // (nobody else moves it while the role is held)
+                if (k < appended.load(std::memory_order_acquire)) {
+                    hipError_t q = hipSetDevice(device);
+                    if (q == hipSuccess) q = hipEventSynchronize(events[(size_t)k]);
+                    if (q == hipSuccess && landed) landed(k);
+                    if (q == hipSuccess) {
+                        ready.store(k + 1, std::memory_order_release);
+                    } else {
+                        error = q;
+                        abort.store(true, std::memory_order_release);
+                    }
+                }
+                watching.store(false, std::memory_order_release);
+                spin = 0;
+                continue;
+            }
+            if (spin < 64) std::this_thread::yield();
+            else std::this_thread::sleep_for(std::chrono::microseconds(20));
+        }
+    }
+};
+
+// the threads that follow a BlockHandoff (declared behind what they read: it is destroyed - joined - first)
+struct HandoffTeam {
+    BlockHandoff &handoff;
+    std::vector<std::thread> threads;
+    explicit HandoffTeam(BlockHandoff &handoff_) : handoff(handoff_) {}
+    void join_all() {
+        for (std::thread &t : threads)
+            if (t.joinable()) t.join();
+    }
+    ~HandoffTeam() {
+        handoff.stop();
+        join_all();
+    }
+};
+
 }  // namespace
 
 namespace {
@@ -1530,6 +1603,7 @@ int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring
             return fail(ADH_ERR_INVALID_ARGUMENT, "output buffer is NULL");
     HIP_TRY(hipSetDevice(h->device));
     const bool timing = getenv("ADH_DEBUG_TIMING") != nullptr;  // developer switch: stage times to stderr
+    const bool dbg_events = timing && atoi(getenv("ADH_DEBUG_TIMING")) >= 2;  // per-chunk D2H spans, hand-off times
     auto now = [] {
         return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
     };
@@ -1681,6 +1755,14 @@ int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring
     const int64_t n_chunks = (int64_t)cut.size() - 1;
     const bool compact = compact_wanted && n_chunks <= 4096;
     const PadLayout play(n, top_k, n_chunks);
+    // ADH_DEBUG_TIMING=2, the hand-off of every packed block on the host's clock (ms after the call began): its total
+    // seen by the enqueue thread, the team told that it has landed, every thread of the team done with its stripe
+    // (one entry per chunk and thread: each thread writes its own)
+    const int dbg_T = dbg_events ? host_threads_for(n) : 0;
+    std::vector<double> dbg_tot_seen(dbg_events ? (size_t)n_chunks : 0, 0.0), dbg_told(dbg_tot_seen.size(), 0.0);
+    std::vector<double> dbg_stripe_done(dbg_tot_seen.size() * (size_t)dbg_T, 0.0), dbg_stripe_took(dbg_stripe_done.size(), 0.0);
+    std::vector<hipEvent_t> dbg_k;  // scoring stream, per chunk: before its kernels, behind them, behind its helpers
+    double dbg_start_host = 0.0;    // the host's clock when dbg_start was recorded
     std::vector<hipEvent_t> &tot_ready = aux_events;  // per chunk: its pack kernel is done, its total on the host
     if (compact) {
         if (h->cmp_dev_bytes < play.total) {
@@ -1799,29 +1881,31 @@ int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring
     };
     // host threads unpack finished blocks into the caller's arrays WHILE the later chunks are enqueued and scored (the
     // enqueue loop waits for every chunk's totals, so it takes as long as the kernels: with the team started behind it
-    // the unpacking - 2 ms per 450 000-row block - came on top: 32 ms per 3 M candidates).  The calling thread
-    // publishes blocks as their copies complete (cop_publish), thread w takes stripe w of T of every block.
-    // base[ci] / cnt[ci] are written once, before `ready` passes ci, and never again: a worker reads only its own
-    // chunk's pair (a chunk that does not fit - and every one behind it - is published with a count of 0).
+    // the unpacking - 2 ms per 450 000-row block - came on top: 32 ms per 3 M candidates).  The team takes the blocks
+    // as their copies complete (BlockHandoff; flush_cop appends the events), thread w takes stripe w of T of every block.
+    // base[ci] / cnt[ci] are written once, by the watcher of chunk ci before it publishes the chunk, and never again:
+    // a worker reads only its own chunk's pair (a chunk that does not fit - and every one behind it - is published
+    // with a count of 0).
     std::vector<int64_t> cop_base_r((size_t)n_chunks + 1, 0), cop_base_s((size_t)n_chunks + 1, 0);
     std::vector<int64_t> cop_cnt_r((size_t)n_chunks, 0), cop_cnt_s((size_t)n_chunks, 0);
     bool cop_overflow = false;
-    int64_t cop_published = 0;
     const int cop_T = cop ? host_threads_for(n) : 0;
     int cop_started = 0;
-    struct CopTeam {  // (declared behind what its threads read: it is destroyed - joined - first)
-        std::vector<std::thread> threads;
-        std::atomic<int64_t> ready{0};
-        std::atomic<bool> abort{false};
-        void join_all() {
-            for (std::thread &t : threads)
-                if (t.joinable()) t.join();
-        }
-        ~CopTeam() {  // (an early return: whoever still waits for a block gives up)
-            abort.store(true);
-            join_all();
-        }
-    } cop_team;
+    BlockHandoff cop_handoff(cop ? n_chunks : 0, h->device);
+    cop_handoff.landed = [&](int64_t ci) {
+        const uint64_t tot = cop_tot_host[(size_t)ci];
+        cop_base_r[(size_t)ci + 1] = cop_base_r[(size_t)ci] + (int64_t)(tot >> 32);
+        cop_base_s[(size_t)ci + 1] = cop_base_s[(size_t)ci] + (int64_t)(tot & 0xFFFFFFFFull);
+        if (cop_base_r[(size_t)ci + 1] > cop->rows_capacity || cop_base_s[(size_t)ci + 1] > cop->slots_capacity)
+            cop_overflow = true;
+        // count on (the caller learns what it needs); an overflowing chunk and all behind it copy nothing
+        cop_cnt_r[(size_t)ci] = cop_overflow ? 0 : (int64_t)(tot >> 32);
+        cop_cnt_s[(size_t)ci] = cop_overflow ? 0 : (int64_t)(tot & 0xFFFFFFFFull);
+        if (timing)
+            fprintf(stderr, "[adh]   compact chunk %lld: %lld rows, %lld slots on the host %.2f ms after the call began\n",
+                    (long long)ci, (long long)(tot >> 32), (long long)(tot & 0xFFFFFFFFull), now() - t_0);
+    };
+    HandoffTeam cop_team(cop_handoff);
     auto cop_stripe = [&](int64_t ci, int w) {
         if (cop_cnt_r[(size_t)ci] == 0 && cop_cnt_s[(size_t)ci] == 0) return;
         cop_copy_stripe(cop_stage + cop_lay.base(cut[(size_t)ci], ci), cop_cnt_r[(size_t)ci], cop_cnt_s[(size_t)ci],
@@ -1829,104 +1913,62 @@ int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring
     };
     auto cop_worker = [&](int w) {
         for (int64_t ci = 0; ci < n_chunks; ++ci) {
-            while (cop_team.ready.load(std::memory_order_acquire) <= ci) {
-                if (cop_team.abort.load(std::memory_order_relaxed)) return;
-                std::this_thread::yield();
-            }
+            if (!cop_handoff.wait_for(ci)) return;
             cop_stripe(ci, w);
         }
-    };
-    for (int w = 0; w < cop_T; ++w) {
-        try {
-            cop_team.threads.emplace_back(cop_worker, w);
-            ++cop_started;
-        } catch (const std::system_error &) {
-            break;
-        }
-    }
-    auto cop_publish = [&](bool wait) -> hipError_t {
-        while (cop_published < (int64_t)chunk_done.size()) {
-            const int64_t ci = cop_published;
-            const hipError_t q = wait ? hipEventSynchronize(chunk_done[(size_t)ci]) : hipEventQuery(chunk_done[(size_t)ci]);
-            if (q == hipErrorNotReady) return hipSuccess;
-            if (q != hipSuccess) return q;
-            const uint64_t tot = cop_tot_host[(size_t)ci];
-            cop_base_r[(size_t)ci + 1] = cop_base_r[(size_t)ci] + (int64_t)(tot >> 32);
-            cop_base_s[(size_t)ci + 1] = cop_base_s[(size_t)ci] + (int64_t)(tot & 0xFFFFFFFFull);
-            if (cop_base_r[(size_t)ci + 1] > cop->rows_capacity || cop_base_s[(size_t)ci + 1] > cop->slots_capacity)
-                cop_overflow = true;
-            // count on (the caller learns what it needs); an overflowing chunk and all behind it copy nothing
-            cop_cnt_r[(size_t)ci] = cop_overflow ? 0 : (int64_t)(tot >> 32);
-            cop_cnt_s[(size_t)ci] = cop_overflow ? 0 : (int64_t)(tot & 0xFFFFFFFFull);
-            if (timing)
-                fprintf(stderr, "[adh]   compact chunk %lld: %lld rows, %lld slots on the host %.2f ms after the call began\n",
-                        (long long)ci, (long long)(tot >> 32), (long long)(tot & 0xFFFFFFFFull), now() - t_0);
-            cop_team.ready.store(ci + 1, std::memory_order_release);
-            ++cop_published;
-        }
-        return hipSuccess;
     };
     unsigned char *const cmp_dev = static_cast<unsigned char *>(h->cmp_dev), *const cmp_host = static_cast<unsigned char *>(h->cmp_host);
     // compacted copy-out: the host team expands landed blocks WHILE the later chunks are enqueued and scored - the
     // enqueue loop waits for every chunk's pack kernel, so it lasts as long as the kernels, and a team started behind
     // it (as the padded path's rebuild team is) had all blocks but none done at that point: 3 M candidates 25 - 30 ms,
-    // the team finishing 6 ms after the last copy.  The calling thread publishes chunks as their copies complete
-    // (fill_publish); worker w takes stripe w of T of every chunk.
+    // the team finishing 6 ms after the last copy.  The team takes the chunks as their copies complete (BlockHandoff;
+    // the enqueue loop appends the events behind flush_compact); worker w takes stripe w of T of every chunk.
     const int fill_T = compact ? host_threads_for(n) : 0;
-    int fill_started = 0;
-    int64_t fill_published = 0;
-    struct FillTeam {  // (declared behind what its threads read: it is destroyed - joined - first)
-        std::vector<std::thread> threads;
-        std::atomic<int64_t> ready{0};
-        std::atomic<bool> abort{false};
-        void join_all() {
-            for (std::thread &t : threads)
-                if (t.joinable()) t.join();
-        }
-        ~FillTeam() {
-            abort.store(true);
-            join_all();
-        }
-    } fill_team;
-    auto fill_stripe = [&](int64_t ci, int w) {
+    BlockHandoff fill_handoff(compact ? n_chunks : 0, h->device);
+    if (dbg_events) fill_handoff.landed = [&](int64_t ci) { dbg_told[(size_t)ci] = now() - t_0; };
+    HandoffTeam fill_team(fill_handoff);
+    // A chunk is handed out in tiles of kFillTile rows (on multiples of it: fill_host_rows works in aligned groups of 16
+    // rows), claimed one by one.  With one fixed stripe per thread a chunk took as long as its slowest thread: of the 16
+    // stripes of a 500 000-row block the quickest took 1.1 ms and the slowest 1.7 - 2.4 (team and enqueue thread are 17
+    // on a quota of 16 cores), and the team was 0.5 - 1.2 ms behind the last copy (profiles/headline_pipeline.json,
+    // `fixed_stripes`).
+    constexpr int64_t kFillTile = 2048;
+    std::vector<std::atomic<int64_t>> fill_next((size_t)n_chunks);
+    for (std::atomic<int64_t> &next : fill_next) next.store(0, std::memory_order_relaxed);
+    auto fill_stripe = [&](int64_t ci, int w) {  // (thread w's share of chunk ci; w only names it in the debug times)
         const int64_t a = cut[(size_t)ci], b = cut[(size_t)ci + 1];
-        const int64_t lo = a + (b - a) * w / fill_T, hi = a + (b - a) * (w + 1) / fill_T;
-        if (hi > lo) fill_host_rows(h, c, out, cmp_host + play.base(a, ci), b - a, a, lo, hi);
+        const double t_in = dbg_events ? now() : 0.0;
+        for (;;) {
+            const int64_t t = a / kFillTile + fill_next[(size_t)ci].fetch_add(1, std::memory_order_relaxed);
+            const int64_t lo = std::max(a, t * kFillTile), hi = std::min(b, (t + 1) * kFillTile);
+            if (lo >= b) break;
+            fill_host_rows(h, c, out, cmp_host + play.base(a, ci), b - a, a, lo, hi);
+        }
+        if (dbg_events && w < dbg_T) {
+            dbg_stripe_done[(size_t)ci * (size_t)dbg_T + (size_t)w] = now() - t_0;
+            dbg_stripe_took[(size_t)ci * (size_t)dbg_T + (size_t)w] = now() - t_in;
+        }
     };
     auto fill_worker = [&](int w) {
         for (int64_t ci = 0; ci < n_chunks; ++ci) {
-            // (waiting threads back off to short sleeps: a team that spins burns the CPU quota the busy ones need)
-            for (int spin = 0; fill_team.ready.load(std::memory_order_acquire) <= ci; ++spin) {
-                if (fill_team.abort.load(std::memory_order_relaxed)) return;
-                if (spin < 64) std::this_thread::yield();
-                else std::this_thread::sleep_for(std::chrono::microseconds(20));
-            }
+            // (waiting threads sleep: a team that spins burns the CPU quota the busy ones need)
+            if (!fill_handoff.wait_for(ci)) return;
             fill_stripe(ci, w);
         }
     };
-    for (int w = 0; w < fill_T; ++w) {
-        try {
-            fill_team.threads.emplace_back(fill_worker, w);
-            ++fill_started;
-        } catch (const std::system_error &) {
-            break;  // (the calling thread takes the stripes that have no thread, at the end)
-        }
-    }
-    auto fill_publish = [&](bool wait) -> hipError_t {
-        while (fill_published < (int64_t)chunk_done.size()) {
-            const hipEvent_t ev = chunk_done[(size_t)fill_published];
-            const hipError_t q = wait ? hipEventSynchronize(ev) : hipEventQuery(ev);
-            if (q == hipErrorNotReady) return hipSuccess;
-            if (q != hipSuccess) return q;
-            fill_team.ready.store(++fill_published, std::memory_order_release);
-        }
-        return hipSuccess;
-    };
     const double t_1 = now();
-    const bool dbg_events = timing && atoi(getenv("ADH_DEBUG_TIMING")) >= 2;  // per-chunk D2H spans
     std::vector<hipEvent_t> dbg;
     std::vector<uint64_t> dbg_bytes;  // copy-out bytes of every chunk
     hipEvent_t dbg_start = nullptr;   // on the copy-in stream, before the first column goes up
+    struct DbgEvents {  // (the ADH_DEBUG_TIMING=2 events go on every way out of the call)
+        std::vector<hipEvent_t> &spans, &marks;
+        hipEvent_t &start;
+        ~DbgEvents() {
+            for (hipEvent_t e : spans) (void)hipEventDestroy(e);
+            for (hipEvent_t e : marks) (void)hipEventDestroy(e);
+            if (start) (void)hipEventDestroy(start);
+        }
+    } dbg_guard{dbg, dbg_k, dbg_start};
     auto fail_sync = [&](int code) {
         (void)hipDeviceSynchronize();
         (void)hipGetLastError();
@@ -1938,6 +1980,7 @@ int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring
     auto flush_compact = [&](int64_t ci) -> int {
         const int64_t a = cut[(size_t)ci], b = cut[(size_t)ci + 1];
         HIP_TRY(hipEventSynchronize(tot_ready[(size_t)ci]));
+        if (dbg_events) dbg_tot_seen[(size_t)ci] = now() - t_0;
         const PadBlock L((uint64_t)(b - a), (uint64_t)h->cmp_tot_pinned[ci]);
         const size_t base = play.base(a, ci);
         HIP_TRY(hipMemcpyAsync(cmp_host + base, cmp_dev + base, L.total, hipMemcpyDeviceToHost, so));
@@ -1949,39 +1992,112 @@ int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring
         chunk_done.push_back(ev);
         return ADH_OK;
     };
-    // Chunk 0: its columns + plan on the copy-in stream.  The columns of ALL later chunks follow in
-    // one go right behind it (one H2D per column): H2D copies issued while the D2H copies of earlier
-    // chunks are in flight slowed those down four-fold for two chunks on MI355X (measured; the
-    // copy engines are shared), whereas one early burst overlaps only the kernels of chunk 0.
+    // the tables of chunk ci that travel as they are (all of them, the wire columns, or valid + features beside the packed
+    // block), row range by row range
+    // (A chunk is up to nine copies and the engine idles ~10 us between two of them - a 47 000-row chunk, 21 MB, takes
+    // 0.46 ms = 46 GB/s where each copy runs at 55, `rocprofv3 --memory-copy-trace` - but a second copy-out stream for
+    // the feature table does not fill the gaps: measured in round 5, same times to the 0.01 ms, and taken out again.)
+    auto copy_tables = [&](int64_t ci) -> int {
+        const int64_t a = cut[(size_t)ci], b = cut[(size_t)ci + 1];
+        if (dbg_events) {
+            hipEvent_t e0, e1;
+            (void)hipEventCreate(&e0);
+            (void)hipEventCreate(&e1);
+            (void)hipEventRecord(e0, so);
+            dbg.push_back(e0);
+            dbg.push_back(e1);
+            dbg_bytes.push_back(h->d2h_bytes);
+        }
+        for (int i = 0; i < kNumOutFields && !cop && !resident; ++i) {
+            const OutFieldDesc &f = kOutFields[i];
+            void *host = *out_member(out, f);
+            const bool is_slot = f.member == offsetof(adh_output_t, fragment_lib_slot);
+            const bool is_stat = f.member == offsetof(adh_output_t, stat_matched_peaks);
+            if (is_slot && !host && rebuild) host = slot_host;
+            if (!host) continue;
+            if (rebuild && !f.wire && !is_stat) continue;  // rebuilt on the host below
+            if (compact && f.per_row < 0) continue;        // the fragment tables travel packed (flush_compact)
+            const size_t rb = out_row_bytes(f, top_k);
+            hipError_t e = hipMemcpyAsync(static_cast<unsigned char *>(host) + (size_t)a * rb,
+                                          static_cast<unsigned char *>(*out_member(&dev, f)) + (size_t)a * rb,
+                                          (size_t)(b - a) * rb, hipMemcpyDeviceToHost, so);
+            if (e != hipSuccess) return fail(ADH_ERR_HIP, std::string("hipMemcpyAsync D2H: ") + hipGetErrorString(e));
+            h->d2h_bytes += (uint64_t)(b - a) * rb;
+        }
+        if (rebuild && !compact) {
+            hipEvent_t ev = nullptr;
+            int rc_e = get_event(h, &ev);
+            if (rc_e != ADH_OK) return rc_e;
+            HIP_TRY(hipEventRecord(ev, so));
+            chunk_done.push_back(ev);
+        }
+        if (dbg_events) {
+            (void)hipEventRecord(dbg.back(), so);
+            dbg_bytes.back() = h->d2h_bytes - dbg_bytes.back();
+        }
+        return ADH_OK;
+    };
+    // The copy-in stream, in order: columns(0) plan(0) | columns(1) plan(1) | columns(2) | plan(2) | columns(3 .. last)
+    // | plan(3) ...: every chunk up to 2 goes up just ahead of its plan, ALL later rows in one burst behind the plan of
+    // chunk 2 (one H2D per column).  One burst, because uploads of every chunk beside the copy-outs slowed those down
+    // four-fold (round 3; the copy engines are shared); behind plan(2), because a plan queued behind the burst waits
+    // for all of it: with the burst behind plan(1) the kernels of chunk 2 started 1.4 - 1.7 ms after those of chunk 1
+    // had ended and the copy-out had a hole of 1.15 ms (profiles/headline_pipeline.json, `before`).  The burst
+    // overlaps the copy-out of chunks 0 and 1 in both orders: that copy runs at 47 - 49 instead of 56 GB/s.
     // (ADH_H2D_BURST_LATE=0: the whole burst before the plan of chunk 1, the order of round 3)
     const char *late_env = getenv("ADH_H2D_BURST_LATE");
     const bool late_burst = !(late_env && atoi(late_env) == 0);
     if (dbg_events) {
         (void)hipEventCreate(&dbg_start);
         (void)hipEventRecord(dbg_start, si);
+        dbg_start_host = now() - t_0;
     }
     rc = cand_upload_range(h, c, 0, cut[1], si);
     if (rc == ADH_OK) rc = plan_enqueue(h, h->slots[0], cfg, 0, cut[1], si);
-    // ... of which chunk 1's rows go first and the rest behind the plan of chunk 1: its kernels - and with them the
-    // second copy-out - start ~4 ms earlier than behind the whole burst, and the copy-out stream has no gap to wait out
     if (rc == ADH_OK && n_chunks > 1) rc = cand_upload_range(h, c, cut[1], late_burst ? cut[2] : n, si);
     if (rc != ADH_OK) return fail_sync(rc);
+    // the host teams start now that the device has work: started in front of the first copy-in, the 16 threads made
+    // the call's set-up 0.4 - 0.5 ms instead of 0.07 - 0.10 (profiles/headline_pipeline.json, `setup_ms`)
+    for (int w = 0; w < cop_T; ++w) {
+        try {
+            cop_team.threads.emplace_back(cop_worker, w);
+            ++cop_started;
+        } catch (const std::system_error &) {
+            break;
+        }
+    }
+    for (int w = 0; w < fill_T; ++w) {
+        try {
+            fill_team.threads.emplace_back(fill_worker, w);
+        } catch (const std::system_error &) {
+            break;  // (the threads there are - at the end the calling thread too - take the tiles)
+        }
+    }
     for (int64_t ci = 0; ci < n_chunks; ++ci) {
         const int64_t a = cut[(size_t)ci], b = cut[(size_t)ci + 1];
         const int ps = (int)(ci & 1);
-        if (cop && cop_publish(false) != hipSuccess) return fail_sync(fail(ADH_ERR_HIP, "scoring pipeline (compact copy-out)"));
-        if (compact && fill_publish(false) != hipSuccess) return fail_sync(fail(ADH_ERR_HIP, "scoring pipeline (compacted copy-out)"));
         if (ci + 1 < n_chunks) {
             // plan of the next chunk: the other plan slot is free once the kernels of chunk ci - 1 are done
             const int64_t a2 = b, b2 = cut[(size_t)ci + 2];
             if (ci >= 1) HIP_TRY(hipStreamWaitEvent(si, h->ev_k[ps ^ 1], 0));
             rc = plan_enqueue(h, h->slots[ps ^ 1], cfg, a2, b2 - a2, si);
-            if (rc == ADH_OK && ci == 0 && late_burst && n_chunks > 2) rc = cand_upload_range(h, c, cut[2], n, si);
+            // (the rows of chunk 2 behind the plan of chunk 1, ALL later rows behind the plan of chunk 2: see above)
+            if (rc == ADH_OK && late_burst && ci == 0 && n_chunks > 2) rc = cand_upload_range(h, c, cut[2], cut[3], si);
+            if (rc == ADH_OK && late_burst && ci == 1 && n_chunks > 3) rc = cand_upload_range(h, c, cut[3], n, si);
             if (rc != ADH_OK) return fail_sync(rc);
         }
         Plan p;
         rc = plan_finish(h, h->slots[ps], cfg, a, b - a, p);
+        auto dbg_mark = [&] {  // (ADH_DEBUG_TIMING=2: a time stamp on the scoring stream)
+            hipEvent_t e = nullptr;
+            if (dbg_events && hipEventCreate(&e) == hipSuccess) {
+                (void)hipEventRecord(e, sk);
+                dbg_k.push_back(e);
+            }
+        };
+        dbg_mark();
         if (rc == ADH_OK) rc = launch_scoring(h, p, cfg, &dev_k, sk);
+        dbg_mark();
         if (rc != ADH_OK) return fail_sync(rc);
         if (compact) {  // filled slots per row, their offsets, the packed block: behind the chunk's kernels
             unsigned char *blk = cmp_dev + play.base(a, ci);
@@ -2017,65 +2133,46 @@ int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring
             aux_events.push_back(ev);
             cop_tot_ready.push_back(ev);
         }
+        dbg_mark();
         HIP_TRY(hipEventRecord(h->ev_k[ps], sk));
         if (cop && ci > 0) {  // the block of the previous chunk, now that the host can know its size
             rc = flush_cop(ci - 1);
             if (rc != ADH_OK) return fail_sync(rc);
+            rc = cop_handoff.append(chunk_done.back());
+            if (rc != ADH_OK) return fail_sync(rc);
         }
-        if (compact && ci > 0) {  // the packed columns of the previous chunk, now that the host can know their length
+        // Copy-out.  Compacted: the packed block of a chunk goes AHEAD of its valid / features rows (from chunk 1 on: the
+        // link is busy with chunk ci - 1 when the kernels of chunk ci end, so that the host enqueues both only once it
+        // knows the block's length costs nothing).  The team expands a block while the rows that need no work follow
+        // it on the link - with the rows first, the blocks of the last three chunks landed within the last 1.4 ms of
+        // the copy-out and the team ended 1.0 - 1.3 ms after the last copy (profiles/headline_pipeline.json, `before`,
+        // `handoff_ms`).  Chunk 0 keeps its rows first: they leave the moment its kernels end.
+        if (compact && ci > 0) {  // (flush_compact waits for the pack kernel of chunk ci - 1: its kernels are done)
             rc = flush_compact(ci - 1);
             if (rc != ADH_OK) return fail_sync(rc);
-        }
-        HIP_TRY(hipStreamWaitEvent(so, h->ev_k[ps], 0));
-        if (dbg_events) {
-            hipEvent_t e0, e1;
-            (void)hipEventCreate(&e0);
-            (void)hipEventCreate(&e1);
-            (void)hipEventRecord(e0, so);
-            dbg.push_back(e0);
-            dbg.push_back(e1);
-            dbg_bytes.push_back(h->d2h_bytes);
-        }
-        // (A chunk is up to nine copies and the engine idles ~10 us between two of them - a 47 000-row chunk, 21 MB, takes
-        // 0.46 ms = 46 GB/s where each copy runs at 55, `rocprofv3 --memory-copy-trace` - but a second copy-out stream for
-        // the feature table does not fill the gaps: measured in round 5, same times to the 0.01 ms, and taken out again.)
-        for (int i = 0; i < kNumOutFields && !cop && !resident; ++i) {
-            const OutFieldDesc &f = kOutFields[i];
-            void *host = *out_member(out, f);
-            const bool is_slot = f.member == offsetof(adh_output_t, fragment_lib_slot);
-            const bool is_stat = f.member == offsetof(adh_output_t, stat_matched_peaks);
-            if (is_slot && !host && rebuild) host = slot_host;
-            if (!host) continue;
-            if (rebuild && !f.wire && !is_stat) continue;  // rebuilt on the host below
-            if (compact && f.per_row < 0) continue;        // the fragment tables travel packed (flush_compact)
-            const size_t rb = out_row_bytes(f, top_k);
-            hipError_t e = hipMemcpyAsync(static_cast<unsigned char *>(host) + (size_t)a * rb,
-                                          static_cast<unsigned char *>(*out_member(&dev, f)) + (size_t)a * rb,
-                                          (size_t)(b - a) * rb, hipMemcpyDeviceToHost, so);
-            if (e != hipSuccess) {
-                fail(ADH_ERR_HIP, std::string("hipMemcpyAsync D2H: ") + hipGetErrorString(e));
-                return fail_sync(ADH_ERR_HIP);
-            }
-            h->d2h_bytes += (uint64_t)(b - a) * rb;
-        }
-        if (rebuild && !compact) {
-            hipEvent_t ev = nullptr;
-            rc = get_event(h, &ev);
+            rc = fill_handoff.append(chunk_done.back());
             if (rc != ADH_OK) return fail_sync(rc);
-            HIP_TRY(hipEventRecord(ev, so));
-            chunk_done.push_back(ev);
+            if (ci > 1) rc = copy_tables(ci - 1);
+            if (rc != ADH_OK) return fail_sync(rc);
         }
-        if (dbg_events) {
-            (void)hipEventRecord(dbg.back(), so);
-            dbg_bytes.back() = h->d2h_bytes - dbg_bytes.back();
+        if (!compact || ci == 0) {
+            HIP_TRY(hipStreamWaitEvent(so, h->ev_k[ps], 0));
+            rc = copy_tables(ci);
+            if (rc != ADH_OK) return fail_sync(rc);
         }
     }
     if (compact) {
         rc = flush_compact(n_chunks - 1);
         if (rc != ADH_OK) return fail_sync(rc);
+        rc = fill_handoff.append(chunk_done.back());
+        if (rc != ADH_OK) return fail_sync(rc);
+        if (n_chunks > 1) rc = copy_tables(n_chunks - 1);
+        if (rc != ADH_OK) return fail_sync(rc);
     }
     if (cop) {
         rc = flush_cop(n_chunks - 1);
+        if (rc != ADH_OK) return fail_sync(rc);
+        rc = cop_handoff.append(chunk_done.back());
         if (rc != ADH_OK) return fail_sync(rc);
     }
     const double t_2 = now();
@@ -2083,12 +2180,12 @@ int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring
     if (rc != ADH_OK) return fail_sync(rc);
     if (cop) {
         // the blocks still on their way, then the threads (they have been unpacking since the first block landed)
-        hipError_t ee = cop_publish(true);
-        if (ee == hipSuccess) cop_team.join_all();
-        if (ee != hipSuccess) {
-            fail(ADH_ERR_HIP, std::string("scoring pipeline (compact copy-out): ") + hipGetErrorString(ee));
+        // (the calling thread joins the watch: a team of no threads still gets every block published)
+        if (!cop_handoff.wait_for(n_chunks - 1)) {
+            fail(ADH_ERR_HIP, std::string("scoring pipeline (compact copy-out): ") + hipGetErrorString(cop_handoff.error));
             return fail_sync(ADH_ERR_HIP);
         }
+        cop_team.join_all();
         for (int64_t ci = 0; ci < n_chunks; ++ci)  // (stripes of threads that could not be started)
             for (int w = cop_started; w < cop_T; ++w) cop_stripe(ci, w);
         if (timing) fprintf(stderr, "[adh]   compact: host team done %.2f ms after the call began (%d threads)\n", now() - t_0, cop_T);
@@ -2104,14 +2201,12 @@ int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring
     }
     if (compact) {
         // the blocks still on their way, then the team (it has been expanding since the first block landed)
-        hipError_t ee = fill_publish(true);
-        if (ee == hipSuccess) fill_team.join_all();
-        if (ee != hipSuccess) {
-            fail(ADH_ERR_HIP, std::string("scoring pipeline (compacted copy-out): ") + hipGetErrorString(ee));
+        if (!fill_handoff.wait_for(n_chunks - 1)) {
+            fail(ADH_ERR_HIP, std::string("scoring pipeline (compacted copy-out): ") + hipGetErrorString(fill_handoff.error));
             return fail_sync(ADH_ERR_HIP);
         }
-        for (int64_t ci = 0; ci < n_chunks; ++ci)  // (stripes of threads that could not be started)
-            for (int w = fill_started; w < fill_T; ++w) fill_stripe(ci, w);
+        for (int64_t ci = 0; ci < n_chunks; ++ci) fill_stripe(ci, fill_T);  // (this thread takes what is left)
+        fill_team.join_all();
         if (timing) fprintf(stderr, "[adh]   compacted copy-out: host team done %.2f ms after the call began (%d threads)\n", now() - t_0, fill_T);
     } else if (rebuild) {
         // host threads follow the copy-out stream chunk by chunk: thread w takes the w-th stripe of every chunk
@@ -2179,8 +2274,44 @@ int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring
                     i / 2, (long long)(cut[i / 2 + 1] - cut[i / 2]), since, from_start, ms, (double)dbg_bytes[i / 2] / 1e6,
                     (double)dbg_bytes[i / 2] / 1e6 / std::max(ms, 1e-3f));
         }
-        if (dbg_start) (void)hipEventDestroy(dbg_start);
-        for (hipEvent_t e : dbg) (void)hipEventDestroy(e);
+        // the hand-off of the packed blocks; a copy's end is its event's time behind dbg_start, put on the host's clock
+        // at the moment dbg_start was recorded (the copy-in stream is idle then)
+        const double t_ret = now() - t_0;
+        double last_landed = 0.0;
+        for (size_t ci = 0; compact && dbg_start && ci < chunk_done.size() && ci < dbg_told.size(); ++ci) {
+            float landed = 0.f;
+            (void)hipEventElapsedTime(&landed, dbg_start, chunk_done[ci]);
+            last_landed = dbg_start_host + landed;
+            double team_done = 0.0, took_lo = 1e30, took_hi = 0.0;
+            for (int w = 0; w < dbg_T; ++w) {
+                team_done = std::max(team_done, dbg_stripe_done[ci * (size_t)dbg_T + (size_t)w]);
+                took_lo = std::min(took_lo, dbg_stripe_took[ci * (size_t)dbg_T + (size_t)w]);
+                took_hi = std::max(took_hi, dbg_stripe_took[ci * (size_t)dbg_T + (size_t)w]);
+            }
+            fprintf(stderr, "[adh]   block %zu: total seen %.2f ms after the call began, copy ended %.2f, team told %.2f (lag %.2f), "
+                            "last thread done %.2f (a stripe took %.2f - %.2f ms)\n",
+                    ci, dbg_tot_seen[ci], last_landed, dbg_told[ci], dbg_told[ci] - last_landed, team_done, took_lo, took_hi);
+        }
+        if (compact && dbg_start)
+            fprintf(stderr, "[adh]   tail: the call returns %.2f ms after it began, %.2f ms after the last copy ended\n", t_ret,
+                    t_ret - last_landed);
+        // the scoring stream: a chunk's kernels, its helpers (count, scan, pack), the idle time in front of it
+        double k_sum = 0.0;
+        for (size_t i = 0; i + 2 < dbg_k.size(); i += 3) {
+            float k_ms = 0.f, help_ms = 0.f, idle_ms = 0.f, at = 0.f;
+            (void)hipEventElapsedTime(&k_ms, dbg_k[i], dbg_k[i + 1]);
+            (void)hipEventElapsedTime(&help_ms, dbg_k[i + 1], dbg_k[i + 2]);
+            if (i >= 3) (void)hipEventElapsedTime(&idle_ms, dbg_k[i - 1], dbg_k[i]);
+            if (dbg_start) (void)hipEventElapsedTime(&at, dbg_start, dbg_k[i]);
+            k_sum += (double)k_ms + (double)help_ms;
+            fprintf(stderr, "[adh]   chunk %zu: kernels start %.2f ms after the call's first copy-in, last %.2f ms, helpers %.3f ms, "
+                            "scoring stream idle before them %.2f ms\n", i / 3, at, k_ms, help_ms, idle_ms);
+        }
+        if (dbg_k.size() >= 3) {
+            float span = 0.f;
+            (void)hipEventElapsedTime(&span, dbg_k.front(), dbg_k.back());
+            fprintf(stderr, "[adh]   scoring stream: %.2f ms from the first kernel to the last helper, %.2f ms of them busy\n", span, k_sum);
+        }
     }
     unwind.ok = true;
     h->tables_current = true;
@@ -2198,6 +2329,10 @@ int adh_score_candidates_compact(adh_handle_t *h, const adh_candidates_t *c, con
     if (!h || !c || !cfg || !cop) return fail(ADH_ERR_INVALID_ARGUMENT, "NULL argument");
     if (cop->top_k <= 0 || cop->rows_capacity < 0 || cop->slots_capacity < 0)
         return fail(ADH_ERR_INVALID_ARGUMENT, "compact output: top_k / capacities");
+    if (cop->top_k > 255)  // (a row's number of filled slots travels as one byte)
+        return fail(ADH_ERR_INVALID_ARGUMENT, "compact output: top_k above 255");
+    if (h->h_lib.size() != (size_t)h->n_lib)  // (the team reads the library columns from the host copy)
+        return fail(ADH_ERR_NOT_STAGED, "compact output: no host copy of the staged library");
     adh_output_t shape{};
     shape.n = c->n;
     shape.top_k = cop->top_k;
