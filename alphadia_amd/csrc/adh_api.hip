@@ -359,7 +359,7 @@ struct adh_handle {
                                           // tables are rebuilt from it on the host instead of crossing PCIe
     void *slot_stage = nullptr;           // page-locked fragment_lib_slot staging when the caller passes none
     size_t slot_stage_bytes = 0;
-    // compacted copy-out of the fragment tables (adh_score_host.hip): a block per chunk - per-row offsets + the filled
+    // compacted copy-out of the fragment tables (adh_copyout.hip): a block per chunk - per-row offsets + the filled
     // slots of the six wire columns - on the device and in page-locked host memory; scan scratch; the chunks' totals
     void *cmp_dev = nullptr, *cmp_host = nullptr, *cmp_scan = nullptr;
     size_t cmp_dev_bytes = 0, cmp_host_bytes = 0, cmp_scan_bytes = 0;
@@ -368,7 +368,6 @@ struct adh_handle {
     void *cop_cnt = nullptr, *cop_scan = nullptr, *cop_stage = nullptr, *cop_dev = nullptr;
     size_t cop_cnt_bytes = 0, cop_scan_bytes = 0, cop_stage_bytes = 0, cop_dev_bytes = 0;
     uint64_t *cop_tot_pinned = nullptr;     // totals of up to 4096 chunks, page-locked
-    std::vector<uint64_t> cop_tot_host;
     int64_t n_lib = 0;
     double *d_wtp = nullptr;        // precursor weight table [2][64]
     uint64_t im_scratch_budget = 0; // bytes the scratch of one ion-mobility chunk may reserve (0: not asked yet)

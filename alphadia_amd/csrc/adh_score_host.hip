@@ -448,17 +448,28 @@ void settle_copy_path(adh_handle *h) {
     (void)hipGetLastError();  // (no room for it: the copies stay slow, nothing else changes)
 }
 
-int ensure_scratch(adh_handle *h, uint64_t bytes) {
-    if (h->scratch_slab_bytes >= bytes) return ADH_OK;
+// The grow-only buffers of a handle: `*p` holds at least `need` bytes afterwards (`*bytes` says how many); a block that
+// has to grow is replaced by one of need + slack bytes.  Device memory goes back only once the device is idle
+// (whatever was enqueued may still read the old block).
+int grow_device(void **p, size_t *bytes, size_t need, size_t slack) {
+    if (*bytes >= need) return ADH_OK;
     HIP_TRY(hipDeviceSynchronize());
-    if (h->scratch_slab) (void)hipFree(h->scratch_slab);
-    h->scratch_slab = nullptr;
-    h->scratch_slab_bytes = 0;
-    const uint64_t want = bytes + bytes / 4;
-    HIP_TRY(hipMalloc(&h->scratch_slab, want));
-    h->scratch_slab_bytes = want;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr, *bytes = 0;
+    HIP_TRY(hipMalloc(p, need + slack));
+    *bytes = need + slack;
     return ADH_OK;
 }
+// ... and page-locked host memory
+int grow_pinned(void **p, size_t *bytes, size_t need, size_t slack) {
+    if (*bytes >= need) return ADH_OK;
+    if (*p) (void)hipHostFree(*p);
+    *p = nullptr, *bytes = 0;
+    HIP_TRY(hipHostMalloc(p, need + slack, hipHostMallocDefault));
+    *bytes = need + slack;
+    return ADH_OK;
+}
+int ensure_scratch(adh_handle *h, uint64_t bytes) { return grow_device(&h->scratch_slab, &h->scratch_slab_bytes, bytes, bytes / 4); }
 
 // fold finished timing triples into the running sums so that the event list stays short
 void fold_timed(adh_handle *h, bool wait) {
@@ -938,6 +949,42 @@ int64_t pick_chunk(int64_t n, bool fine) {
 
 }  // extern "C"
 
+namespace {
+// The chunk boundaries of a host -> host call over n > 0 rows: chunk ci is rows [cut[ci], cut[ci + 1]).  A short first
+// chunk (its H2D, plan and kernels are the un-overlapped ramp of the D2H-bound pipeline), then equal chunks of
+// pick_chunk's length - of at most max_rows rows, where the caller sets a bound (> 0: the ion-mobility scratch fit,
+// the 32-bit offsets of the compacted copy-outs) - and, for the packed mode (`packed`), a short last one.  Reads
+// ADH_CHUNK, ADH_CHUNK_PARTS, ADH_CHUNK_MIN (pick_chunk), ADH_FIRST_CHUNK_DIV and ADH_LAST_CHUNK_DIV; no GPU.
+std::vector<int64_t> chunk_cuts(int64_t n, bool ion_mobility, int64_t max_rows, bool packed) {
+    int64_t chunk = pick_chunk(n, !ion_mobility);
+    if (max_rows > 0 && max_rows < chunk) {  // (as many equal parts as the bound asks for)
+        const int64_t parts = (n + max_rows - 1) / max_rows;
+        chunk = (n + parts - 1) / parts;
+    }
+    std::vector<int64_t> cut{0};
+    // a short first chunk: its copy-out starts early.  A quarter of a chunk - or half of one for a table of many
+    // chunks, where the copy-out is what the call waits for and the first copy-out should cover the kernels of the
+    // (full) second chunk: 3 M candidates 29.3 -> 28.6 ms; tables of two or three chunks lose with it
+    // (ADH_FIRST_CHUNK_DIV fixes the divisor)
+    const char *first_div_str = getenv("ADH_FIRST_CHUNK_DIV");
+    const int first_div_env = first_div_str && atoi(first_div_str) > 0 ? atoi(first_div_str) : 0;
+    // (tables of up to three chunks: no short first chunk - 48 000 rows 1.45 against 1.65 ms, 96 000 1.93 against 2.02)
+    const int first_div = first_div_env ? first_div_env : (n >= 4 * chunk ? 2 : ((n > 3 * chunk || ion_mobility) ? 4 : 1));
+    if (n > chunk) cut.push_back(std::max<int64_t>(chunk / first_div, 1));
+    while (cut.back() < n) cut.push_back(std::min(n, cut.back() + chunk));
+    if (packed && cut.size() >= 4) {
+        // a short last chunk: the host team expands a block only once it has landed, so the team's work on the last
+        // block comes after the last copy (ADH_LAST_CHUNK_DIV: the last chunk's share, 1 = no split)
+        int last_div = 4;
+        if (const char *env = getenv("ADH_LAST_CHUNK_DIV")) last_div = std::max(atoi(env), 1);
+        const int64_t last = cut.back() - cut[cut.size() - 2];
+        if (last_div > 1 && last / last_div >= 256) cut.insert(cut.end() - 1, n - last / last_div);
+    }
+    return cut;
+}
+
+}  // namespace
+
 // The columns of the device tables that repeat the candidate table (precursor_idx, rank) or the library (per
 // fragment slot) from fragment_lib_slot: the device-side twin of rebuild_host_rows, one thread per slot.
 __global__ void adh_rebuild_columns_kernel(DevCands c, const LibRec *__restrict__ lib, DevOut out, int64_t n) {
@@ -967,220 +1014,7 @@ __global__ void adh_rebuild_columns_kernel(DevCands c, const LibRec *__restrict_
     out.fragment_loss_type[t] = l.loss_type;
 }
 
-// ---- compacted copy-out of the fragment tables of the padded path.  A candidate fills the first K of its top_k fragment
-// slots (K = fragments with signal: 4.6 of 12 on the headline) and 58 % of the 264 bytes per candidate that the five
-// computed fragment tables + fragment_lib_slot put on PCIe are zeros.  Per chunk of the pipeline, behind its scoring
-// kernels: K per row, an exclusive scan, and a pack kernel that writes the filled slots of the six columns into ONE
-// block (PadBlock) and stores the chunk's total straight into page-locked memory - the host sizes the block's single
-// copy from it without a round trip behind the copy-out backlog (see adh_cop_pack_kernel for why no copy fetches it).
-// The host team expands the block into the caller's padded tables and fills the library / id columns in the same pass
-// (fill_host_rows).
-__global__ void adh_slot_count_kernel(const uint16_t *__restrict__ lib_slot, int64_t row0, int64_t n, int top_k,
-                                      uint32_t *__restrict__ cnt) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i > n) return;
-    uint32_t k = 0;
-    if (i < n) {
-        const uint16_t *s = lib_slot + (row0 + i) * (int64_t)top_k;
-        while (k < (uint32_t)top_k && s[k]) ++k;  // (filled slots are the leading ones: candidate.py:403-442)
-    }
-    cnt[i] = k;  // (entry n: 0, so that the scan's last entry is the total)
-}
-
-// a chunk's block of R rows and S filled slots: [offsets u32 x (R + 1) | fragment_lib_slot u16 x S | mz_observed, height,
-// intensity, mass_error, correlation f32 x S]; every column starts on a multiple of 16 bytes
-struct PadBlock {
-    size_t slot, f[5], total;
-    __host__ __device__ PadBlock(uint64_t R, uint64_t S) {
-        size_t o = ((R + 1) * 4 + 15) & ~(size_t)15;
-        slot = o, o += (S * 2 + 15) & ~(size_t)15;
-        for (int j = 0; j < 5; ++j) f[j] = o, o += (S * 4 + 15) & ~(size_t)15;
-        total = o;
-    }
-};
-// where the block of the chunk that starts at row a sits in the staging buffers (device and host alike): room for every
-// slot filled, and 64 bytes of slack behind the last block (the host reads a row's 12 floats unmasked)
-struct PadLayout {
-    size_t per_row, total;
-    PadLayout(int64_t n, int top_k, int64_t n_chunks)
-        : per_row(4 + (size_t)top_k * 22), total((size_t)n * per_row + (size_t)(n_chunks + 1) * 1024 + 64) {}
-    size_t base(int64_t a, int64_t ci) const { return ((size_t)a * per_row + (size_t)ci * 1024 + 255) & ~(size_t)255; }
-};
-
-// one thread per (row, slot) of the chunk; the offsets (block + 0) are the scanned counts
-__global__ void adh_pad_pack_kernel(DevOut t, int64_t row0, int64_t n, int top_k, unsigned char *__restrict__ block,
-                                    uint32_t *__restrict__ total) {
-    const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t *off = reinterpret_cast<const uint32_t *>(block);
-    const uint32_t S = off[n];
-    if (id == 0) *total = S;  // (page-locked host memory)
-    if (id >= n * top_k) return;
-    const int64_t i = id / top_k;
-    const int j = (int)(id - i * top_k);
-    const uint32_t a = off[i], k = off[i + 1] - a;
-    if ((uint32_t)j >= k) return;
-    const PadBlock L(n, S);
-    const int64_t src = (row0 + i) * (int64_t)top_k + j;
-    const size_t dst = (size_t)a + (size_t)j;
-    reinterpret_cast<uint16_t *>(block + L.slot)[dst] = t.fragment_lib_slot[src];
-    reinterpret_cast<float *>(block + L.f[0])[dst] = t.fragment_mz_observed[src];
-    reinterpret_cast<float *>(block + L.f[1])[dst] = t.fragment_height[src];
-    reinterpret_cast<float *>(block + L.f[2])[dst] = t.fragment_intensity[src];
-    reinterpret_cast<float *>(block + L.f[3])[dst] = t.fragment_mass_error[src];
-    reinterpret_cast<float *>(block + L.f[4])[dst] = t.fragment_correlation[src];
-}
-
-// ---- compacted, column-major copy-out of the operator path (round 5, adh_score_candidates_compact).  What the
-// DataFrames of collect_candidates / collect_fragments keep of the padded tables is 91 % of the rows and 38 % of the
-// fragment slots (headline).  Per chunk, behind its scoring kernels: (valid, filled slots) per row as one 64-bit count,
-// an exclusive scan, and a pack kernel that writes every column of the chunk's valid rows and filled slots - features
-// transposed to [feature][row], the library columns of a slot read from the staged library, ids from the candidate
-// table - DENSELY into the chunk's block of a device staging buffer (CopBlock: where a column starts follows from the
-// chunk's two totals).  The totals reach the host first (8 bytes, stored by the pack kernel straight into page-locked
-// memory); the host then moves the block with ONE DMA copy of exactly its used bytes into a page-locked twin, and host
-// threads unpack finished blocks into the caller's arrays while later chunks are scored.
-// (Measured and dropped: the pack kernel storing through PCIe straight into host memory.  Kernel stores reach the link
-// rate - tools/probes/kcopy_probe.hip: 54-55 GB/s from 64 workgroups - but a copy-out kernel does not run BESIDE the
-// scoring kernels: on a stream of its own its workgroups wait until the scoring stream's backlog has drained (first
-// chunk on the host 15.7 ms into a 36 ms call), on a high-priority stream the launches of the scoring stream stall
-// instead (52 ms), and a compute unit backed up with PCIe stores stalls every wavefront on it: scoring kernels of a step
-// 14.5 ms alone, 16.8 beside 32 copying workgroups, 23.5 beside 64, 27.2 beside 128.  An 8-byte hipMemcpyAsync is such
-// a kernel, too: with the totals fetched that way the first block arrived 57 ms into the call.)
-__global__ void adh_cop_count_kernel(const uint8_t *__restrict__ valid, const uint16_t *__restrict__ lib_slot, int64_t row0,
-                                     int64_t n, int top_k, uint64_t *__restrict__ cnt) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i > n) return;
-    uint64_t v = 0;
-    if (i < n && valid[row0 + i]) {
-        const uint16_t *s = lib_slot + (row0 + i) * (int64_t)top_k;
-        uint32_t k = 0;
-        while (k < (uint32_t)top_k && s[k]) ++k;  // (filled slots are the leading ones: candidate.py:403-442)
-        v = (1ull << 32) | k;
-    }
-    cnt[i] = v;  // (entry n: 0, so that the scan's last entry is the total)
-}
-
-// a chunk's block, dense: [row u32 | filled slots u8 | features f32 [46][R]] for its R valid rows, then
-// [fragment_lib_slot u16 | 5 computed float columns] for its S filled slots; every column starts on a multiple of 16
-// bytes.  Round 6: what repeats the candidate table (precursor_idx, rank, and fragment_row = the row of a slot's
-// candidate) and the seven library columns of a slot stay off the wire - 26 instead of 42 bytes per slot, 188 instead of
-// 193 per row - and are rebuilt by the unpack team from the caller's candidate columns and the host copy of the
-// library, as the padded path does (rebuild_host_rows).
-struct CopBlock {
-    size_t row, cnt, feat, s_slot, s_f[5], total;
-    __host__ __device__ CopBlock(uint64_t R, uint64_t S) {
-        size_t o = 0;
-        row = o, o += (R * 4 + 15) & ~(size_t)15;
-        cnt = o, o += (R + 15) & ~(size_t)15;
-        feat = o, o += (R * 4 * ADH_NUM_FEATURES + 15) & ~(size_t)15;
-        s_slot = o, o += (S * 2 + 15) & ~(size_t)15;
-        for (int j = 0; j < 5; ++j) s_f[j] = o, o += (S * 4 + 15) & ~(size_t)15;
-        total = o;
-    }
-};
-// where the block of the chunk that starts at row a sits in the staging buffers (device and host alike): room for
-// every row valid and every slot filled
-struct CopLayout {
-    size_t per_row, total;
-    CopLayout(int64_t n, int top_k, int64_t n_chunks)
-        : per_row(5 + 4 * ADH_NUM_FEATURES + (size_t)top_k * 22), total((size_t)n * per_row + (size_t)(n_chunks + 1) * 1024) {}
-    size_t base(int64_t a, int64_t ci) const { return ((size_t)a * per_row + (size_t)ci * 1024 + 255) & ~(size_t)255; }
-};
-
-__global__ void adh_cop_pack_kernel(DevOut t, DevCands c, const LibRec *__restrict__ lib, int64_t row0, int64_t n, int top_k,
-                                    const uint64_t *__restrict__ off, unsigned char *__restrict__ block,
-                                    uint64_t *__restrict__ totals) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint64_t tot = off[n];
-    const uint64_t R = tot >> 32, S = tot & 0xFFFFFFFFull;
-    if (tid == 0) totals[0] = tot;  // (page-locked host memory)
-    const CopBlock L(R, S);
-    uint32_t *const o_row = reinterpret_cast<uint32_t *>(block + L.row);
-    uint8_t *const o_cnt = block + L.cnt;
-    float *const o_feat = reinterpret_cast<float *>(block + L.feat);
-    // valid rows: row id, number of filled slots, the feature row transposed (consecutive lanes = consecutive output
-    // rows of one column)
-    for (int64_t i = tid; i < n; i += stride) {
-        const uint64_t o = off[i], o1 = off[i + 1];
-        if ((o1 >> 32) == (o >> 32)) continue;
-        const int64_t j = (int64_t)(o >> 32), r = row0 + i;
-        o_row[j] = (uint32_t)r;
-        o_cnt[j] = (uint8_t)((uint32_t)o1 - (uint32_t)o);
-        const float *f = t.features + r * ADH_NUM_FEATURES;
-#pragma unroll
-        for (int k = 0; k < ADH_NUM_FEATURES; ++k) o_feat[(size_t)k * R + (size_t)j] = f[k];
-    }
-    // filled slots
-    uint16_t *const s_slot = reinterpret_cast<uint16_t *>(block + L.s_slot);
-    const int64_t n_slots = n * (int64_t)top_k;
-    for (int64_t id = tid; id < n_slots; id += stride) {
-        const int64_t i = id / top_k;
-        const int s = (int)(id - i * top_k);
-        const uint64_t o = off[i], o1 = off[i + 1];
-        const uint32_t a = (uint32_t)o, k = (uint32_t)o1 - a;
-        if ((uint32_t)s >= k) continue;
-        const int64_t r = row0 + i, src = r * (int64_t)top_k + s;
-        const size_t dst = (size_t)a + (size_t)s;
-        s_slot[dst] = t.fragment_lib_slot[src];
-        reinterpret_cast<float *>(block + L.s_f[0])[dst] = t.fragment_mz_observed[src];
-        reinterpret_cast<float *>(block + L.s_f[1])[dst] = t.fragment_height[src];
-        reinterpret_cast<float *>(block + L.s_f[2])[dst] = t.fragment_intensity[src];
-        reinterpret_cast<float *>(block + L.s_f[3])[dst] = t.fragment_mass_error[src];
-        reinterpret_cast<float *>(block + L.s_f[4])[dst] = t.fragment_correlation[src];
-    }
-}
-
-namespace {
-// stripe w of T of a finished block (page-locked host copy) -> the caller's arrays (rows at base_r, slots at base_s): the
-// stripe is a range of the block's valid rows together with their slots; what the block leaves out - ids, the row of a
-// slot's candidate, the library columns - comes from the candidate columns `c` and the library `lib`
-void cop_copy_stripe(const unsigned char *block, int64_t cnt_r, int64_t cnt_s, int64_t base_r, int64_t base_s,
-                     adh_compact_output_t *out, int w, int T, const adh_candidates_t *c, const LibRec *lib) {
-    const CopBlock L((uint64_t)cnt_r, (uint64_t)cnt_s);
-    const int64_t lo = cnt_r * w / T, hi = cnt_r * (w + 1) / T;
-    if (hi <= lo) return;
-    const uint32_t *rows = reinterpret_cast<const uint32_t *>(block + L.row);
-    const uint8_t *cnt = block + L.cnt;
-    int64_t s_lo = 0;  // slots of the rows before the stripe
-    for (int64_t j = 0; j < lo; ++j) s_lo += cnt[j];
-    memcpy(out->row + base_r + lo, rows + lo, (size_t)(hi - lo) * 4);
-    const float *fb = reinterpret_cast<const float *>(block + L.feat);
-    for (int k = 0; k < ADH_NUM_FEATURES; ++k)
-        memcpy(out->features + (size_t)k * (size_t)out->rows_capacity + (size_t)(base_r + lo),
-               fb + (size_t)k * (size_t)cnt_r + (size_t)lo, (size_t)(hi - lo) * 4);
-    const uint16_t *slot = reinterpret_cast<const uint16_t *>(block + L.s_slot);
-    int64_t d = base_s + s_lo, at = s_lo;
-    for (int64_t j = lo; j < hi; ++j) {
-        const uint32_t r = rows[j];
-        const uint32_t p = c->precursor_idx[r];
-        const uint8_t rk = c->rank ? c->rank[r] : (uint8_t)0;
-        out->precursor_idx[base_r + j] = p;
-        out->rank[base_r + j] = rk;
-        const LibRec *base = lib + c->frag_start_idx[r];
-        const int k = (int)cnt[j];
-        for (int q = 0; q < k; ++q, ++d, ++at) {
-            const LibRec &l = base[slot[at] - 1];
-            out->fragment_row[d] = r;
-            out->fragment_precursor_idx[d] = p;
-            out->fragment_rank[d] = rk;
-            out->fragment_mz_library[d] = l.mz_library;
-            out->fragment_mz[d] = l.mz;
-            out->fragment_position[d] = l.position;
-            out->fragment_number[d] = l.number;
-            out->fragment_type[d] = l.type;
-            out->fragment_charge[d] = l.charge;
-            out->fragment_loss_type[d] = l.loss_type;
-        }
-    }
-    const size_t m = (size_t)(at - s_lo);
-    if (m) {
-        float *const fcol[5] = {out->fragment_mz_observed, out->fragment_height, out->fragment_intensity, out->fragment_mass_error,
-                                out->fragment_correlation};
-        for (int j = 0; j < 5; ++j) memcpy(fcol[j] + base_s + s_lo, block + L.s_f[j] + (size_t)s_lo * 4, m * 4);
-    }
-}
-}  // namespace
+#include "adh_copyout.hip"
 
 extern "C" {
 
@@ -1280,317 +1114,61 @@ int adh_kernel_time_ms(adh_handle_t *h, double *gather_ms, double *feature_ms, i
 
 namespace {
 
-// rows [a, b) of the rebuildable host columns (OutputPsmDF columns that repeat the candidate table / the library,
-// alphadia/search/scoring/output.py:17-97; written by the kernels as candidate.py:175-176, 403-481)
-void rebuild_host_rows(const adh_handle *h, const adh_candidates_t *c, adh_output_t *out, const uint16_t *slots,
-                       int64_t a, int64_t b) {
-    const int top_k = out->top_k;
-    const LibRec *lib = h->h_lib.data();
-    for (int64_t i = a; i < b; ++i) {
-        const bool skip = c->flags && (c->flags[i] & ADH_FLAG_SKIP);
-        const uint32_t p = skip ? 0u : c->precursor_idx[i];
-        const uint8_t r = skip ? (uint8_t)0 : c->rank[i];
-        out->precursor_idx[i] = p;
-        out->rank[i] = r;
-        const LibRec *base = lib + c->frag_start_idx[i];
-        for (int j = 0; j < top_k; ++j) {
-            const size_t o = (size_t)i * (size_t)top_k + (size_t)j;
-            const uint16_t s = slots[o];
-            if (s) {
-                const LibRec &l = base[s - 1];
-                out->fragment_precursor_idx[o] = p;
-                out->fragment_rank[o] = r;
-                out->fragment_mz_library[o] = l.mz_library;
-                out->fragment_mz[o] = l.mz;
-                out->fragment_position[o] = l.position;
-                out->fragment_number[o] = l.number;
-                out->fragment_type[o] = l.type;
-                out->fragment_charge[o] = l.charge;
-                out->fragment_loss_type[o] = l.loss_type;
-            } else {
-                out->fragment_precursor_idx[o] = 0;
-                out->fragment_rank[o] = 0;
-                out->fragment_mz_library[o] = 0.0f;
-                out->fragment_mz[o] = 0.0f;
-                out->fragment_position[o] = 0;
-                out->fragment_number[o] = 0;
-                out->fragment_type[o] = 0;
-                out->fragment_charge[o] = 0;
-                out->fragment_loss_type[o] = 0;
-            }
+// ion-mobility candidates reserve a scratch block sized for their dense tiles (116 KB at 38 scans x 29 cycles,
+// although ~1 % of it is touched): *max_rows bounds a chunk so that the slab stays within a third of the free device
+// memory (0: no bound).  Tile sizes from the host columns; K <= top_k fragments, 3 observations assumed.
+int im_chunk_bound(adh_handle *h, const adh_candidates_t *c, const adh_scoring_config_t *cfg, int64_t *max_rows) {
+    *max_rows = 0;
+    int64_t cells = 1;
+    for (int64_t i = 0; i < c->n; ++i) {
+        const int64_t S = std::max<int64_t>(c->scan_stop[i] - c->scan_start[i], 1);
+        const int64_t F = std::max<int64_t>((c->frame_stop[i] - c->frame_start[i]) / std::max(h->tims.cycle_len, 1) + 1, 1);
+        cells = std::max(cells, S * F);
+    }
+    const int64_t k_max = std::max<int64_t>(std::min<int64_t>(cfg->top_k_fragments, 64), 1);
+    const uint64_t block = (uint64_t)cells * 8 * (uint64_t)(k_max * 3 + 4) + 4096;
+    if (h->im_scratch_budget == 0) {  // (asked once per staged run: hipMemGetInfo takes ~2 ms)
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
+            h->im_scratch_budget = std::max<uint64_t>((free_b + h->scratch_slab_bytes) / 3, 1ull << 30);
+    }
+    if (h->im_scratch_budget) {
+        const uint64_t budget = h->im_scratch_budget;
+        if (block > budget)
+            return fail(ADH_ERR_UNSUPPORTED, "one ion-mobility candidate's tiles exceed a third of the free device memory");
+        *max_rows = (int64_t)std::max<uint64_t>(budget / block, 64);  // (the budget holds, down to 64 rows per chunk)
+    }
+    return ADH_OK;
+}
+
+// a call that fails half way leaves no tables behind (a reader would rebuild columns of a half-filled table), and its
+// events go back to the pool.  The one place that synchronises the device and clears the error after a failure: the
+// copy-out mode is declared behind it, so its team is stopped and joined first.
+struct PipelineUnwind {
+    adh_handle *h;
+    DevTables &tab;
+    std::vector<hipEvent_t> &events;
+    std::vector<hipEvent_t> &aux;
+    bool ok = false;
+    ~PipelineUnwind() {
+        for (std::vector<hipEvent_t> *list : {&events, &aux}) {
+            h->free_events.insert(h->free_events.end(), list->begin(), list->end());
+            list->clear();
         }
-    }
-}
-
-// rows [lo, hi) of the chunk that starts at row a0 and has R rows, from its packed block (host copy): ONE pass that
-// writes every host column of a row - precursor_idx and rank, the five computed fragment columns and fragment_lib_slot
-// (when the caller asked for it) from the block, the library / id columns of the row's K filled slots from the host copy
-// of the library - with zeros behind the K filled slots.  Byte for byte what the copy of the padded tables plus
-// rebuild_host_rows write (skipped rows have no filled slot: zeros everywhere).
-void fill_host_rows(const adh_handle *h, const adh_candidates_t *c, adh_output_t *out, const unsigned char *blk, int64_t R,
-                    int64_t a0, int64_t lo, int64_t hi) {
-    const int top_k = out->top_k;
-    const LibRec *lib = h->h_lib.data();
-    const uint32_t *off = reinterpret_cast<const uint32_t *>(blk);
-    const PadBlock L((uint64_t)R, (uint64_t)off[R]);
-    const uint16_t *src_s = reinterpret_cast<const uint16_t *>(blk + L.slot);
-    const float *src[5];
-    for (int j = 0; j < 5; ++j) src[j] = reinterpret_cast<const float *>(blk + L.f[j]);
-    float *const dst[5] = {out->fragment_mz_observed, out->fragment_height, out->fragment_intensity, out->fragment_mass_error,
-                           out->fragment_correlation};
-    uint16_t *const slot_out = out->fragment_lib_slot;  // (NULL: the caller did not ask for the slots)
-    uint8_t *const u8col[6] = {out->fragment_rank, out->fragment_position, out->fragment_number, out->fragment_type,
-                               out->fragment_charge, out->fragment_loss_type};
-    if (top_k == 12) {
-        // the usual width (default.yaml:185), in tiles of 16 rows.  A tile's rows of every column are assembled in local
-        // buffers first, then each column's part of the tile leaves as one run of streaming stores (768 bytes of a 4-byte
-        // column, 192 of a byte column: whole cache lines, as tiles start on multiples of 16 rows) - one column after the
-        // other.  (Storing a row's 14 columns side by side with streaming stores left the core's write-combining buffers
-        // to be flushed half-filled: the host team took 2x as long as the copies it replaces.)  The packed source is
-        // read unmasked (a column has slack behind its last entry, the buffer behind its last block) and cut to the
-        // row's k entries with a mask.
-        alignas(16) static const uint32_t kMask[13][12] = {
-#define ADH_M(k) {k > 0 ? ~0u : 0u, k > 1 ? ~0u : 0u, k > 2 ? ~0u : 0u, k > 3 ? ~0u : 0u, k > 4 ? ~0u : 0u, k > 5 ? ~0u : 0u, \
-                  k > 6 ? ~0u : 0u, k > 7 ? ~0u : 0u, k > 8 ? ~0u : 0u, k > 9 ? ~0u : 0u, k > 10 ? ~0u : 0u, k > 11 ? ~0u : 0u}
-            ADH_M(0), ADH_M(1), ADH_M(2), ADH_M(3), ADH_M(4), ADH_M(5), ADH_M(6), ADH_M(7), ADH_M(8), ADH_M(9), ADH_M(10), ADH_M(11), ADH_M(12)
-#undef ADH_M
-        };
-        constexpr int TR = 16;
-        alignas(64) float tf[8][TR * 12];    // 5 computed columns, mz_library, mz, fragment_precursor_idx (as bits)
-        alignas(64) uint8_t tb[6][TR * 12];  // fragment_rank, position, number, type, charge, loss_type
-        alignas(64) uint16_t ts[TR * 12];
-        alignas(64) uint32_t tp[TR];
-        alignas(64) uint8_t tr[TR];
-        float *const dstf[8] = {dst[0], dst[1], dst[2], dst[3], dst[4], out->fragment_mz_library, out->fragment_mz,
-                                reinterpret_cast<float *>(out->fragment_precursor_idx)};
-        auto put = [](void *d, const void *src_, size_t bytes, bool nt) {
-            if (nt && (reinterpret_cast<uintptr_t>(d) & 15u) == 0 && bytes % 16 == 0) {
-                for (size_t q = 0; q < bytes; q += 16)
-                    _mm_stream_si128(reinterpret_cast<__m128i *>(static_cast<char *>(d) + q),
-                                     _mm_load_si128(reinterpret_cast<const __m128i *>(static_cast<const char *>(src_) + q)));
-            } else {
-                memcpy(d, src_, bytes);
-            }
-        };
-        for (int64_t t0 = lo; t0 < hi;) {
-            const int64_t t1 = std::min<int64_t>(hi, (t0 / TR + 1) * TR);
-            const int m = (int)(t1 - t0);
-            const bool full = m == TR;
-            memset(tf[5], 0, sizeof(tf[5]) * 2);
-            memset(tb, 0, sizeof(tb));
-            memset(ts, 0, sizeof(ts));
-            for (int q = 0; q < m; ++q) {
-                const int64_t i = t0 + q;
-                const bool skip = c->flags && (c->flags[i] & ADH_FLAG_SKIP);
-                const uint32_t p = skip ? 0u : c->precursor_idx[i];
-                const uint8_t r = skip ? (uint8_t)0 : c->rank[i];
-                tp[q] = p;
-                tr[q] = r;
-                const uint32_t o = off[i - a0];
-                const uint32_t k = std::min<uint32_t>(off[i - a0 + 1] - o, 12u);
-                const __m128 m0 = _mm_load_ps(reinterpret_cast<const float *>(kMask[k]));
-                const __m128 m1 = _mm_load_ps(reinterpret_cast<const float *>(kMask[k] + 4));
-                const __m128 m2 = _mm_load_ps(reinterpret_cast<const float *>(kMask[k] + 8));
-                for (int j = 0; j < 5; ++j) {
-                    const float *sp = src[j] + o;
-                    float *row = tf[j] + q * 12;
-                    _mm_store_ps(row, _mm_and_ps(_mm_loadu_ps(sp), m0));
-                    _mm_store_ps(row + 4, _mm_and_ps(_mm_loadu_ps(sp + 4), m1));
-                    _mm_store_ps(row + 8, _mm_and_ps(_mm_loadu_ps(sp + 8), m2));
-                }
-                const __m128 pv = _mm_castsi128_ps(_mm_set1_epi32((int)p));
-                _mm_store_ps(tf[7] + q * 12, _mm_and_ps(pv, m0));
-                _mm_store_ps(tf[7] + q * 12 + 4, _mm_and_ps(pv, m1));
-                _mm_store_ps(tf[7] + q * 12 + 8, _mm_and_ps(pv, m2));
-                // the library columns of the k filled slots (zeros behind: the buffers were cleared)
-                const LibRec *base = lib + c->frag_start_idx[i];
-                for (uint32_t u = 0; u < k; ++u) {
-                    const int e = q * 12 + (int)u;
-                    const uint16_t sl = src_s[o + u];
-                    const LibRec &l = base[sl - 1];
-                    ts[e] = sl;
-                    tf[5][e] = l.mz_library;
-                    tf[6][e] = l.mz;
-                    tb[0][e] = r;
-                    tb[1][e] = l.position;
-                    tb[2][e] = l.number;
-                    tb[3][e] = l.type;
-                    tb[4][e] = l.charge;
-                    tb[5][e] = l.loss_type;
-                }
-            }
-            const size_t r0 = (size_t)t0 * 12;
-            for (int j = 0; j < 8; ++j) put(dstf[j] + r0, tf[j], (size_t)m * 48, full);
-            for (int j = 0; j < 6; ++j) put(u8col[j] + r0, tb[j], (size_t)m * 12, full);
-            if (slot_out) put(slot_out + r0, ts, (size_t)m * 24, full);
-            put(out->precursor_idx + t0, tp, (size_t)m * 4, full);
-            put(out->rank + t0, tr, (size_t)m, false);  // (16 bytes: a quarter of a line)
-            t0 = t1;
-        }
-        _mm_sfence();
-        return;
-    }
-    // any other width: plain loops
-    for (int64_t i = lo; i < hi; ++i) {
-        const bool skip = c->flags && (c->flags[i] & ADH_FLAG_SKIP);
-        const uint32_t p = skip ? 0u : c->precursor_idx[i];
-        const uint8_t r = skip ? (uint8_t)0 : c->rank[i];
-        out->precursor_idx[i] = p;
-        out->rank[i] = r;
-        const uint32_t o = off[i - a0];
-        const int k = (int)std::min<uint32_t>(off[i - a0 + 1] - o, (uint32_t)top_k);
-        const size_t r0 = (size_t)i * (size_t)top_k;
-        const LibRec *base = lib + c->frag_start_idx[i];
-        int t = 0;
-        for (; t < k; ++t) {
-            const size_t d = r0 + (size_t)t;
-            const uint16_t s = src_s[o + t];
-            const LibRec &l = base[s - 1];
-            for (int j = 0; j < 5; ++j) dst[j][d] = src[j][o + t];
-            if (slot_out) slot_out[d] = s;
-            out->fragment_precursor_idx[d] = p;
-            out->fragment_rank[d] = r;
-            out->fragment_mz_library[d] = l.mz_library;
-            out->fragment_mz[d] = l.mz;
-            out->fragment_position[d] = l.position;
-            out->fragment_number[d] = l.number;
-            out->fragment_type[d] = l.type;
-            out->fragment_charge[d] = l.charge;
-            out->fragment_loss_type[d] = l.loss_type;
-        }
-        const size_t rest = (size_t)(top_k - t);
-        if (!rest) continue;
-        const size_t d = r0 + (size_t)t;
-        for (int j = 0; j < 5; ++j) memset(dst[j] + d, 0, rest * 4);
-        if (slot_out) memset(slot_out + d, 0, rest * 2);
-        memset(out->fragment_precursor_idx + d, 0, rest * 4);
-        memset(out->fragment_mz_library + d, 0, rest * 4);
-        memset(out->fragment_mz + d, 0, rest * 4);
-        for (int j = 0; j < 6; ++j) memset(u8col[j] + d, 0, rest);
-    }
-}
-
-// this rank's share of the host: at most 16 threads, and of the cores this process may use (host_cpu_budget: quota,
-// affinity, hardware) only the LOCAL_WORLD_SIZE-th part - the ranks of a node run side by side under ONE quota
-int host_thread_share() {
-    int t = 16;
-    if (const char *env = getenv("ADH_HOST_THREADS")) t = atoi(env);
-    else {
-        int ranks = 1;
-        if (const char *lw = getenv("LOCAL_WORLD_SIZE")) ranks = std::max(atoi(lw), 1);
-        t = std::min<int>(t, std::max<int>(host_cpu_budget() / ranks, 1));
-    }
-    return std::max(t, 1);
-}
-
-int host_threads_for(int64_t n) {
-    // the team that rebuilds the id / library columns behind the copy-out (or unpacks the compact blocks)
-    const int t = (int)std::min<int64_t>(host_thread_share(), n / 16384);  // (a thread per 16 k rows at least: starting one costs ~20 us)
-    return std::max(t, 1);
-}
-
-// Does the host rebuild the id / library columns of the padded tables (197 of 646 bytes per candidate stay off PCIe),
-// or does the device write them and the link carry everything?  A thread rebuilds ~23 000 rows per ms, the link delivers
-// 122 000 rows per ms of wire tables: below ~6 threads the team is what the call waits for (measured with 2 threads -
-// the eighth part of the pool's 16-core quota: a 375 000-row shard takes 8.9 ms against 4.6), and the 44 % more bytes
-// cost less (every GPU of a node has its own link, the ranks share the CPU quota).  ADH_REBUILD_MIN_THREADS moves the
-// threshold (0: always rebuild).
-bool host_rebuild_pays() {
-    int least = 6;
-    if (const char *env = getenv("ADH_REBUILD_MIN_THREADS")) least = atoi(env);
-    return host_thread_share() >= least;
-}
-
-// Does the padded path copy the fragment tables out compacted (adh_pad_pack_kernel, fill_host_rows)?  The wire drops from
-// 449 to ~290 bytes per candidate, and the host team writes the 5 computed columns it no longer gets by DMA.  That pays
-// where the call waits for the link and the team keeps pace with it: a large table (ADH_COMPACT_MIN_ROWS, default
-// 1 000 000 rows) and at least 12 threads of host.  ADH_COMPACT_COPY_OUT=1 / =0 forces it on / off.
-bool compact_copy_out_pays(int64_t n) {
-    if (const char *env = getenv("ADH_COMPACT_COPY_OUT")) return atoi(env) != 0;
-    int64_t least_rows = 1000000;
-    if (const char *env = getenv("ADH_COMPACT_MIN_ROWS")) least_rows = atoll(env);
-    return host_thread_share() >= 12 && n >= least_rows;
-}
-
-// The hand-off of landed blocks to a host team (the compacted copy-outs).  The enqueue thread only appends the event
-// that follows a block's copy (append).  Whichever thread of the team runs out of work first becomes the watcher: it
-// waits on the oldest event nobody has waited for, runs `landed` for that chunk and publishes it.  So a block reaches
-// the team when its copy ends, wherever the enqueue thread happens to be (it sleeps a chunk long waiting for the next
-// pack total; a poll from there found a block either at once or one chunk - 2.6 ms - late).  Nobody spins: the watcher
-// sits in hipEventSynchronize, the others back off to short sleeps (a team that spins burns the CPU quota the busy
-// ones need; a team woken all at once from a condition variable took 3 - 8 ms over a 500 000-row block instead of
-// 1.5 - 2.5 and ended 3 - 17 ms behind the last copy: profiles/headline_pipeline.json, `condition_variable`).
-// The events live in an array sized for every chunk
-// before a thread starts: the enqueue thread writes entry `appended` and then raises the count, the watcher - one at
-// a time, the role is claimed with `watching` - reads entries below it; what `landed` writes is published with `ready`.
-struct BlockHandoff {
-    std::vector<hipEvent_t> events;
-    std::atomic<int64_t> appended{0}, ready{0};
-    std::atomic<bool> watching{false}, abort{false};
-    hipError_t error = hipSuccess;  // (written by a watcher before it raises `abort`)
-    int device = 0;
-    std::function<void(int64_t)> landed;  // once per chunk, in order, before the chunk is published
-
-    BlockHandoff(int64_t n_chunks, int device_) : events((size_t)std::max<int64_t>(n_chunks, 0), nullptr), device(device_) {}
-    int append(hipEvent_t ev) {  // (the enqueue thread only)
-        const int64_t k = appended.load(std::memory_order_relaxed);
-        if (k >= (int64_t)events.size())  // (an event nobody would ever wait for: a waiter of its chunk would hang)
-            return fail(ADH_ERR_INVALID_ARGUMENT, "scoring pipeline: more copy-out events than chunks");
-        events[(size_t)k] = ev;
-        appended.store(k + 1, std::memory_order_release);
-        return ADH_OK;
-    }
-    void stop() { abort.store(true, std::memory_order_release); }  // (an early return: whoever still waits gives up)
-    // true once chunk ci has landed; false when the call is given up or a wait has failed (`error`)
-    bool wait_for(int64_t ci) {
-        for (int spin = 0;; ++spin) {
-            if (ready.load(std::memory_order_acquire) > ci) return true;
-            if (abort.load(std::memory_order_acquire)) return false;
-            if (appended.load(std::memory_order_acquire) > ready.load(std::memory_order_relaxed) &&
-                !watching.exchange(true, std::memory_order_acq_rel)) {
-                const int64_t k = ready.load(std::memory_order_acquire);  // (nobody else moves it while the role is held)
-                if (k < appended.load(std::memory_order_acquire)) {
-                    hipError_t q = hipSetDevice(device);
-                    if (q == hipSuccess) q = hipEventSynchronize(events[(size_t)k]);
-                    if (q == hipSuccess && landed) landed(k);
-                    if (q == hipSuccess) {
-                        ready.store(k + 1, std::memory_order_release);
-                    } else {
-                        error = q;
-                        abort.store(true, std::memory_order_release);
-                    }
-                }
-                watching.store(false, std::memory_order_release);
-                spin = 0;
-                continue;
-            }
-            if (spin < 64) std::this_thread::yield();
-            else std::this_thread::sleep_for(std::chrono::microseconds(20));
+        if (!ok) {
+            (void)hipDeviceSynchronize();
+            (void)hipGetLastError();
+            h->last_tables = -1;
+            h->last_rows = 0;
+            tab.partial = false;
         }
     }
 };
 
-// the threads that follow a BlockHandoff (declared behind what they read: it is destroyed - joined - first)
-struct HandoffTeam {
-    BlockHandoff &handoff;
-    std::vector<std::thread> threads;
-    explicit HandoffTeam(BlockHandoff &handoff_) : handoff(handoff_) {}
-    void join_all() {
-        for (std::thread &t : threads)
-            if (t.joinable()) t.join();
-    }
-    ~HandoffTeam() {
-        handoff.stop();
-        join_all();
-    }
-};
-
-}  // namespace
-
-namespace {
 // the host -> host pipeline behind adh_score_candidates (padded tables into `out`) and adh_score_candidates_compact
 // (`cop` set: `out` only carries n and top_k, the compacted columns go to `cop`) and adh_score_candidates_resident
-// (`resident`: `out` only carries n and top_k, nothing is copied back)
+// (`resident`: `out` only carries n and top_k, nothing is copied back).  This is the schedule of the three streams;
+// how the results leave the device is the copy-out mode's part (adh_copyout.hip).
 int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring_config_t *cfg, adh_output_t *out,
                    adh_compact_output_t *cop, bool resident = false) {
     if (!h || !c || !cfg || !out) return fail(ADH_ERR_INVALID_ARGUMENT, "NULL argument");
@@ -1602,12 +1180,7 @@ int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring
         if (!kOutFields[i].optional && *out_member(out, kOutFields[i]) == nullptr)
             return fail(ADH_ERR_INVALID_ARGUMENT, "output buffer is NULL");
     HIP_TRY(hipSetDevice(h->device));
-    const bool timing = getenv("ADH_DEBUG_TIMING") != nullptr;  // developer switch: stage times to stderr
-    const bool dbg_events = timing && atoi(getenv("ADH_DEBUG_TIMING")) >= 2;  // per-chunk D2H spans, hand-off times
-    auto now = [] {
-        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-    };
-    const double t_0 = now();
+    PipelineTrace trace;  // developer switch ADH_DEBUG_TIMING: stage times to stderr
     const int64_t n = c->n;
     const int top_k = out->top_k;
     h->plan = Plan();            // the resident table (adh_upload_candidates) is replaced
@@ -1630,10 +1203,10 @@ int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring
     h->last_tables = slot;
     h->last_rows = n;
     {
-        const double t_s = now();
+        const double t_s = trace.now();
         const bool was = g_big_free.load();
         settle_copy_path(h);
-        if (timing && was) fprintf(stderr, "[adh] copy path settled in %.1f ms\n", now() - t_s);
+        if (trace.timing && was) fprintf(stderr, "[adh] copy path settled in %.1f ms\n", trace.now() - t_s);
     }
     if (cop) cop->n_rows = cop->n_slots = 0;
     h->tables_current = false;
@@ -1642,87 +1215,31 @@ int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring
         h->tables_current = rc == ADH_OK;
         return rc;
     }
-    std::vector<hipEvent_t> chunk_done;
-    // a call that fails half way leaves no tables behind (a reader would rebuild columns of a half-filled
-    // table), and its events go back to the pool
-    std::vector<hipEvent_t> aux_events;  // (events of the compacted copy-out, returned with the others)
-    struct Unwind {
-        adh_handle *h;
-        DevTables &tab;
-        std::vector<hipEvent_t> &events;
-        std::vector<hipEvent_t> &aux;
-        bool ok = false;
-        ~Unwind() {
-            for (hipEvent_t ev : events) h->free_events.push_back(ev);
-            events.clear();
-            for (hipEvent_t ev : aux) h->free_events.push_back(ev);
-            aux.clear();
-            if (!ok) {
-                (void)hipDeviceSynchronize();
-                (void)hipGetLastError();
-                h->last_tables = -1;
-                h->last_rows = 0;
-                tab.partial = false;
-            }
-        }
-    } unwind{h, tab, chunk_done, aux_events};
+    std::vector<hipEvent_t> chunk_done, tot_ready;  // (events of the copy-out mode, per chunk)
+    PipelineUnwind unwind{h, tab, chunk_done, tot_ready};
     adh_output_t dev = tab.view;
     dev.n = n;
-    hipStream_t sk = h->stream, si = h->stream_in, so = h->stream_out;
+    hipStream_t sk = h->stream, si = h->stream_in;
     HIP_TRY(hipMemsetAsync(tab.base, 0, tab.used, sk));
     tab.partial = false;
 
-    // chunk boundaries: a short first chunk (its H2D, plan and kernels are the un-overlapped ramp
-    // of the D2H-bound pipeline), then equal chunks
-    int64_t chunk = pick_chunk(n, !h->tims_staged);
-    if (h->tims_staged && n > 0) {
-        // ion-mobility candidates reserve a scratch block sized for their dense tiles (116 KB at 38 scans x 29
-        // cycles, although ~1 % of it is touched): bound the chunk so that the slab stays within a third of the
-        // free device memory.  Tile sizes from the host columns; K <= top_k fragments, 3 observations assumed.
-        int64_t cells = 1;
-        for (int64_t i = 0; i < n; ++i) {
-            const int64_t S = std::max<int64_t>(c->scan_stop[i] - c->scan_start[i], 1);
-            const int64_t F = std::max<int64_t>((c->frame_stop[i] - c->frame_start[i]) / std::max(h->tims.cycle_len, 1) + 1, 1);
-            cells = std::max(cells, S * F);
-        }
-        const int64_t k_max = std::max<int64_t>(std::min<int64_t>(cfg->top_k_fragments, 64), 1);
-        const uint64_t block = (uint64_t)cells * 8 * (uint64_t)(k_max * 3 + 4) + 4096;
-        if (h->im_scratch_budget == 0) {  // (asked once per staged run: hipMemGetInfo takes ~2 ms)
-            size_t free_b = 0, total_b = 0;
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
-                h->im_scratch_budget = std::max<uint64_t>((free_b + h->scratch_slab_bytes) / 3, 1ull << 30);
-        }
-        if (h->im_scratch_budget) {
-            const uint64_t budget = h->im_scratch_budget;
-            if (block > budget)
-                return fail(ADH_ERR_UNSUPPORTED, "one ion-mobility candidate's tiles exceed a third of the free device memory");
-            const int64_t fit = (int64_t)std::max<uint64_t>(budget / block, 64);  // (the budget holds, down to 64 rows per chunk)
-            if (fit < chunk) {
-                const int64_t parts = (n + fit - 1) / fit;
-                chunk = (n + parts - 1) / parts;
-            }
-        }
-    }
     // rebuildable columns: not copied back, rebuilt on the host from fragment_lib_slot (see kOutFields)
-    if (cop)  // (a chunk's slot offsets are 32-bit words of the packed count)
-        chunk = std::min<int64_t>(chunk, std::max<int64_t>((int64_t)(0xFFFFFFFFull / (uint64_t)top_k) - 1, 1));
     const bool rebuild = !cop && !resident && h->h_lib.size() == (size_t)h->n_lib && !getenv("ADH_DEBUG_COPY_ALL") && host_rebuild_pays();
     // compacted copy-out of the fragment tables (see adh_slot_count_kernel, compact_copy_out_pays)
     const bool compact_wanted = rebuild && top_k <= 65535 && compact_copy_out_pays(n);
-    if (compact_wanted)  // (a chunk's offsets are 32-bit)
-        chunk = std::min<int64_t>(chunk, std::max<int64_t>((int64_t)(0xFFFFFFFFull / (uint64_t)top_k) - 1, 1));
-    uint16_t *slot_host = out->fragment_lib_slot;
-    if (rebuild && !slot_host) {
-        const size_t need = (size_t)n * (size_t)top_k * sizeof(uint16_t);
-        if (h->slot_stage_bytes < need) {
-            if (h->slot_stage) (void)hipHostFree(h->slot_stage);
-            h->slot_stage = nullptr;
-            h->slot_stage_bytes = 0;
-            HIP_TRY(hipHostMalloc(&h->slot_stage, need + need / 8, hipHostMallocDefault));
-            h->slot_stage_bytes = need + need / 8;
-        }
-        slot_host = static_cast<uint16_t *>(h->slot_stage);
+    // chunk boundaries: at most max_rows rows per chunk
+    int64_t max_rows = 0;
+    if (h->tims_staged) {
+        rc = im_chunk_bound(h, c, cfg, &max_rows);
+        if (rc != ADH_OK) return rc;
     }
+    if (cop || compact_wanted) {  // (a chunk's slot offsets are 32-bit words of the packed count)
+        const int64_t fits_32 = std::max<int64_t>((int64_t)(0xFFFFFFFFull / (uint64_t)top_k) - 1, 1);
+        max_rows = max_rows ? std::min(max_rows, fits_32) : fits_32;
+    }
+    const std::vector<int64_t> cut = chunk_cuts(n, h->tims_staged, max_rows, compact_wanted);
+    const int64_t n_chunks = (int64_t)cut.size() - 1;
+    const bool compact = compact_wanted && n_chunks <= 4096;
     adh_output_t dev_k = dev;  // what the kernels write
     if ((rebuild || cop || resident) && !getenv("ADH_DEBUG_WRITE_ALL")) {
         // ... and the kernels need not write them either: nobody on the host waits for them, and a reader of the
@@ -1733,310 +1250,15 @@ int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring
         }
         tab.partial = true;
     }
-    std::vector<int64_t> cut{0};
-    // a short first chunk: its copy-out starts early.  A quarter of a chunk - or half of one for a table of many
-    // chunks, where the copy-out is what the call waits for and the first copy-out should cover the kernels of the
-    // (full) second chunk: 3 M candidates 29.3 -> 28.6 ms; tables of two or three chunks lose with it
-    // (ADH_FIRST_CHUNK_DIV fixes the divisor)
-    const char *first_div_str = getenv("ADH_FIRST_CHUNK_DIV");
-    const int first_div_env = first_div_str && atoi(first_div_str) > 0 ? atoi(first_div_str) : 0;
-    // (tables of up to three chunks: no short first chunk - 48 000 rows 1.45 against 1.65 ms, 96 000 1.93 against 2.02)
-    const int first_div = first_div_env ? first_div_env : (n >= 4 * chunk ? 2 : ((n > 3 * chunk || h->tims_staged) ? 4 : 1));
-    if (n > chunk) cut.push_back(std::max<int64_t>(chunk / first_div, 1));
-    while (cut.back() < n) cut.push_back(std::min(n, cut.back() + chunk));
-    if (compact_wanted && cut.size() >= 4) {
-        // a short last chunk: the host team expands a block only once it has landed, so the team's work on the last
-        // block comes after the last copy (ADH_LAST_CHUNK_DIV: the last chunk's share, 1 = no split)
-        int last_div = 4;
-        if (const char *env = getenv("ADH_LAST_CHUNK_DIV")) last_div = std::max(atoi(env), 1);
-        const int64_t last = cut.back() - cut[cut.size() - 2];
-        if (last_div > 1 && last / last_div >= 256) cut.insert(cut.end() - 1, n - last / last_div);
-    }
-    const int64_t n_chunks = (int64_t)cut.size() - 1;
-    const bool compact = compact_wanted && n_chunks <= 4096;
-    const PadLayout play(n, top_k, n_chunks);
-    // ADH_DEBUG_TIMING=2, the hand-off of every packed block on the host's clock (ms after the call began): its total
-    // seen by the enqueue thread, the team told that it has landed, every thread of the team done with its stripe
-    // (one entry per chunk and thread: each thread writes its own)
-    const int dbg_T = dbg_events ? host_threads_for(n) : 0;
-    std::vector<double> dbg_tot_seen(dbg_events ? (size_t)n_chunks : 0, 0.0), dbg_told(dbg_tot_seen.size(), 0.0);
-    std::vector<double> dbg_stripe_done(dbg_tot_seen.size() * (size_t)dbg_T, 0.0), dbg_stripe_took(dbg_stripe_done.size(), 0.0);
-    std::vector<hipEvent_t> dbg_k;  // scoring stream, per chunk: before its kernels, behind them, behind its helpers
-    double dbg_start_host = 0.0;    // the host's clock when dbg_start was recorded
-    std::vector<hipEvent_t> &tot_ready = aux_events;  // per chunk: its pack kernel is done, its total on the host
-    if (compact) {
-        if (h->cmp_dev_bytes < play.total) {
-            HIP_TRY(hipDeviceSynchronize());
-            if (h->cmp_dev) (void)hipFree(h->cmp_dev);
-            h->cmp_dev = nullptr;
-            h->cmp_dev_bytes = 0;
-            HIP_TRY(hipMalloc(&h->cmp_dev, play.total + play.total / 8));
-            h->cmp_dev_bytes = play.total + play.total / 8;
-        }
-        if (h->cmp_host_bytes < play.total) {
-            if (h->cmp_host) (void)hipHostFree(h->cmp_host);
-            h->cmp_host = nullptr;
-            h->cmp_host_bytes = 0;
-            HIP_TRY(hipHostMalloc(&h->cmp_host, play.total + play.total / 8, hipHostMallocDefault));
-            h->cmp_host_bytes = play.total + play.total / 8;
-        }
-        if (!h->cmp_tot_pinned) HIP_TRY(hipHostMalloc((void **)&h->cmp_tot_pinned, 4096 * 4, hipHostMallocDefault));
-        int64_t longest = 0;
-        for (int64_t ci = 0; ci < n_chunks; ++ci) longest = std::max(longest, cut[(size_t)ci + 1] - cut[(size_t)ci]);
-        size_t scan_bytes = 0;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (uint32_t *)nullptr, (uint32_t *)nullptr, (int)(longest + 1), sk));
-        if (h->cmp_scan_bytes < scan_bytes) {
-            HIP_TRY(hipDeviceSynchronize());
-            if (h->cmp_scan) (void)hipFree(h->cmp_scan);
-            h->cmp_scan = nullptr;
-            h->cmp_scan_bytes = 0;
-            HIP_TRY(hipMalloc(&h->cmp_scan, scan_bytes + 256));
-            h->cmp_scan_bytes = scan_bytes + 256;
-        }
-    }
-    // operator path: counts / offsets of every chunk (one uint64 per row + one per chunk), scan scratch, staging block
-    const CopLayout cop_lay(n, top_k, n_chunks);
-    if (cop) {
-        if (!cop->row || !cop->precursor_idx || !cop->rank || !cop->features || !cop->fragment_row ||
-            !cop->fragment_precursor_idx || !cop->fragment_rank || !cop->fragment_mz_library || !cop->fragment_mz ||
-            !cop->fragment_mz_observed || !cop->fragment_height || !cop->fragment_intensity || !cop->fragment_mass_error ||
-            !cop->fragment_correlation || !cop->fragment_position || !cop->fragment_number || !cop->fragment_type ||
-            !cop->fragment_charge || !cop->fragment_loss_type)
-            return fail(ADH_ERR_INVALID_ARGUMENT, "compact output buffer is NULL");
-        // the caller's arrays are usually fresh allocations: ask for huge pages where the kernel gives them on request
-        // (270 000 first-touch faults of 4 KiB pages per 3 M candidates otherwise, taken by the copying threads)
-        {
-            auto advise = [](void *p, size_t bytes) {
-                const uintptr_t lo = ((uintptr_t)p + (2u << 20) - 1) & ~(uintptr_t)((2u << 20) - 1);
-                const uintptr_t hi = ((uintptr_t)p + bytes) & ~(uintptr_t)((2u << 20) - 1);
-                if (hi > lo) (void)madvise((void *)lo, hi - lo, MADV_HUGEPAGE);
-            };
-            const size_t rc_ = (size_t)cop->rows_capacity, sc_ = (size_t)cop->slots_capacity;
-            advise(cop->features, rc_ * ADH_NUM_FEATURES * 4);
-            advise(cop->row, rc_ * 4), advise(cop->precursor_idx, rc_ * 4);
-            void *const s4[] = {cop->fragment_row, cop->fragment_precursor_idx, cop->fragment_mz_library, cop->fragment_mz,
-                                cop->fragment_mz_observed, cop->fragment_height, cop->fragment_intensity,
-                                cop->fragment_mass_error, cop->fragment_correlation};
-            for (void *p4 : s4) advise(p4, sc_ * 4);
-            void *const s1[] = {cop->fragment_rank, cop->fragment_position, cop->fragment_number, cop->fragment_type,
-                                cop->fragment_charge, cop->fragment_loss_type};
-            for (void *p1 : s1) advise(p1, sc_);
-        }
-        const size_t cnt_bytes = (size_t)(n + n_chunks) * 8;
-        if (h->cop_cnt_bytes < cnt_bytes) {
-            HIP_TRY(hipDeviceSynchronize());
-            if (h->cop_cnt) (void)hipFree(h->cop_cnt);
-            h->cop_cnt = nullptr, h->cop_cnt_bytes = 0;
-            HIP_TRY(hipMalloc(&h->cop_cnt, cnt_bytes + cnt_bytes / 8));
-            h->cop_cnt_bytes = cnt_bytes + cnt_bytes / 8;
-        }
-        int64_t longest = 0;
-        for (int64_t ci = 0; ci < n_chunks; ++ci) longest = std::max(longest, cut[(size_t)ci + 1] - cut[(size_t)ci]);
-        size_t scan_bytes = 0;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (int)(longest + 1), sk));
-        if (h->cop_scan_bytes < scan_bytes) {
-            HIP_TRY(hipDeviceSynchronize());
-            if (h->cop_scan) (void)hipFree(h->cop_scan);
-            h->cop_scan = nullptr, h->cop_scan_bytes = 0;
-            HIP_TRY(hipMalloc(&h->cop_scan, scan_bytes + 256));
-            h->cop_scan_bytes = scan_bytes + 256;
-        }
-        if (h->cop_stage_bytes < cop_lay.total) {
-            if (h->cop_stage) (void)hipHostFree(h->cop_stage);
-            h->cop_stage = nullptr, h->cop_stage_bytes = 0;
-            HIP_TRY(hipHostMalloc(&h->cop_stage, cop_lay.total + cop_lay.total / 8, hipHostMallocDefault));
-            h->cop_stage_bytes = cop_lay.total + cop_lay.total / 8;
-        }
-        if (n_chunks > 4096) return fail(ADH_ERR_UNSUPPORTED, "compact output: more than 4096 chunks");
-        if (!h->cop_tot_pinned) HIP_TRY(hipHostMalloc((void **)&h->cop_tot_pinned, 4096 * 8, hipHostMallocDefault));
-        if (h->cop_dev_bytes < cop_lay.total) {
-            HIP_TRY(hipDeviceSynchronize());
-            if (h->cop_dev) (void)hipFree(h->cop_dev);
-            h->cop_dev = nullptr, h->cop_dev_bytes = 0;
-            const size_t want = cop_lay.total + cop_lay.total / 8 + 4096;
-            HIP_TRY(hipMalloc(&h->cop_dev, want));
-            h->cop_dev_bytes = want;
-        }
-    }
-    unsigned char *const cop_stage = static_cast<unsigned char *>(h->cop_stage);
-    unsigned char *const cop_dev = static_cast<unsigned char *>(h->cop_dev);
-    std::vector<hipEvent_t> cop_tot_ready;   // per chunk: its totals are on the host (events return with aux_events)
-    std::vector<uint64_t> &cop_tot_host = h->cop_tot_host;
-    if (cop) cop_tot_host.assign((size_t)n_chunks, 0);
-    // the block of chunk ci: wait for its totals (its kernels are done then), ONE copy of the used bytes
-    auto flush_cop = [&](int64_t ci) -> int {
-        HIP_TRY(hipEventSynchronize(cop_tot_ready[(size_t)ci]));
-        const uint64_t tot = h->cop_tot_pinned[ci];
-        cop_tot_host[(size_t)ci] = tot;
-        const CopBlock L(tot >> 32, tot & 0xFFFFFFFFull);
-        const size_t base = cop_lay.base(cut[(size_t)ci], ci);
-        if (L.total > 0) HIP_TRY(hipMemcpyAsync(cop_stage + base, cop_dev + base, L.total, hipMemcpyDeviceToHost, so));
-        h->d2h_bytes += L.total + 8;
-        hipEvent_t ev = nullptr;
-        int rc_e = get_event(h, &ev);
-        if (rc_e != ADH_OK) return rc_e;
-        HIP_TRY(hipEventRecord(ev, so));
-        chunk_done.push_back(ev);
-        return ADH_OK;
-    };
-    // host threads unpack finished blocks into the caller's arrays WHILE the later chunks are enqueued and scored (the
-    // enqueue loop waits for every chunk's totals, so it takes as long as the kernels: with the team started behind it
-    // the unpacking - 2 ms per 450 000-row block - came on top: 32 ms per 3 M candidates).  The team takes the blocks
-    // as their copies complete (BlockHandoff; flush_cop appends the events), thread w takes stripe w of T of every block.
-    // base[ci] / cnt[ci] are written once, by the watcher of chunk ci before it publishes the chunk, and never again:
-    // a worker reads only its own chunk's pair (a chunk that does not fit - and every one behind it - is published
-    // with a count of 0).
-    std::vector<int64_t> cop_base_r((size_t)n_chunks + 1, 0), cop_base_s((size_t)n_chunks + 1, 0);
-    std::vector<int64_t> cop_cnt_r((size_t)n_chunks, 0), cop_cnt_s((size_t)n_chunks, 0);
-    bool cop_overflow = false;
-    const int cop_T = cop ? host_threads_for(n) : 0;
-    int cop_started = 0;
-    BlockHandoff cop_handoff(cop ? n_chunks : 0, h->device);
-    cop_handoff.landed = [&](int64_t ci) {
-        const uint64_t tot = cop_tot_host[(size_t)ci];
-        cop_base_r[(size_t)ci + 1] = cop_base_r[(size_t)ci] + (int64_t)(tot >> 32);
-        cop_base_s[(size_t)ci + 1] = cop_base_s[(size_t)ci] + (int64_t)(tot & 0xFFFFFFFFull);
-        if (cop_base_r[(size_t)ci + 1] > cop->rows_capacity || cop_base_s[(size_t)ci + 1] > cop->slots_capacity)
-            cop_overflow = true;
-        // count on (the caller learns what it needs); an overflowing chunk and all behind it copy nothing
-        cop_cnt_r[(size_t)ci] = cop_overflow ? 0 : (int64_t)(tot >> 32);
-        cop_cnt_s[(size_t)ci] = cop_overflow ? 0 : (int64_t)(tot & 0xFFFFFFFFull);
-        if (timing)
-            fprintf(stderr, "[adh]   compact chunk %lld: %lld rows, %lld slots on the host %.2f ms after the call began\n",
-                    (long long)ci, (long long)(tot >> 32), (long long)(tot & 0xFFFFFFFFull), now() - t_0);
-    };
-    HandoffTeam cop_team(cop_handoff);
-    auto cop_stripe = [&](int64_t ci, int w) {
-        if (cop_cnt_r[(size_t)ci] == 0 && cop_cnt_s[(size_t)ci] == 0) return;
-        cop_copy_stripe(cop_stage + cop_lay.base(cut[(size_t)ci], ci), cop_cnt_r[(size_t)ci], cop_cnt_s[(size_t)ci],
-                        cop_base_r[(size_t)ci], cop_base_s[(size_t)ci], cop, w, cop_T, c, h->h_lib.data());
-    };
-    auto cop_worker = [&](int w) {
-        for (int64_t ci = 0; ci < n_chunks; ++ci) {
-            if (!cop_handoff.wait_for(ci)) return;
-            cop_stripe(ci, w);
-        }
-    };
-    unsigned char *const cmp_dev = static_cast<unsigned char *>(h->cmp_dev), *const cmp_host = static_cast<unsigned char *>(h->cmp_host);
-    // compacted copy-out: the host team expands landed blocks WHILE the later chunks are enqueued and scored - the
-    // enqueue loop waits for every chunk's pack kernel, so it lasts as long as the kernels, and a team started behind
-    // it (as the padded path's rebuild team is) had all blocks but none done at that point: 3 M candidates 25 - 30 ms,
-    // the team finishing 6 ms after the last copy.  The team takes the chunks as their copies complete (BlockHandoff;
-    // the enqueue loop appends the events behind flush_compact); worker w takes stripe w of T of every chunk.
-    const int fill_T = compact ? host_threads_for(n) : 0;
-    BlockHandoff fill_handoff(compact ? n_chunks : 0, h->device);
-    if (dbg_events) fill_handoff.landed = [&](int64_t ci) { dbg_told[(size_t)ci] = now() - t_0; };
-    HandoffTeam fill_team(fill_handoff);
-    // A chunk is handed out in tiles of kFillTile rows (on multiples of it: fill_host_rows works in aligned groups of 16
-    // rows), claimed one by one.  With one fixed stripe per thread a chunk took as long as its slowest thread: of the 16
-    // stripes of a 500 000-row block the quickest took 1.1 ms and the slowest 1.7 - 2.4 (team and enqueue thread are 17
-    // on a quota of 16 cores), and the team was 0.5 - 1.2 ms behind the last copy (profiles/headline_pipeline.json,
-    // `fixed_stripes`).
-    constexpr int64_t kFillTile = 2048;
-    std::vector<std::atomic<int64_t>> fill_next((size_t)n_chunks);
-    for (std::atomic<int64_t> &next : fill_next) next.store(0, std::memory_order_relaxed);
-    auto fill_stripe = [&](int64_t ci, int w) {  // (thread w's share of chunk ci; w only names it in the debug times)
-        const int64_t a = cut[(size_t)ci], b = cut[(size_t)ci + 1];
-        const double t_in = dbg_events ? now() : 0.0;
-        for (;;) {
-            const int64_t t = a / kFillTile + fill_next[(size_t)ci].fetch_add(1, std::memory_order_relaxed);
-            const int64_t lo = std::max(a, t * kFillTile), hi = std::min(b, (t + 1) * kFillTile);
-            if (lo >= b) break;
-            fill_host_rows(h, c, out, cmp_host + play.base(a, ci), b - a, a, lo, hi);
-        }
-        if (dbg_events && w < dbg_T) {
-            dbg_stripe_done[(size_t)ci * (size_t)dbg_T + (size_t)w] = now() - t_0;
-            dbg_stripe_took[(size_t)ci * (size_t)dbg_T + (size_t)w] = now() - t_in;
-        }
-    };
-    auto fill_worker = [&](int w) {
-        for (int64_t ci = 0; ci < n_chunks; ++ci) {
-            // (waiting threads sleep: a team that spins burns the CPU quota the busy ones need)
-            if (!fill_handoff.wait_for(ci)) return;
-            fill_stripe(ci, w);
-        }
-    };
-    const double t_1 = now();
-    std::vector<hipEvent_t> dbg;
-    std::vector<uint64_t> dbg_bytes;  // copy-out bytes of every chunk
-    hipEvent_t dbg_start = nullptr;   // on the copy-in stream, before the first column goes up
-    struct DbgEvents {  // (the ADH_DEBUG_TIMING=2 events go on every way out of the call)
-        std::vector<hipEvent_t> &spans, &marks;
-        hipEvent_t &start;
-        ~DbgEvents() {
-            for (hipEvent_t e : spans) (void)hipEventDestroy(e);
-            for (hipEvent_t e : marks) (void)hipEventDestroy(e);
-            if (start) (void)hipEventDestroy(start);
-        }
-    } dbg_guard{dbg, dbg_k, dbg_start};
-    auto fail_sync = [&](int code) {
-        (void)hipDeviceSynchronize();
-        (void)hipGetLastError();
-        return code;
-    };
-    // the packed block of chunk ci: wait for its pack kernel (an event on the scoring stream - the next chunk's kernels
-    // are already queued; never a copy behind the copy-out backlog), ONE copy of its used bytes, then mark the chunk
-    // complete for the host team
-    auto flush_compact = [&](int64_t ci) -> int {
-        const int64_t a = cut[(size_t)ci], b = cut[(size_t)ci + 1];
-        HIP_TRY(hipEventSynchronize(tot_ready[(size_t)ci]));
-        if (dbg_events) dbg_tot_seen[(size_t)ci] = now() - t_0;
-        const PadBlock L((uint64_t)(b - a), (uint64_t)h->cmp_tot_pinned[ci]);
-        const size_t base = play.base(a, ci);
-        HIP_TRY(hipMemcpyAsync(cmp_host + base, cmp_dev + base, L.total, hipMemcpyDeviceToHost, so));
-        h->d2h_bytes += L.total;
-        hipEvent_t ev = nullptr;
-        int rc_e = get_event(h, &ev);
-        if (rc_e != ADH_OK) return rc_e;
-        HIP_TRY(hipEventRecord(ev, so));
-        chunk_done.push_back(ev);
-        return ADH_OK;
-    };
-    // the tables of chunk ci that travel as they are (all of them, the wire columns, or valid + features beside the packed
-    // block), row range by row range
-    // (A chunk is up to nine copies and the engine idles ~10 us between two of them - a 47 000-row chunk, 21 MB, takes
-    // 0.46 ms = 46 GB/s where each copy runs at 55, `rocprofv3 --memory-copy-trace` - but a second copy-out stream for
-    // the feature table does not fill the gaps: measured in round 5, same times to the 0.01 ms, and taken out again.)
-    auto copy_tables = [&](int64_t ci) -> int {
-        const int64_t a = cut[(size_t)ci], b = cut[(size_t)ci + 1];
-        if (dbg_events) {
-            hipEvent_t e0, e1;
-            (void)hipEventCreate(&e0);
-            (void)hipEventCreate(&e1);
-            (void)hipEventRecord(e0, so);
-            dbg.push_back(e0);
-            dbg.push_back(e1);
-            dbg_bytes.push_back(h->d2h_bytes);
-        }
-        for (int i = 0; i < kNumOutFields && !cop && !resident; ++i) {
-            const OutFieldDesc &f = kOutFields[i];
-            void *host = *out_member(out, f);
-            const bool is_slot = f.member == offsetof(adh_output_t, fragment_lib_slot);
-            const bool is_stat = f.member == offsetof(adh_output_t, stat_matched_peaks);
-            if (is_slot && !host && rebuild) host = slot_host;
-            if (!host) continue;
-            if (rebuild && !f.wire && !is_stat) continue;  // rebuilt on the host below
-            if (compact && f.per_row < 0) continue;        // the fragment tables travel packed (flush_compact)
-            const size_t rb = out_row_bytes(f, top_k);
-            hipError_t e = hipMemcpyAsync(static_cast<unsigned char *>(host) + (size_t)a * rb,
-                                          static_cast<unsigned char *>(*out_member(&dev, f)) + (size_t)a * rb,
-                                          (size_t)(b - a) * rb, hipMemcpyDeviceToHost, so);
-            if (e != hipSuccess) return fail(ADH_ERR_HIP, std::string("hipMemcpyAsync D2H: ") + hipGetErrorString(e));
-            h->d2h_bytes += (uint64_t)(b - a) * rb;
-        }
-        if (rebuild && !compact) {
-            hipEvent_t ev = nullptr;
-            int rc_e = get_event(h, &ev);
-            if (rc_e != ADH_OK) return rc_e;
-            HIP_TRY(hipEventRecord(ev, so));
-            chunk_done.push_back(ev);
-        }
-        if (dbg_events) {
-            (void)hipEventRecord(dbg.back(), so);
-            dbg_bytes.back() = h->d2h_bytes - dbg_bytes.back();
-        }
-        return ADH_OK;
-    };
+    const CopyOut call(h, c, dev, cut, chunk_done, tot_ready, trace);
+    std::unique_ptr<CopyOut> copy_out;  // (behind `unwind`: a failed call joins its team before the device is synchronised)
+    if (resident) copy_out.reset(new CopyOut(call));
+    else if (cop) copy_out.reset(new OperatorCopyOut(call, cop));
+    else if (compact) copy_out.reset(new PackedCopyOut(call, out));
+    else copy_out.reset(new PlainCopyOut(call, out, rebuild));
+    rc = copy_out->prepare();
+    if (rc != ADH_OK) return rc;
+    trace.t_1 = trace.now();
     // The copy-in stream, in order: columns(0) plan(0) | columns(1) plan(1) | columns(2) | plan(2) | columns(3 .. last)
     // | plan(3) ...: every chunk up to 2 goes up just ahead of its plan, ALL later rows in one burst behind the plan of
     // chunk 2 (one H2D per column).  One burst, because uploads of every chunk beside the copy-outs slowed those down
@@ -2044,35 +1266,14 @@ int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring
     // for all of it: with the burst behind plan(1) the kernels of chunk 2 started 1.4 - 1.7 ms after those of chunk 1
     // had ended and the copy-out had a hole of 1.15 ms (profiles/headline_pipeline.json, `before`).  The burst
     // overlaps the copy-out of chunks 0 and 1 in both orders: that copy runs at 47 - 49 instead of 56 GB/s.
-    // (ADH_H2D_BURST_LATE=0: the whole burst before the plan of chunk 1, the order of round 3)
-    const char *late_env = getenv("ADH_H2D_BURST_LATE");
-    const bool late_burst = !(late_env && atoi(late_env) == 0);
-    if (dbg_events) {
-        (void)hipEventCreate(&dbg_start);
-        (void)hipEventRecord(dbg_start, si);
-        dbg_start_host = now() - t_0;
-    }
+    trace.mark_start(si);
     rc = cand_upload_range(h, c, 0, cut[1], si);
     if (rc == ADH_OK) rc = plan_enqueue(h, h->slots[0], cfg, 0, cut[1], si);
-    if (rc == ADH_OK && n_chunks > 1) rc = cand_upload_range(h, c, cut[1], late_burst ? cut[2] : n, si);
-    if (rc != ADH_OK) return fail_sync(rc);
+    if (rc == ADH_OK && n_chunks > 1) rc = cand_upload_range(h, c, cut[1], cut[2], si);
+    if (rc != ADH_OK) return rc;
     // the host teams start now that the device has work: started in front of the first copy-in, the 16 threads made
     // the call's set-up 0.4 - 0.5 ms instead of 0.07 - 0.10 (profiles/headline_pipeline.json, `setup_ms`)
-    for (int w = 0; w < cop_T; ++w) {
-        try {
-            cop_team.threads.emplace_back(cop_worker, w);
-            ++cop_started;
-        } catch (const std::system_error &) {
-            break;
-        }
-    }
-    for (int w = 0; w < fill_T; ++w) {
-        try {
-            fill_team.threads.emplace_back(fill_worker, w);
-        } catch (const std::system_error &) {
-            break;  // (the threads there are - at the end the calling thread too - take the tiles)
-        }
-    }
+    copy_out->start_team();
     for (int64_t ci = 0; ci < n_chunks; ++ci) {
         const int64_t a = cut[(size_t)ci], b = cut[(size_t)ci + 1];
         const int ps = (int)(ci & 1);
@@ -2082,237 +1283,35 @@ int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring
             if (ci >= 1) HIP_TRY(hipStreamWaitEvent(si, h->ev_k[ps ^ 1], 0));
             rc = plan_enqueue(h, h->slots[ps ^ 1], cfg, a2, b2 - a2, si);
             // (the rows of chunk 2 behind the plan of chunk 1, ALL later rows behind the plan of chunk 2: see above)
-            if (rc == ADH_OK && late_burst && ci == 0 && n_chunks > 2) rc = cand_upload_range(h, c, cut[2], cut[3], si);
-            if (rc == ADH_OK && late_burst && ci == 1 && n_chunks > 3) rc = cand_upload_range(h, c, cut[3], n, si);
-            if (rc != ADH_OK) return fail_sync(rc);
+            if (rc == ADH_OK && ci == 0 && n_chunks > 2) rc = cand_upload_range(h, c, cut[2], cut[3], si);
+            if (rc == ADH_OK && ci == 1 && n_chunks > 3) rc = cand_upload_range(h, c, cut[3], n, si);
+            if (rc != ADH_OK) return rc;
         }
         Plan p;
         rc = plan_finish(h, h->slots[ps], cfg, a, b - a, p);
-        auto dbg_mark = [&] {  // (ADH_DEBUG_TIMING=2: a time stamp on the scoring stream)
-            hipEvent_t e = nullptr;
-            if (dbg_events && hipEventCreate(&e) == hipSuccess) {
-                (void)hipEventRecord(e, sk);
-                dbg_k.push_back(e);
-            }
-        };
-        dbg_mark();
+        trace.mark(sk);
         if (rc == ADH_OK) rc = launch_scoring(h, p, cfg, &dev_k, sk);
-        dbg_mark();
-        if (rc != ADH_OK) return fail_sync(rc);
-        if (compact) {  // filled slots per row, their offsets, the packed block: behind the chunk's kernels
-            unsigned char *blk = cmp_dev + play.base(a, ci);
-            uint32_t *d_off = reinterpret_cast<uint32_t *>(blk);
-            const int64_t nr = b - a;
-            hipLaunchKernelGGL(adh_slot_count_kernel, dim3((unsigned)((nr + 256) / 256)), dim3(256), 0, sk, dev.fragment_lib_slot, a,
-                               nr, top_k, d_off);
-            size_t scan_bytes = h->cmp_scan_bytes;
-            HIP_TRY(hipcub::DeviceScan::ExclusiveSum(h->cmp_scan, scan_bytes, d_off, d_off, (int)(nr + 1), sk));
-            hipLaunchKernelGGL(adh_pad_pack_kernel, dim3((unsigned)((nr * top_k + 255) / 256)), dim3(256), 0, sk, dev, a, nr, top_k,
-                               blk, h->cmp_tot_pinned + ci);
-            HIP_TRY(hipGetLastError());
-            hipEvent_t ev = nullptr;  // (when the total can be read)
-            rc = get_event(h, &ev);
-            if (rc != ADH_OK) return fail_sync(rc);
-            HIP_TRY(hipEventRecord(ev, sk));
-            tot_ready.push_back(ev);
-        }
-        uint64_t *cop_off = cop ? static_cast<uint64_t *>(h->cop_cnt) + a + ci : nullptr;
-        if (cop) {
-            const int64_t nr = b - a;
-            hipLaunchKernelGGL(adh_cop_count_kernel, dim3((unsigned)((nr + 256) / 256)), dim3(256), 0, sk, dev.valid,
-                               dev.fragment_lib_slot, a, nr, top_k, cop_off);
-            size_t scan_bytes = h->cop_scan_bytes;
-            HIP_TRY(hipcub::DeviceScan::ExclusiveSum(h->cop_scan, scan_bytes, cop_off, cop_off, (int)(nr + 1), sk));
-            hipLaunchKernelGGL(adh_cop_pack_kernel, dim3((unsigned)std::min<int64_t>((nr * top_k + 255) / 256, 8192)), dim3(256), 0,
-                               sk, dev, h->cs.d, h->d_lib, a, nr, top_k, cop_off, cop_dev + cop_lay.base(a, ci), h->cop_tot_pinned + ci);
-            HIP_TRY(hipGetLastError());
-            hipEvent_t ev = nullptr;  // (when the totals can be read)
-            rc = get_event(h, &ev);
-            if (rc != ADH_OK) return fail_sync(rc);
-            HIP_TRY(hipEventRecord(ev, sk));
-            aux_events.push_back(ev);
-            cop_tot_ready.push_back(ev);
-        }
-        dbg_mark();
+        trace.mark(sk);
+        if (rc == ADH_OK) rc = copy_out->pack(ci);
+        if (rc != ADH_OK) return rc;
+        trace.mark(sk);
         HIP_TRY(hipEventRecord(h->ev_k[ps], sk));
-        if (cop && ci > 0) {  // the block of the previous chunk, now that the host can know its size
-            rc = flush_cop(ci - 1);
-            if (rc != ADH_OK) return fail_sync(rc);
-            rc = cop_handoff.append(chunk_done.back());
-            if (rc != ADH_OK) return fail_sync(rc);
-        }
-        // Copy-out.  Compacted: the packed block of a chunk goes AHEAD of its valid / features rows (from chunk 1 on: the
-        // link is busy with chunk ci - 1 when the kernels of chunk ci end, so that the host enqueues both only once it
-        // knows the block's length costs nothing).  The team expands a block while the rows that need no work follow
-        // it on the link - with the rows first, the blocks of the last three chunks landed within the last 1.4 ms of
-        // the copy-out and the team ended 1.0 - 1.3 ms after the last copy (profiles/headline_pipeline.json, `before`,
-        // `handoff_ms`).  Chunk 0 keeps its rows first: they leave the moment its kernels end.
-        if (compact && ci > 0) {  // (flush_compact waits for the pack kernel of chunk ci - 1: its kernels are done)
-            rc = flush_compact(ci - 1);
-            if (rc != ADH_OK) return fail_sync(rc);
-            rc = fill_handoff.append(chunk_done.back());
-            if (rc != ADH_OK) return fail_sync(rc);
-            if (ci > 1) rc = copy_tables(ci - 1);
-            if (rc != ADH_OK) return fail_sync(rc);
-        }
-        if (!compact || ci == 0) {
-            HIP_TRY(hipStreamWaitEvent(so, h->ev_k[ps], 0));
-            rc = copy_tables(ci);
-            if (rc != ADH_OK) return fail_sync(rc);
-        }
+        rc = copy_out->copy_out(ci);
+        if (rc != ADH_OK) return rc;
     }
-    if (compact) {
-        rc = flush_compact(n_chunks - 1);
-        if (rc != ADH_OK) return fail_sync(rc);
-        rc = fill_handoff.append(chunk_done.back());
-        if (rc != ADH_OK) return fail_sync(rc);
-        if (n_chunks > 1) rc = copy_tables(n_chunks - 1);
-        if (rc != ADH_OK) return fail_sync(rc);
-    }
-    if (cop) {
-        rc = flush_cop(n_chunks - 1);
-        if (rc != ADH_OK) return fail_sync(rc);
-        rc = cop_handoff.append(chunk_done.back());
-        if (rc != ADH_OK) return fail_sync(rc);
-    }
-    const double t_2 = now();
+    rc = copy_out->flush();
+    if (rc != ADH_OK) return rc;
+    trace.t_2 = trace.now();
     rc = comm_gather_slot(h, slot);  // after the last chunk's kernels; overlaps the remaining D2H
-    if (rc != ADH_OK) return fail_sync(rc);
-    if (cop) {
-        // the blocks still on their way, then the threads (they have been unpacking since the first block landed)
-        // (the calling thread joins the watch: a team of no threads still gets every block published)
-        if (!cop_handoff.wait_for(n_chunks - 1)) {
-            fail(ADH_ERR_HIP, std::string("scoring pipeline (compact copy-out): ") + hipGetErrorString(cop_handoff.error));
-            return fail_sync(ADH_ERR_HIP);
-        }
-        cop_team.join_all();
-        for (int64_t ci = 0; ci < n_chunks; ++ci)  // (stripes of threads that could not be started)
-            for (int w = cop_started; w < cop_T; ++w) cop_stripe(ci, w);
-        if (timing) fprintf(stderr, "[adh]   compact: host team done %.2f ms after the call began (%d threads)\n", now() - t_0, cop_T);
-        cop->n_rows = cop_base_r[(size_t)n_chunks];
-        cop->n_slots = cop_base_s[(size_t)n_chunks];
-        if (cop_overflow) {
-            (void)hipStreamSynchronize(sk);
-            (void)hipStreamSynchronize(so);
-            unwind.ok = true;  // (the device tables are complete)
-            h->tables_current = true;
-            return fail(ADH_ERR_INVALID_ARGUMENT, "compact output: rows_capacity / slots_capacity too small (n_rows / n_slots say what is needed)");
-        }
-    }
-    if (compact) {
-        // the blocks still on their way, then the team (it has been expanding since the first block landed)
-        if (!fill_handoff.wait_for(n_chunks - 1)) {
-            fail(ADH_ERR_HIP, std::string("scoring pipeline (compacted copy-out): ") + hipGetErrorString(fill_handoff.error));
-            return fail_sync(ADH_ERR_HIP);
-        }
-        for (int64_t ci = 0; ci < n_chunks; ++ci) fill_stripe(ci, fill_T);  // (this thread takes what is left)
-        fill_team.join_all();
-        if (timing) fprintf(stderr, "[adh]   compacted copy-out: host team done %.2f ms after the call began (%d threads)\n", now() - t_0, fill_T);
-    } else if (rebuild) {
-        // host threads follow the copy-out stream chunk by chunk: thread w takes the w-th stripe of every chunk
-        const int T = host_threads_for(n);
-        std::atomic<int64_t> ready{0};
-        std::atomic<bool> abort{false};
-        auto worker = [&](int w) {
-            for (int64_t ci = 0; ci < n_chunks; ++ci) {
-                while (ready.load(std::memory_order_acquire) <= ci) {
-                    if (abort.load(std::memory_order_relaxed)) return;
-                    std::this_thread::yield();
-                }
-                const int64_t a = cut[(size_t)ci], b = cut[(size_t)ci + 1];
-                const int64_t lo = a + (b - a) * w / T, hi = a + (b - a) * (w + 1) / T;
-                rebuild_host_rows(h, c, out, slot_host, lo, hi);
-            }
-        };
-        std::vector<std::thread> team;
-        for (int w = 1; w < T; ++w) {
-            try {
-                team.emplace_back(worker, w);
-            } catch (const std::system_error &) {
-                break;  // (the calling thread takes the stripes that have no thread)
-            }
-        }
-        const int started = (int)team.size() + 1;
-        hipError_t ee = hipSuccess;
-        for (int64_t ci = 0; ci < n_chunks && ee == hipSuccess; ++ci) {
-            ee = hipEventSynchronize(chunk_done[(size_t)ci]);
-            if (ee != hipSuccess) break;
-            ready.store(ci + 1, std::memory_order_release);
-            const int64_t a = cut[(size_t)ci], b = cut[(size_t)ci + 1];
-            auto stripe = [&](int w) {
-                const int64_t lo = a + (b - a) * w / T, hi = a + (b - a) * (w + 1) / T;
-                rebuild_host_rows(h, c, out, slot_host, lo, hi);
-            };
-            stripe(0);
-            for (int w = started; w < T; ++w) stripe(w);
-        }
-        if (ee != hipSuccess) abort.store(true);
-        for (std::thread &t : team) t.join();
-        if (ee != hipSuccess) {
-            fail(ADH_ERR_HIP, std::string("scoring pipeline (copy-out): ") + hipGetErrorString(ee));
-            return fail_sync(ADH_ERR_HIP);
-        }
+    if (rc == ADH_OK) rc = copy_out->finish();
+    if (rc != ADH_OK) {
+        unwind.ok = h->tables_current = copy_out->tables_stand;  // (the operator mode's overflow: the device tables are complete)
+        return rc;
     }
     hipError_t e = hipStreamSynchronize(sk);
-    if (e == hipSuccess) e = hipStreamSynchronize(so);
-    if (e != hipSuccess) {
-        fail(ADH_ERR_HIP, std::string("scoring pipeline: ") + hipGetErrorString(e));
-        return fail_sync(ADH_ERR_HIP);
-    }
-    if (timing)
-        fprintf(stderr, "[adh] score_candidates n=%lld in %lld chunks: setup %.2f ms, enqueue %.2f, drain %.2f\n",
-                (long long)n, (long long)n_chunks, t_1 - t_0, t_2 - t_1, now() - t_2);
-    if (dbg_events) {
-        for (size_t i = 0; i + 1 < dbg.size(); i += 2) {
-            float ms = 0.f, since = 0.f;
-            (void)hipEventElapsedTime(&ms, dbg[i], dbg[i + 1]);
-            (void)hipEventElapsedTime(&since, dbg[0], dbg[i]);
-            float from_start = 0.f;
-            if (dbg_start) (void)hipEventElapsedTime(&from_start, dbg_start, dbg[i]);
-            fprintf(stderr, "[adh]   chunk %zu (%lld rows): D2H starts %.2f ms after the first (%.2f ms after the call's first copy-in), "
-                            "lasts %.2f ms for %.1f MB = %.1f GB/s\n",
-                    i / 2, (long long)(cut[i / 2 + 1] - cut[i / 2]), since, from_start, ms, (double)dbg_bytes[i / 2] / 1e6,
-                    (double)dbg_bytes[i / 2] / 1e6 / std::max(ms, 1e-3f));
-        }
-        // the hand-off of the packed blocks; a copy's end is its event's time behind dbg_start, put on the host's clock
-        // at the moment dbg_start was recorded (the copy-in stream is idle then)
-        const double t_ret = now() - t_0;
-        double last_landed = 0.0;
-        for (size_t ci = 0; compact && dbg_start && ci < chunk_done.size() && ci < dbg_told.size(); ++ci) {
-            float landed = 0.f;
-            (void)hipEventElapsedTime(&landed, dbg_start, chunk_done[ci]);
-            last_landed = dbg_start_host + landed;
-            double team_done = 0.0, took_lo = 1e30, took_hi = 0.0;
-            for (int w = 0; w < dbg_T; ++w) {
-                team_done = std::max(team_done, dbg_stripe_done[ci * (size_t)dbg_T + (size_t)w]);
-                took_lo = std::min(took_lo, dbg_stripe_took[ci * (size_t)dbg_T + (size_t)w]);
-                took_hi = std::max(took_hi, dbg_stripe_took[ci * (size_t)dbg_T + (size_t)w]);
-            }
-            fprintf(stderr, "[adh]   block %zu: total seen %.2f ms after the call began, copy ended %.2f, team told %.2f (lag %.2f), "
-                            "last thread done %.2f (a stripe took %.2f - %.2f ms)\n",
-                    ci, dbg_tot_seen[ci], last_landed, dbg_told[ci], dbg_told[ci] - last_landed, team_done, took_lo, took_hi);
-        }
-        if (compact && dbg_start)
-            fprintf(stderr, "[adh]   tail: the call returns %.2f ms after it began, %.2f ms after the last copy ended\n", t_ret,
-                    t_ret - last_landed);
-        // the scoring stream: a chunk's kernels, its helpers (count, scan, pack), the idle time in front of it
-        double k_sum = 0.0;
-        for (size_t i = 0; i + 2 < dbg_k.size(); i += 3) {
-            float k_ms = 0.f, help_ms = 0.f, idle_ms = 0.f, at = 0.f;
-            (void)hipEventElapsedTime(&k_ms, dbg_k[i], dbg_k[i + 1]);
-            (void)hipEventElapsedTime(&help_ms, dbg_k[i + 1], dbg_k[i + 2]);
-            if (i >= 3) (void)hipEventElapsedTime(&idle_ms, dbg_k[i - 1], dbg_k[i]);
-            if (dbg_start) (void)hipEventElapsedTime(&at, dbg_start, dbg_k[i]);
-            k_sum += (double)k_ms + (double)help_ms;
-            fprintf(stderr, "[adh]   chunk %zu: kernels start %.2f ms after the call's first copy-in, last %.2f ms, helpers %.3f ms, "
-                            "scoring stream idle before them %.2f ms\n", i / 3, at, k_ms, help_ms, idle_ms);
-        }
-        if (dbg_k.size() >= 3) {
-            float span = 0.f;
-            (void)hipEventElapsedTime(&span, dbg_k.front(), dbg_k.back());
-            fprintf(stderr, "[adh]   scoring stream: %.2f ms from the first kernel to the last helper, %.2f ms of them busy\n", span, k_sum);
-        }
-    }
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream_out);
+    if (e != hipSuccess) return fail(ADH_ERR_HIP, std::string("scoring pipeline: ") + hipGetErrorString(e));
+    trace.report(cut, chunk_done, compact);
     unwind.ok = true;
     h->tables_current = true;
     return ADH_OK;
@@ -2568,6 +1567,17 @@ int adh_trim_device_cache(void) {
 int adh_host_threads(int64_t n_rows, int32_t *threads, int32_t *cpu_budget) {
     if (threads) *threads = host_threads_for(n_rows);
     if (cpu_budget) *cpu_budget = host_cpu_budget();
+    return ADH_OK;
+}
+
+int adh_chunk_cuts(int64_t n_rows, int32_t ion_mobility, int64_t max_rows, int32_t packed, int64_t *cuts, int64_t capacity,
+                   int64_t *n_cuts) {
+    if (n_rows <= 0 || !n_cuts || capacity < 0 || (capacity > 0 && !cuts))
+        return fail(ADH_ERR_INVALID_ARGUMENT, "adh_chunk_cuts: bad argument");
+    const std::vector<int64_t> cut = chunk_cuts(n_rows, ion_mobility != 0, max_rows, packed != 0);
+    *n_cuts = (int64_t)cut.size();  // (what the caller needs, should the array be too short)
+    if (*n_cuts > capacity) return fail(ADH_ERR_INVALID_ARGUMENT, "adh_chunk_cuts: capacity too small (n_cuts says what is needed)");
+    std::copy(cut.begin(), cut.end(), cuts);
     return ADH_OK;
 }
 

@@ -147,41 +147,24 @@ int adh_take_rows(adh_handle_t *h, const int64_t *rows, int64_t n, adh_compact_o
         return fail(ADH_ERR_UNSUPPORTED, "take_rows: more than 2^32 fragment slots");
     out->n_rows = out->n_slots = 0;
     if (n == 0) return ADH_OK;
-    if (!out->row || !out->precursor_idx || !out->rank || !out->features || !out->fragment_row ||
-        !out->fragment_precursor_idx || !out->fragment_rank || !out->fragment_mz_library || !out->fragment_mz ||
-        !out->fragment_mz_observed || !out->fragment_height || !out->fragment_intensity || !out->fragment_mass_error ||
-        !out->fragment_correlation || !out->fragment_position || !out->fragment_number || !out->fragment_type ||
-        !out->fragment_charge || !out->fragment_loss_type)
-        return fail(ADH_ERR_INVALID_ARGUMENT, "compact output buffer is NULL");
+    if (!compact_output_complete(out)) return fail(ADH_ERR_INVALID_ARGUMENT, "compact output buffer is NULL");
     HIP_TRY(hipSetDevice(h->device));
     int rc = materialise_tables(h);  // (ids and library columns of a resident or compact scoring call)
     if (rc != ADH_OK) return rc;
     hipStream_t st = h->stream;
     // device scratch (grow-only, shared with the compact path - both are synchronous): counts [n + 1] then rows [n]
     const size_t cnt_bytes = (size_t)(2 * n + 1) * 8;
-    if (h->cop_cnt_bytes < cnt_bytes) {
-        HIP_TRY(hipDeviceSynchronize());
-        if (h->cop_cnt) (void)hipFree(h->cop_cnt);
-        h->cop_cnt = nullptr, h->cop_cnt_bytes = 0;
-        HIP_TRY(hipMalloc(&h->cop_cnt, cnt_bytes + cnt_bytes / 8));
-        h->cop_cnt_bytes = cnt_bytes + cnt_bytes / 8;
-    }
+    rc = grow_device(&h->cop_cnt, &h->cop_cnt_bytes, cnt_bytes, cnt_bytes / 8);
+    if (rc != ADH_OK) return rc;
     uint64_t *const d_cnt = static_cast<uint64_t *>(h->cop_cnt);
     int64_t *const d_rows = reinterpret_cast<int64_t *>(d_cnt + n + 1);
-    size_t scan_bytes = 0;
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, d_cnt, d_cnt, (int)(n + 1), st));
-    if (h->cop_scan_bytes < scan_bytes) {
-        HIP_TRY(hipDeviceSynchronize());
-        if (h->cop_scan) (void)hipFree(h->cop_scan);
-        h->cop_scan = nullptr, h->cop_scan_bytes = 0;
-        HIP_TRY(hipMalloc(&h->cop_scan, scan_bytes + 256));
-        h->cop_scan_bytes = scan_bytes + 256;
-    }
+    rc = grow_scan_scratch<uint64_t>(&h->cop_scan, &h->cop_scan_bytes, n + 1, st);
+    if (rc != ADH_OK) return rc;
     HIP_TRY(hipMemcpyAsync(d_rows, rows, (size_t)n * 8, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(take::count_kernel, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, st, tab.valid,
                        tab.fragment_lib_slot, d_rows, n, top_k, d_cnt);
     HIP_TRY(hipGetLastError());
-    scan_bytes = h->cop_scan_bytes;
+    size_t scan_bytes = h->cop_scan_bytes;
     HIP_TRY(hipcub::DeviceScan::ExclusiveSum(h->cop_scan, scan_bytes, d_cnt, d_cnt, (int)(n + 1), st));
     uint64_t tot = 0;
     HIP_TRY(hipMemcpyAsync(&tot, d_cnt + n, 8, hipMemcpyDeviceToHost, st));
@@ -194,19 +177,9 @@ int adh_take_rows(adh_handle_t *h, const int64_t *rows, int64_t n, adh_compact_o
         return fail(ADH_ERR_INVALID_ARGUMENT, "take_rows: rows_capacity / slots_capacity too small (n_rows / n_slots say what is needed)");
     if (R == 0) return ADH_OK;
     const take::Block L((uint64_t)R, (uint64_t)S);
-    if (h->cop_dev_bytes < L.total) {
-        HIP_TRY(hipDeviceSynchronize());
-        if (h->cop_dev) (void)hipFree(h->cop_dev);
-        h->cop_dev = nullptr, h->cop_dev_bytes = 0;
-        HIP_TRY(hipMalloc(&h->cop_dev, L.total + L.total / 8 + 4096));
-        h->cop_dev_bytes = L.total + L.total / 8 + 4096;
-    }
-    if (h->cop_stage_bytes < L.total) {
-        if (h->cop_stage) (void)hipHostFree(h->cop_stage);
-        h->cop_stage = nullptr, h->cop_stage_bytes = 0;
-        HIP_TRY(hipHostMalloc(&h->cop_stage, L.total + L.total / 8, hipHostMallocDefault));
-        h->cop_stage_bytes = L.total + L.total / 8;
-    }
+    rc = grow_device(&h->cop_dev, &h->cop_dev_bytes, L.total, L.total / 8 + 4096);
+    if (rc == ADH_OK) rc = grow_pinned(&h->cop_stage, &h->cop_stage_bytes, L.total, L.total / 8);
+    if (rc != ADH_OK) return rc;
     unsigned char *const d_block = static_cast<unsigned char *>(h->cop_dev);
     unsigned char *const block = static_cast<unsigned char *>(h->cop_stage);
     const int64_t work = std::max<int64_t>(n * (int64_t)top_k, n);

@@ -29,6 +29,7 @@ EXPORTED_SYMBOLS = [
     "adh_host_take_objects",
     "adh_trim_device_cache",
     "adh_host_threads",
+    "adh_chunk_cuts",
     "adh_upload_candidates",
     "adh_score_uploaded",
     "adh_get_stream",
@@ -156,6 +157,19 @@ def host_threads(n_rows: int) -> tuple[int, int]:
     fn.argtypes = [C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     _check(fn(int(n_rows), C.byref(t), C.byref(b)), "adh_host_threads")
     return int(t.value), int(b.value)
+
+
+def chunk_cuts(n_rows: int, ion_mobility: bool = False, max_rows: int = 0, packed: bool = False) -> list[int]:
+    """Chunk boundaries of a host -> host scoring call over ``n_rows`` candidates (the library's ``adh_chunk_cuts``):
+    chunk i is rows [cuts[i], cuts[i + 1]).  ``max_rows``: the call's bound on a chunk's rows (0: none); ``packed``:
+    the compacted copy-out of the padded tables is in use.  Reads the ``ADH_CHUNK*`` switches; needs no GPU."""
+    fn = lib.adh_chunk_cuts
+    fn.argtypes = [C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64)]
+    count = C.c_int64(0)
+    fn(int(n_rows), int(ion_mobility), int(max_rows), int(packed), None, 0, C.byref(count))  # (the size query)
+    cuts = (C.c_int64 * max(count.value, 1))()
+    _check(fn(int(n_rows), int(ion_mobility), int(max_rows), int(packed), cuts, len(cuts), C.byref(count)), "adh_chunk_cuts")
+    return list(cuts[: count.value])
 
 
 _pylib = None       # the same library through ctypes.PyDLL: calls keep the GIL (adh_host_take_objects needs that)

@@ -394,6 +394,17 @@ int adh_trim_device_cache(void);
 int adh_host_threads(int64_t n_rows, int32_t *threads, int32_t *cpu_budget);
 
 /*
+ * The chunk boundaries of a host -> host scoring call over n_rows > 0 candidates: chunk i of the pipeline is rows
+ * [cuts[i], cuts[i + 1]), cuts[0] = 0, cuts[*n_cuts - 1] = n_rows.  ion_mobility: the staged run is an ion-mobility run;
+ * max_rows > 0: no chunk longer than that (the call passes the fit of the ion-mobility scratch and the 32-bit offsets of
+ * the compacted copy-outs), 0: no bound; packed: the call uses the compacted copy-out of the padded tables (a short
+ * last chunk).  Reads ADH_CHUNK, ADH_CHUNK_PARTS, ADH_CHUNK_MIN, ADH_FIRST_CHUNK_DIV and ADH_LAST_CHUNK_DIV as the call
+ * does.  *n_cuts is set even where `capacity` entries are too few (ADH_ERR_INVALID_ARGUMENT then).  Needs no GPU.
+ */
+int adh_chunk_cuts(int64_t n_rows, int32_t ion_mobility, int64_t max_rows, int32_t packed, int64_t *cuts, int64_t capacity,
+                   int64_t *n_cuts);
+
+/*
  * dst[i] = src[idx[i]] for n entries of arrays of CPython object pointers (NumPy dtype=object) - the string columns
  * the features frame takes over from the precursor table (scoring.py:430-445 merges them in) - on `threads` host
  * threads, reference counts raised atomically.  The caller must hold the GIL for the whole call (ctypes.PyDLL) and

@@ -1,4 +1,4 @@
-"""GPU tests of the hand-off of landed blocks to the host team (BlockHandoff in adh_score_host.hip): the compacted
+"""GPU tests of the hand-off of landed blocks to the host team (BlockHandoff in adh_copyout.hip): the compacted
 copy-out of adh_score_candidates and the operator's adh_score_candidates_compact give a block to their team when its
 copy ends - a thread of the team waits on the copy's event, the enqueue thread only appends events.  Many small
 chunks and a team of several threads make the threads meet at the hand-off; every table is compared byte for byte

@@ -434,3 +434,76 @@ def test_host_threads_follow_the_cgroup_quota(tmp_path, monkeypatch):
     # the override
     monkeypatch.setenv("ADH_HOST_THREADS", "5")
     assert runtime.host_threads(big)[0] == 5
+
+
+_CHUNK_ENV = ("ADH_CHUNK", "ADH_CHUNK_PARTS", "ADH_CHUNK_MIN", "ADH_FIRST_CHUNK_DIV", "ADH_LAST_CHUNK_DIV")
+
+# (n, ion_mobility, max_rows, packed, environment) -> the cuts of the pipeline as it was before chunk_cuts existed:
+# printed by a host program made of that commit's pick_chunk and cut-building lines (the bound applied where that code
+# applied the fit of the ion-mobility scratch)
+_CHUNK_CUTS = [
+    ((1, False, 0, False, {}), [0, 1]),
+    ((48_000, False, 0, False, {}), [0, 24000, 48000]),
+    ((120_000, False, 0, False, {}), [0, 40000, 80000, 120000]),
+    ((130_000, False, 0, False, {}), [0, 16250, 48750, 81250, 113750, 130000]),
+    ((375_000, False, 0, False, {}), [0, 37500, 112500, 187500, 262500, 337500, 375000]),
+    ((375_000, False, 0, True, {}), [0, 37500, 112500, 187500, 262500, 337500, 365625, 375000]),
+    ((3_000_000, False, 0, False, {}), [0, 250000, 750000, 1250000, 1750000, 2250000, 2750000, 3000000]),
+    ((3_000_000, False, 0, True, {}), [0, 250000, 750000, 1250000, 1750000, 2250000, 2750000, 2937500, 3000000]),
+    ((600_000, True, 0, False, {}), [0, 75000, 375000, 600000]),
+    ((100_000, True, 0, False, {}), [0, 100000]),
+    ((7_500, False, 0, False, {"ADH_CHUNK": "1500"}), [0, 750, 2250, 3750, 5250, 6750, 7500]),
+    # a row bound below the picked chunk (the ion-mobility scratch fit): the parts are recomputed
+    ((600_000, True, 70_000, False, {}),
+     [0, 33333, 100000, 166667, 233334, 300001, 366668, 433335, 500002, 566669, 600000]),
+    ((600_000, True, 250_000, False, {}), [0, 50000, 250000, 450000, 600000]),
+    ((100_000, True, 64, False, {}), [0, 32] + list(range(96, 100_000, 64)) + [100_000]),
+    ((375_000, False, 0, False, {"ADH_FIRST_CHUNK_DIV": "1"}), [0, 75000, 150000, 225000, 300000, 375000]),
+    ((375_000, False, 0, False, {"ADH_FIRST_CHUNK_DIV": "7"}), [0, 10714, 85714, 160714, 235714, 310714, 375000]),
+    ((3_000_000, False, 0, True, {"ADH_LAST_CHUNK_DIV": "1"}),
+     [0, 250000, 750000, 1250000, 1750000, 2250000, 2750000, 3000000]),
+    ((3_000_000, False, 0, True, {"ADH_LAST_CHUNK_DIV": "2"}),
+     [0, 250000, 750000, 1250000, 1750000, 2250000, 2750000, 2875000, 3000000]),
+    ((10_000, False, 0, True, {"ADH_CHUNK_PARTS": "3", "ADH_CHUNK_MIN": "2000"}), [0, 3334, 6668, 9167, 10000]),
+    ((40_961, False, 0, False, {}), [0, 20481, 40961]),
+    ((163_841, False, 0, True, {}), [0, 16384, 49153, 81922, 114691, 147460, 159746, 163841]),
+    ((2_097_152, False, 0, True, {}), [0, 262144, 786432, 1310720, 1835008, 2031616, 2097152]),
+    ((2_097_151, False, 0, True, {}), [0, 209715, 629146, 1048577, 1468008, 1887439, 2044723, 2097151]),
+]
+
+
+@pytest.mark.parametrize("args, expected", _CHUNK_CUTS, ids=[str(i) for i in range(len(_CHUNK_CUTS))])
+def test_chunk_cuts_are_the_pipelines_schedule(monkeypatch, args, expected):
+    """The chunk boundaries of a host -> host scoring call (adh_chunk_cuts, no GPU): the byte-identity tests of the
+    pipeline pass whatever the cuts are, so the schedule itself is pinned here - short first chunk, equal chunks, the
+    packed mode's short last chunk, the caller's bound on a chunk's rows, the ADH_CHUNK* switches."""
+    from alphadia_amd import runtime
+
+    n, ion_mobility, max_rows, packed, env = args
+    for name in _CHUNK_ENV:
+        monkeypatch.delenv(name, raising=False)
+    for name, value in env.items():
+        monkeypatch.setenv(name, value)
+    cuts = runtime.chunk_cuts(n, ion_mobility=ion_mobility, max_rows=max_rows, packed=packed)
+    assert cuts[0] == 0 and cuts[-1] == n and all(b > a for a, b in zip(cuts, cuts[1:]))
+    if max_rows:
+        assert max(b - a for a, b in zip(cuts, cuts[1:])) <= max_rows
+    if packed and len(cuts) >= 5 and env.get("ADH_LAST_CHUNK_DIV") != "1":
+        # the short last chunk: the last quarter (ADH_LAST_CHUNK_DIV-th part) of what the last chunk would have been
+        whole = n - cuts[-3]
+        assert n - cuts[-2] == whole // int(env.get("ADH_LAST_CHUNK_DIV", 4))
+    assert cuts == expected
+
+
+def test_chunk_cuts_report_the_count_they_need():
+    """adh_chunk_cuts with too short an array: an error, and the count the caller needs."""
+    import ctypes as C
+
+    from alphadia_amd import runtime
+
+    fn = runtime.lib.adh_chunk_cuts
+    fn.argtypes = [C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64)]
+    few, count = (C.c_int64 * 2)(-1, -1), C.c_int64(0)
+    assert fn(375_000, 0, 0, 0, few, 2, C.byref(count)) == -1  # ADH_ERR_INVALID_ARGUMENT
+    assert count.value == len(runtime.chunk_cuts(375_000)) and list(few) == [-1, -1]
+    assert fn(0, 0, 0, 0, few, 2, C.byref(count)) == -1

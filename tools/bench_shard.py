@@ -114,7 +114,7 @@ def shard_leg(ctx, soa_all: dict, cfgj, ms_per_step: float | None = None, ways: 
         "shard_ms": [round(s["ms"], 3) for s in contended],
         "d2h_bytes": max(s["d2h_bytes"] for s in contended),
         "policy": "below 6 host threads per rank the device writes the id / library columns and the link carries all "
-                  "646 bytes per candidate (host_rebuild_pays, adh_score_host.hip)",
+                  "646 bytes per candidate (host_rebuild_pays, adh_copyout.hip)",
         "max_shard_ms_if_the_team_rebuilds": max(s["ms"] for s in contended_rb),
     }
     rec["all_gather"] = {
@@ -139,7 +139,7 @@ def sweep(ctx, soa, cfgj, settings, sizes=(24_000, 48_000, 96_000, 192_000, 375_
     from alphadia_amd.distributed import slice_soa
     from alphadia_amd.scoring import pack_assembled
 
-    keys = ("ADH_CHUNK_PARTS", "ADH_CHUNK_MIN", "ADH_FIRST_CHUNK_DIV", "ADH_CHUNK", "ADH_H2D_BURST_LATE", "ADH_FUSED_STREAMS", "ADH_ANY_ORDER")
+    keys = ("ADH_CHUNK_PARTS", "ADH_CHUNK_MIN", "ADH_FIRST_CHUNK_DIV", "ADH_CHUNK", "ADH_FUSED_STREAMS", "ADH_ANY_ORDER")
     for size in sizes:
         m = min(size, len(soa["precursor_idx"]))
         sub = slice_soa(soa, 0, m)
