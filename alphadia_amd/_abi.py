@@ -664,6 +664,15 @@ RESIDENT_PROTOTYPES = {
 }
 
 
+# ... of the staging of one part of a channel-wise decoy strategy
+_f32pp = C.POINTER(C.POINTER(C.c_float))
+STAGE_PART_PROTOTYPES = {
+    "adh_mlp_stage_rows_device_part": [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, _f32pp, C.c_int32,
+                                       C.POINTER(C.c_uint8), C.c_int64, C.POINTER(C.c_int64), C.c_int64, C.c_int64,
+                                       C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
+}
+
+
 # ... and of the accumulated resident tables (the optimisation loop)
 APPEND_PROTOTYPES = {
     "adh_score_candidates_resident_append": [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)],
@@ -692,9 +701,9 @@ QUANT_PROTOTYPES = {
 
 
 def declare(lib) -> None:
-    """Argument types of the entries listed in RESIDENT_PROTOTYPES, APPEND_PROTOTYPES and QUANT_PROTOTYPES (the others
-    are called with explicit casts)."""
-    for name, argtypes in {**RESIDENT_PROTOTYPES, **APPEND_PROTOTYPES, **QUANT_PROTOTYPES}.items():
+    """Argument types of the entries listed in RESIDENT_PROTOTYPES, STAGE_PART_PROTOTYPES, APPEND_PROTOTYPES and
+    QUANT_PROTOTYPES (the others are called with explicit casts)."""
+    for name, argtypes in {**RESIDENT_PROTOTYPES, **STAGE_PART_PROTOTYPES, **APPEND_PROTOTYPES, **QUANT_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = C.c_int

@@ -6,6 +6,8 @@
 // tables adh_score_candidates left in HBM are the input:
 //   adh_mlp_stage_rows_device  fdr.py:86-105  dropna + np.concatenate([targets, decoys]) as a stable
 //                                             partition of the usable rows; X gathered on the device
+//   adh_mlp_stage_rows_device_part            the same for one part of a channel-wise decoy strategy
+//                                             (fdr_manager.py:178-223): one channel plus the decoy channel
 //   adh_mlp_fit                classifiers.py:316-433 (unchanged, trains on the staged rows)
 //   adh_mlp_predict_resident   fdr.py:133     probabilities stay in HBM
 //   adh_fdr_resident           fdr.py:134-178 q-values -> fragment competition (fragcomp.py:231-299,
@@ -36,26 +38,48 @@ __device__ __forceinline__ float column_value(const ColumnSpec &c, const float *
     return features[i * ADH_NUM_FEATURES + 2] - c.extra[-1 - s][i];
 }
 
-// usable rows (valid, no NaN in a classifier column: dropna, fdr.py:86-87), split by decoy flag
-__global__ void usable_kernel(ColumnSpec c, const uint8_t *__restrict__ valid, const float *__restrict__ features,
-                              const uint8_t *__restrict__ decoy, int64_t n, int32_t *__restrict__ flag_t,
-                              int32_t *__restrict__ flag_d) {
+// one part of a decoy strategy (fdr_manager.py:178-223): the rows of `target` and of the decoy channel `decoy`
+// (-1: none), labelled by the decoy column or, with by_channel, by membership of the decoy channel.  channel == nullptr:
+// every row, labelled by the decoy column (the "precursor" strategy, adh_mlp_stage_rows_device)
+struct PartSpec {
+    const int64_t *channel;
+    int64_t target, decoy;
+    int32_t by_channel;
+};
+
+__device__ __forceinline__ bool part_member(const PartSpec &p, int64_t i) {
+    if (!p.channel) return true;
+    const int64_t ch = p.channel[i];
+    return ch == p.target || (p.decoy != -1 && ch == p.decoy);
+}
+
+// the decoy byte the classifier and the q-values see for row i
+__device__ __forceinline__ uint8_t part_label(const PartSpec &p, const uint8_t *__restrict__ decoy, int64_t i) {
+    if (p.channel && p.by_channel) return (uint8_t)(p.decoy != -1 && p.channel[i] == p.decoy);
+    return decoy[i];
+}
+
+// usable rows of the part (valid, no NaN in a classifier column: dropna, fdr.py:86-87), split by label
+__global__ void usable_kernel(ColumnSpec c, PartSpec part, const uint8_t *__restrict__ valid,
+                              const float *__restrict__ features, const uint8_t *__restrict__ decoy, int64_t n,
+                              int32_t *__restrict__ flag_t, int32_t *__restrict__ flag_d) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    bool ok = valid[i] != 0;
+    bool ok = part_member(part, i) && valid[i] != 0;
     for (int j = 0; ok && j < c.d; ++j) {
         const float v = column_value(c, features, i, j);
         ok = !(v != v);
     }
-    flag_t[i] = ok && !decoy[i];
-    flag_d[i] = ok && decoy[i];
+    const uint8_t label = part_label(part, decoy, i);
+    flag_t[i] = ok && !label;
+    flag_d[i] = ok && label;
 }
 
-__global__ void stage_kernel(ColumnSpec c, const float *__restrict__ features, const uint8_t *__restrict__ decoy,
-                             const int32_t *__restrict__ flag_t, const int32_t *__restrict__ flag_d,
-                             const int32_t *__restrict__ pos_t, const int32_t *__restrict__ pos_d, int64_t n,
-                             float *__restrict__ X, float *__restrict__ Y, int64_t *__restrict__ rowmap,
-                             uint8_t *__restrict__ decoy_rows, int64_t *__restrict__ counts) {
+__global__ void stage_kernel(ColumnSpec c, PartSpec part, const float *__restrict__ features,
+                             const uint8_t *__restrict__ decoy, const int32_t *__restrict__ flag_t,
+                             const int32_t *__restrict__ flag_d, const int32_t *__restrict__ pos_t,
+                             const int32_t *__restrict__ pos_d, int64_t n, float *__restrict__ X, float *__restrict__ Y,
+                             int64_t *__restrict__ rowmap, uint8_t *__restrict__ decoy_rows, int64_t *__restrict__ counts) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int64_t n_t = (int64_t)pos_t[n - 1] + flag_t[n - 1];
@@ -68,9 +92,10 @@ __global__ void stage_kernel(ColumnSpec c, const float *__restrict__ features, c
     else if (flag_d[i]) p = n_t + pos_d[i];
     else return;
     for (int j = 0; j < c.d; ++j) X[p * c.d + j] = column_value(c, features, i, j);
-    Y[p] = decoy[i] ? 1.0f : 0.0f;
+    const uint8_t label = part_label(part, decoy, i);
+    Y[p] = label ? 1.0f : 0.0f;
     rowmap[p] = i;
-    decoy_rows[p] = decoy[i];
+    decoy_rows[p] = label;
 }
 
 __global__ void proba_to_score_kernel(const float *__restrict__ proba, int out_dim, int64_t n, double *__restrict__ score) {
@@ -169,10 +194,12 @@ int compact_ids(adh_handle *h, Scratch &s, const int64_t *ids, const uint8_t *fl
 
 }  // namespace fdrdev
 
-int adh_mlp_stage_rows_device(adh_mlp_t *m, const int32_t *src_cols, int32_t d, const float *const *extra_cols,
-                              int32_t n_extra, const uint8_t *decoy, int64_t n_rows, int64_t *n_targets,
-                              int64_t *n_decoys) {
-    using namespace fdrdev;
+namespace fdrdev {
+
+// adh_mlp_stage_rows_device (channel == nullptr) and adh_mlp_stage_rows_device_part
+int stage_rows(adh_mlp_t *m, const int32_t *src_cols, int32_t d, const float *const *extra_cols, int32_t n_extra,
+               const uint8_t *decoy, int64_t n_rows, const int64_t *channel, int64_t target_channel, int64_t decoy_channel,
+               int32_t label_by_channel, int64_t *n_targets, int64_t *n_decoys) {
     if (!m || !src_cols || !decoy || !n_targets || !n_decoys) return fail(ADH_ERR_INVALID_ARGUMENT, "NULL argument");
     adh_handle *h = m->h;
     if (h->last_tables < 0 || h->last_rows != n_rows)
@@ -216,13 +243,21 @@ int adh_mlp_stage_rows_device(adh_mlp_t *m, const int32_t *src_cols, int32_t d, 
     HIP_TRY(s.alloc(&pos_d, n));
     HIP_TRY(s.alloc(&d_counts, 2));
     HIP_TRY(hipMemcpyAsync(d_decoy_all, decoy, n, hipMemcpyHostToDevice, st));
+    PartSpec part = {nullptr, target_channel, decoy_channel, label_by_channel};
+    if (channel) {  // the channel column, uploaded once per call like `decoy`
+        int64_t *d_channel = nullptr;
+        HIP_TRY(s.alloc(&d_channel, n));
+        HIP_TRY(hipMemcpyAsync(d_channel, channel, n * 8, hipMemcpyHostToDevice, st));
+        part.channel = d_channel;
+    }
     for (int e = 0; e < n_extra; ++e) {
         float *d_e = nullptr;
         HIP_TRY(s.alloc(&d_e, n));
         HIP_TRY(hipMemcpyAsync(d_e, extra_cols[e], n * 4, hipMemcpyHostToDevice, st));
         spec.extra[e] = d_e;
     }
-    hipLaunchKernelGGL(usable_kernel, grid_for(n), dim3(256), 0, st, spec, tab.valid, tab.features, d_decoy_all, n, flag_t, flag_d);
+    hipLaunchKernelGGL(usable_kernel, grid_for(n), dim3(256), 0, st, spec, part, tab.valid, tab.features, d_decoy_all, n, flag_t,
+                       flag_d);
     {
         size_t bytes = 0;
         HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, flag_t, pos_t, (int)n, st));
@@ -237,8 +272,8 @@ int adh_mlp_stage_rows_device(adh_mlp_t *m, const int32_t *src_cols, int32_t d, 
     HIP_TRY(hipMalloc((void **)&m->d_Y, std::max<size_t>((size_t)n * 4, 4)));
     HIP_TRY(hipMalloc((void **)&m->d_rowmap, std::max<size_t>((size_t)n * 8, 8)));
     HIP_TRY(hipMalloc((void **)&m->d_decoy, std::max<size_t>((size_t)n, 1)));
-    hipLaunchKernelGGL(stage_kernel, grid_for(n), dim3(256), 0, st, spec, tab.features, d_decoy_all, flag_t, flag_d, pos_t,
-                       pos_d, n, m->d_X, m->d_Y, m->d_rowmap, m->d_decoy, d_counts);
+    hipLaunchKernelGGL(stage_kernel, grid_for(n), dim3(256), 0, st, spec, part, tab.features, d_decoy_all, flag_t, flag_d,
+                       pos_t, pos_d, n, m->d_X, m->d_Y, m->d_rowmap, m->d_decoy, d_counts);
     HIP_TRY(hipGetLastError());
     int64_t counts[2] = {0, 0};
     HIP_TRY(hipMemcpyAsync(counts, d_counts, 16, hipMemcpyDeviceToHost, st));
@@ -249,6 +284,27 @@ int adh_mlp_stage_rows_device(adh_mlp_t *m, const int32_t *src_cols, int32_t d, 
     m->n_rows = counts[0] + counts[1];
     m->has_y = true;
     return ADH_OK;
+}
+
+}  // namespace fdrdev
+
+int adh_mlp_stage_rows_device(adh_mlp_t *m, const int32_t *src_cols, int32_t d, const float *const *extra_cols,
+                              int32_t n_extra, const uint8_t *decoy, int64_t n_rows, int64_t *n_targets,
+                              int64_t *n_decoys) {
+    return fdrdev::stage_rows(m, src_cols, d, extra_cols, n_extra, decoy, n_rows, nullptr, -1, -1, 0, n_targets, n_decoys);
+}
+
+// One part of a channel-wise decoy strategy (alphadia/workflow/managers/fdr_manager.py:178-223): the slicing
+// features_df[features_df["channel"].isin([channel, decoy_channel])] and the target / decoy split of that slice - by the
+// decoy column ("precursor_channel_wise", :189-190) or by the channel ("channel", :213-214) - made in the staging
+// kernels, so the classifier sees the rows of one part without the tables leaving HBM.
+int adh_mlp_stage_rows_device_part(adh_mlp_t *m, const int32_t *src_cols, int32_t d, const float *const *extra_cols,
+                                   int32_t n_extra, const uint8_t *decoy, int64_t n_rows, const int64_t *channel,
+                                   int64_t target_channel, int64_t decoy_channel, int32_t label_by_channel,
+                                   int64_t *n_targets, int64_t *n_decoys) {
+    if (!channel) return fail(ADH_ERR_INVALID_ARGUMENT, "NULL argument");
+    return fdrdev::stage_rows(m, src_cols, d, extra_cols, n_extra, decoy, n_rows, channel, target_channel, decoy_channel,
+                              label_by_channel != 0, n_targets, n_decoys);
 }
 
 int adh_mlp_staged_rows(adh_mlp_t *m, int64_t *rows_out, int64_t capacity) {

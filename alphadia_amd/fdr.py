@@ -320,17 +320,19 @@ class HipBinaryClassifier:
         finally:
             mlp.close()
 
-    def fit_resident(self, src_cols, decoy, extra_cols=(), subset=None):
+    def fit_resident(self, src_cols, decoy, extra_cols=(), subset=None, channel=None, part=None):
         """Train on rows staged straight from the scoring tables in HBM (``adh_mlp_stage_rows_device``).
         ``subset(n_staged) -> rows`` picks the staged rows the classifier may see (perform_fdr's 80 %
-        split).  Returns ``(mlp, table_rows)``: the live device network (the caller closes it) and the
+        split).  ``part = (target_channel, decoy_channel, label_by_channel)`` restricts the staging to one part of a
+        channel-wise decoy strategy (``DeviceMlp.stage_rows_device``; ``channel`` is then the channel of every table
+        row).  Returns ``(mlp, table_rows)``: the live device network (the caller closes it) and the
         candidate row of every staged row."""
         self._prepare(len(src_cols))
         mlp = self._device_mlp()
         try:
-            mlp.stage_rows_device(src_cols, decoy, extra_cols)
+            mlp.stage_rows_device(src_cols, decoy, extra_cols, channel=channel, part=part)
             table_rows = mlp.staged_rows()
-            y_all = (np.asarray(decoy)[table_rows] != 0).astype(np.float64)
+            y_all = part_labels(decoy, channel, part)[table_rows]
             try:
                 base = None if subset is None else np.asarray(subset(len(table_rows)), dtype=np.int64)
             except TooFewPSMError as exc:
@@ -363,6 +365,43 @@ class HipBinaryClassifier:
 
     def predict_proba(self, x: np.ndarray) -> np.ndarray:
         return self._forward(x)
+
+
+def part_labels(decoy, channel=None, part=None) -> np.ndarray:
+    """The class-1 target of every table row as the staging kernels label it: the decoy column, or - in a part
+    ``(target_channel, decoy_channel, label_by_channel)`` with ``label_by_channel`` - membership of the decoy channel
+    (fdr_manager.py:213-214)."""
+    if part is not None and part[2]:
+        return (np.asarray(channel).astype(np.int64) == int(part[1])).astype(np.float64) if int(part[1]) != -1 \
+            else np.zeros(len(channel), np.float64)
+    return (np.asarray(decoy) != 0).astype(np.float64)
+
+
+def part_rows(valid, usable, decoy, channel, part=None) -> tuple[np.ndarray, int, int]:
+    """NumPy restatement of ``adh_mlp_stage_rows_device`` / ``adh_mlp_stage_rows_device_part`` (which rows, which
+    labels, which order), for tests: ``(staged table rows, n_targets, n_decoys)``.  ``valid`` is the table's valid
+    flag, ``usable`` is False where a classifier column is NaN; both have one entry per table row."""
+    channel = np.asarray(channel).astype(np.int64)
+    member = np.ones(len(channel), bool)
+    if part is not None:
+        member = (channel == int(part[0])) | ((channel == int(part[1])) & (int(part[1]) != -1))
+    ok = member & np.asarray(valid, bool) & np.asarray(usable, bool)
+    label = part_labels(decoy, channel, part) != 0
+    targets, decoys = np.flatnonzero(ok & ~label), np.flatnonzero(ok & label)
+    return np.concatenate([targets, decoys]).astype(np.int64), len(targets), len(decoys)
+
+
+def strategy_parts(decoy_strategy: str, channel, valid, decoy_channel: int = -1) -> list[tuple[int, int, int]]:
+    """The parts ``(target_channel, decoy_channel, label_by_channel)`` of a channel-wise decoy strategy over table rows
+    with channels ``channel`` of which ``valid`` are rows of the features frame: "precursor_channel_wise" - one per
+    channel in order of first appearance (``features_df["channel"].unique()``, fdr_manager.py:179), no decoy channel;
+    "channel" - one per channel other than the decoy channel, ascending."""
+    if decoy_strategy not in ("precursor_channel_wise", "channel"):
+        raise ValueError(f"Invalid decoy_strategy: {decoy_strategy}")
+    present = pd.unique(np.asarray(channel)[np.asarray(valid, bool)])
+    if decoy_strategy == "precursor_channel_wise":
+        return [(int(c), -1, 0) for c in present]
+    return [(int(c), int(decoy_channel), 1) for c in sorted(set(present.tolist()) - {decoy_channel})]
 
 
 # --------------------------------------------------------------------------------------------
@@ -469,7 +508,7 @@ def perform_fdr(classifier, available_columns: list[str], df_target: pd.DataFram
 def perform_fdr_resident(classifier, available_columns: list[str], candidates: pd.DataFrame, *, rt_column: str = "rt_library",
                          competitive: bool = False, group_channels: bool = True, dia_cycle: np.ndarray | None = None,
                          fdr_heuristic: float = 0.1, random_state: int | None = None,
-                         device: int | None = None) -> pd.DataFrame:
+                         device: int | None = None, part: tuple | None = None) -> pd.DataFrame:
     """:func:`perform_fdr` for tables that are still in HBM.
 
     ``candidates`` has ONE ROW PER ROW of the device tables of the last scoring call (the assembled
@@ -478,7 +517,12 @@ def perform_fdr_resident(classifier, available_columns: list[str], candidates: p
     rows are staged for the classifier, scored, ranked, put through fragment competition (fragment
     m/z from the fragment table in HBM) and reduced to the best row per group on the device; what
     comes back is the surviving PSMs with ``proba`` and ``qval`` - the frame perform_fdr returns,
-    restricted to the identifying columns."""
+    restricted to the identifying columns.
+
+    ``part = (target_channel, decoy_channel, label_by_channel)`` runs the stage on one part of a channel-wise decoy
+    strategy (fdr_manager.py:178-223): the rows of the two channels, split into targets and decoys by the decoy
+    column or, with ``label_by_channel``, by the channel.  ``_decoy`` is the label the classifier saw; ``decoy``
+    stays the table's column."""
     from alphadia_amd.scoring import DEFAULT_FEATURE_COLUMNS
 
     ctx = runtime.get_context(device)
@@ -495,6 +539,8 @@ def perform_fdr_resident(classifier, available_columns: list[str], candidates: p
         else:
             raise KeyError(f"classifier column {c!r} is neither a scoring feature nor a column of `candidates`")
     decoy = candidates["decoy"].to_numpy()
+    channel = None if part is None else candidates["channel"].to_numpy()
+    labels = part_labels(decoy, channel, part) if part is not None and part[2] else decoy.astype(np.float64)
 
     def subset(n_staged):
         return train_test_indices(n_staged, 0.2, random_state)[0]
@@ -503,13 +549,16 @@ def perform_fdr_resident(classifier, available_columns: list[str], candidates: p
     if getattr(classifier, "device", device) is None:
         classifier.device = device
     try:
-        mlp, table_rows = classifier.fit_resident(src_cols, decoy, extras, subset=subset)
+        if part is None:
+            mlp, table_rows = classifier.fit_resident(src_cols, decoy, extras, subset=subset)
+        else:
+            mlp, table_rows = classifier.fit_resident(src_cols, decoy, extras, subset=subset, channel=channel, part=part)
     except TooFewPSMError as exc:
         # fdr.py:125-137: too few PSMs for a train / test split -> every usable PSM with qval = proba = 1
         logger.warning("Too few PSMs for FDR classification, assigning qval=1.0 and proba=1.0 to all PSMs.")
         rows = np.asarray(getattr(exc, "table_rows", np.zeros(0, np.int64)), dtype=np.int64)
         out = candidates.iloc[rows][id_columns].copy()
-        out["_decoy"] = out["decoy"].to_numpy().astype(np.float64)
+        out["_decoy"] = labels[rows]
         out["proba"] = 1.0
         out["qval"] = 1.0
         out["table_row"] = rows
@@ -527,7 +576,7 @@ def perform_fdr_resident(classifier, available_columns: list[str], candidates: p
     finally:
         mlp.close()
     out = candidates.iloc[rows][id_columns].copy()
-    out["_decoy"] = out["decoy"].to_numpy().astype(np.float64)
+    out["_decoy"] = labels[rows]
     out["proba"] = proba
     out["qval"] = qval
     out["table_row"] = rows
@@ -608,15 +657,23 @@ class HipFDRManager:
         self.classifier_store[tuple(sorted(available))].append(classifier)
         return psm_df
 
-    def fit_predict_resident(self, resident, competitive: bool, version: int = -1) -> pd.DataFrame:
-        """``fit_predict(features_df, "precursor", competitive, df_fragments, version=version)`` for candidates scored
-        with ``HipCandidateScoring.score_resident``: the feature and fragment tables stay in HBM
-        (:func:`perform_fdr_resident`).  The classifier sees the columns in the order ``fit_predict`` gives them (that
-        of the features frame), the seed is drawn from the same generator and the classifier is stored and versioned
-        the same way.  Returns the surviving PSMs in perform_fdr's output order as ids (``precursor_idx, rank,
-        elution_group_idx, channel, decoy``), ``_decoy``, ``proba``, ``qval`` and ``table_row``, the row of the PSM in
-        the device tables; ``attrs["too_few_psms"]`` marks perform_fdr's too-few-PSMs answer (every usable PSM with
-        qval = proba = 1, targets first)."""
+    def fit_predict_resident(self, resident, competitive: bool, version: int = -1, decoy_strategy: str = "precursor",
+                             decoy_channel: int = -1) -> pd.DataFrame:
+        """``fit_predict(features_df, decoy_strategy, competitive, df_fragments, decoy_channel, version)`` for candidates
+        scored with ``HipCandidateScoring.score_resident`` (or accumulated in an ``AccumulatedScores``): the feature and
+        fragment tables stay in HBM (:func:`perform_fdr_resident`).  The classifier sees the columns in the order
+        ``fit_predict`` gives them (that of the features frame), the seed is drawn from the same generator and the
+        classifier is stored and versioned the same way.  Returns the surviving PSMs in perform_fdr's output order as
+        ids (``precursor_idx, rank, elution_group_idx, channel, decoy``), ``_decoy``, ``proba``, ``qval`` and
+        ``table_row``, the row of the PSM in the device tables; ``attrs["too_few_psms"]`` marks perform_fdr's
+        too-few-PSMs answer (every usable PSM with qval = proba = 1, targets first).
+
+        The channel-wise strategies (fdr_manager.py:178-223) stage one part after the other from the same tables
+        (:func:`strategy_parts`; the channels of the *valid* rows count, as the features frame holds only those), refit
+        the same classifier with the same seed and concatenate the parts' frames in part order; a row of the decoy
+        channel comes back once per part it survived in.  ``attrs["parts"]`` lists ``(part, rows, too_few)``; a part
+        with too few PSMs answers as above (its ``_decoy`` is NaN when other parts were classified, as in the host
+        manager's concatenation) and ``attrs["too_few_psms"]`` is set when every part did."""
         wanted = set(self.feature_columns)
         available = [c for c in resident.feature_columns() if c in wanted]
         if not available:
@@ -627,6 +684,21 @@ class HipFDRManager:
         # one row per table row: the ids, and the classifier columns that are not kernel features (delta_rt is
         # rt_observed minus the library rt, formed on the device)
         meta = resident.metadata.copy(deep=False)
+        by_decoy_column = decoy_strategy in ("precursor", "precursor_channel_wise")
+        if by_decoy_column and "decoy" not in meta.columns:
+            raise ValueError("Column 'decoy' not found in features_df")
+        valid = None
+        if decoy_strategy in ("precursor_channel_wise", "channel"):
+            if "channel" not in meta.columns:
+                raise ValueError("Column 'channel' not found in features_df")
+            valid = resident.valid()
+        if decoy_strategy == "channel":
+            if decoy_channel == -1:
+                raise ValueError("decoy_channel must be set if decoy_type is channel")
+            if decoy_channel not in meta["channel"].to_numpy()[valid]:
+                raise ValueError(f"decoy_channel {decoy_channel} not found in features_df")
+        if by_decoy_column:
+            decoy_channel = -1
         for c in available:
             if c in DEFAULT_FEATURE_COLUMNS or c in meta.columns:
                 continue
@@ -641,8 +713,26 @@ class HipFDRManager:
         if cycle is not None and cycle.shape[2] > MAX_DIA_CYCLE_SHAPE:
             cycle = None
         device = self._device if self._device is not None else resident.device
-        psm_df = perform_fdr_resident(classifier, available, meta, rt_column=rt_column, competitive=competitive,
-                                      group_channels=True, dia_cycle=cycle, random_state=seed, device=device)
+        common = dict(rt_column=rt_column, competitive=competitive, random_state=seed, device=device)
+        if decoy_strategy == "precursor":
+            psm_df = perform_fdr_resident(classifier, available, meta, group_channels=True, dia_cycle=cycle, **common)
+        else:
+            parts = strategy_parts(decoy_strategy, meta["channel"].to_numpy(), valid, decoy_channel)
+            if decoy_strategy == "channel":
+                cycle = None  # (fdr_manager.py:210-219 hands perform_fdr neither fragments nor a cycle)
+            frames = [perform_fdr_resident(classifier, available, meta, group_channels=decoy_strategy != "channel",
+                                           dia_cycle=cycle, part=part, **common) for part in parts]
+            too_few = [bool(f.attrs.get("too_few_psms", False)) for f in frames]
+            if any(too_few) and not all(too_few):
+                for f, few in zip(frames, too_few, strict=True):
+                    if few:
+                        f["_decoy"] = np.nan
+            psm_df = pd.concat(frames)
+            if decoy_strategy == "channel":
+                psm_df.loc[psm_df["channel"] == decoy_channel, "decoy"] = 1
+            psm_df.attrs["parts"] = [(part, len(f), few) for part, f, few in zip(parts, frames, too_few, strict=True)]
+            if parts and all(too_few):
+                psm_df.attrs["too_few_psms"] = True
         psm_df.attrs["fragment_competition"] = cycle is not None
 
         self._current_version += 1

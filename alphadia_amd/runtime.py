@@ -56,6 +56,7 @@ EXPORTED_SYMBOLS = [
     "adh_zero_device_tables",
     "adh_debug_get_dense",
     "adh_mlp_stage_rows_device",
+    "adh_mlp_stage_rows_device_part",
     "adh_mlp_staged_rows",
     "adh_mlp_predict_resident",
     "adh_fdr_resident",
@@ -1146,9 +1147,13 @@ class DeviceMlp:
                                       self._p(ya, C.c_float) if ya is not None else None), "adh_mlp_stage_rows")
         self.n_rows = xa.shape[0]
 
-    def stage_rows_device(self, src_cols, decoy, extra_cols=()):
+    def stage_rows_device(self, src_cols, decoy, extra_cols=(), channel=None, part=None):
         """Stage the usable rows of the device tables of the last ``score_host`` call (targets first,
-        then decoys); returns ``(n_targets, n_decoys)``.  See ``adh_mlp_stage_rows_device``."""
+        then decoys); returns ``(n_targets, n_decoys)``.  See ``adh_mlp_stage_rows_device``.
+
+        ``part = (target_channel, decoy_channel, label_by_channel)`` stages one part of a channel-wise decoy
+        strategy instead (``adh_mlp_stage_rows_device_part``): the rows whose ``channel`` is the target or the decoy
+        channel (-1: none), labelled by the decoy channel if ``label_by_channel`` and by ``decoy`` otherwise."""
         sc = _abi.as_c(src_cols, np.int32)
         de = _abi.as_c(np.asarray(decoy) != 0, np.uint8)
         extras = [_abi.as_c(e, np.float32) for e in extra_cols]
@@ -1156,9 +1161,23 @@ class DeviceMlp:
             raise ValueError("extra columns must have one value per candidate row")
         arr = (C.POINTER(C.c_float) * max(len(extras), 1))(*[self._p(e, C.c_float) for e in extras])
         nt, nd = C.c_int64(0), C.c_int64(0)
-        _check(lib.adh_mlp_stage_rows_device(self._m, self._p(sc, C.c_int32), C.c_int32(sc.shape[0]), arr,
-                                             C.c_int32(len(extras)), self._p(de, C.c_uint8), C.c_int64(de.shape[0]),
-                                             C.byref(nt), C.byref(nd)), "adh_mlp_stage_rows_device")
+        if part is None:
+            _check(lib.adh_mlp_stage_rows_device(self._m, self._p(sc, C.c_int32), C.c_int32(sc.shape[0]), arr,
+                                                 C.c_int32(len(extras)), self._p(de, C.c_uint8), C.c_int64(de.shape[0]),
+                                                 C.byref(nt), C.byref(nd)), "adh_mlp_stage_rows_device")
+        else:
+            if channel is None:
+                raise ValueError("a part needs the channel column")
+            ch = _abi.as_c(channel, np.int64)
+            if ch.shape != de.shape:
+                raise HipBackendError(f"channel holds {ch.shape[0] if ch.ndim == 1 else ch.shape} values, decoy "
+                                      f"{de.shape[0]}: one per row of the device tables is needed")
+            target, decoy_channel, by_channel = part
+            _check(lib.adh_mlp_stage_rows_device_part(
+                self._m, self._p(sc, C.c_int32), C.c_int32(sc.shape[0]), arr, C.c_int32(len(extras)),
+                self._p(de, C.c_uint8), C.c_int64(de.shape[0]), self._p(ch, C.c_int64), C.c_int64(int(target)),
+                C.c_int64(int(decoy_channel)), C.c_int32(int(bool(by_channel))), C.byref(nt), C.byref(nd)),
+                "adh_mlp_stage_rows_device_part")
         self.n_rows = int(nt.value) + int(nd.value)
         return int(nt.value), int(nd.value)
 

@@ -1001,6 +1001,14 @@ class ResidentScores:
         if self._scorer._ctx.tables_serial != self._serial:
             raise HipBackendError("the device tables of this scoring call were replaced by a later one")
 
+    def valid(self, start: int = 0, stop: int | None = None) -> np.ndarray:
+        """The valid flags of table rows [start, stop) (default: all; one byte per row crosses PCIe)."""
+        self._check_current()
+        stop = self.n_table if stop is None else int(stop)
+        if not 0 <= start <= stop <= self.n_table:
+            raise ValueError(f"rows [{start}, {stop}) outside the {self.n_table} rows of the device tables")
+        return self._scorer._ctx.table_rows_to_host("valid", start, stop).astype(bool)
+
     def feature_columns(self) -> list[str]:
         """The columns of the features frame, in its order (the frame of no rows; nothing is copied)."""
         if self._columns is None:
@@ -1292,11 +1300,12 @@ def multiplex_candidates(
 
 def requantify_multiplexed(dia_data, psm_df: pd.DataFrame, precursors_flat: pd.DataFrame, fragments_flat: pd.DataFrame,
                            channels: list[int], reference_channel: int, experimental_xic: bool, column_names: dict,
-                           device: int | None = None):
+                           device: int | None = None, resident: bool = False):
     """The scoring half of multiplex requantification
     (multiplexing_requantification_handler.py:95-140): best candidate of every elution group copied
     to all ``channels``, the channel copies scored as one score group gated on the reference
-    channel.  Returns ``(features_df, fragments_df)``; the q-values are the FDR manager's business."""
+    channel.  Returns ``(features_df, fragments_df)``; the q-values are the FDR manager's business.
+    With ``resident`` the tables stay in HBM and the ``ResidentScores`` of the scoring call is returned instead."""
     cols = ["elution_group_idx", "precursor_idx", "rank", "scan_start", "scan_stop", "scan_center", "frame_start",
             "frame_stop", "frame_center", "proba"]
     multiplexed = multiplex_candidates(psm_df[cols], precursors_flat, channels=channels)
@@ -1306,4 +1315,4 @@ def requantify_multiplexed(dia_data, psm_df: pd.DataFrame, precursors_flat: pd.D
                        experimental_xic=bool(experimental_xic)))
     scoring = HipCandidateScoring(dia_data=dia_data, precursors_flat=precursors_flat, fragments_flat=fragments_flat,
                                   config=config, device=device, **column_names)
-    return scoring(multiplexed)
+    return scoring.score_resident(multiplexed) if resident else scoring(multiplexed)

@@ -687,6 +687,20 @@ int adh_mlp_time_ms(adh_mlp_t *mlp, double *fit_ms, double *predict_ms);
 int adh_mlp_stage_rows_device(adh_mlp_t *mlp, const int32_t *src_cols, int32_t d, const float *const *extra_cols,
                               int32_t n_extra, const uint8_t *decoy, int64_t n_rows, int64_t *n_targets,
                               int64_t *n_decoys);
+/*
+ * The same for one part of a channel-wise decoy strategy of FDRManager.fit_predict
+ * (alphadia/workflow/managers/fdr_manager.py:178-223).  `channel` is a host int64[n_rows]; row i takes part iff
+ * channel[i] == target_channel || channel[i] == decoy_channel (a decoy_channel of -1 matches nothing) and it is usable
+ * as above (the NaN check sees the part's rows only).  Its label is channel[i] == decoy_channel when label_by_channel
+ * is set ("channel", :213-214) and decoy[i] != 0 otherwise ("precursor_channel_wise", :189-190).  Staged order, X, Y,
+ * row map and decoy bytes are those of adh_mlp_stage_rows_device for that label vector; the entries after staging
+ * (adh_mlp_fit, adh_mlp_predict_resident, adh_fdr_resident) do not know the difference, and a part may be staged
+ * after adh_fdr_resident ran on the same tables.
+ */
+int adh_mlp_stage_rows_device_part(adh_mlp_t *mlp, const int32_t *src_cols, int32_t d, const float *const *extra_cols,
+                                   int32_t n_extra, const uint8_t *decoy, int64_t n_rows, const int64_t *channel,
+                                   int64_t target_channel, int64_t decoy_channel, int32_t label_by_channel,
+                                   int64_t *n_targets, int64_t *n_decoys);
 /* candidate row of every staged row (8 bytes per row; the host needs it to label its metrics) */
 int adh_mlp_staged_rows(adh_mlp_t *mlp, int64_t *rows_out, int64_t capacity);
 /* network.eval() forward of all staged rows; the probabilities stay in HBM */
