@@ -308,6 +308,29 @@ def pack_fragments(mz_library, mz, intensity, type_, loss_type, charge, number, 
     return Marshalled(s, arrs)
 
 
+# One staged fragment record (LibRec, csrc/adh_device.h) as adh_staged_fragments_read returns it.  Byte offsets:
+# mz_library 0, mz 4, intensity 8; type 12, loss_type 13, charge 14, number 15, position 16, cardinality 17; the
+# rest (18 .. 31) is padding and stays zero.
+LIB_RECORD_DTYPE = np.dtype({
+    "names": ["mz_library", "mz", "intensity", "type", "loss_type", "charge", "number", "position", "cardinality", "pad"],
+    "formats": [np.float32, np.float32, np.float32, np.uint8, np.uint8, np.uint8, np.uint8, np.uint8, np.uint8,
+                (np.uint8, 14)],
+    "offsets": [0, 4, 8, 12, 13, 14, 15, 16, 17, 18],
+    "itemsize": 32,
+})
+
+
+def pack_fragments_calibrated(mz_library, intensity, type_, loss_type, charge, number, position, cardinality):
+    """``adh_fragments_t`` without an m/z column (NULL): what ``adh_stage_fragments_columns`` takes with a model."""
+    arrs = [as_c(mz_library, np.float32), as_c(intensity, np.float32)]
+    arrs += [as_c(a, np.uint8) for a in (type_, loss_type, charge, number, position, cardinality)]
+    n = arrs[0].shape[0]
+    if any(a.shape != (n,) for a in arrs):
+        raise ValueError("fragment columns differ in length")
+    s = Fragments(n, _ptr(arrs[0], C.c_float), None, _ptr(arrs[1], C.c_float), *[_ptr(a, C.c_uint8) for a in arrs[2:]])
+    return Marshalled(s, arrs)
+
+
 def pack_candidates(
     precursor_idx,
     rank,
@@ -700,10 +723,19 @@ QUANT_PROTOTYPES = {
 }
 
 
+# ... and of the library staged from its columns and calibrated in HBM (adh_stage_lib.hip, adh_calibration.hip)
+STAGE_LIB_PROTOTYPES = {
+    "adh_calibrate_staged_fragments": [C.c_void_p, C.POINTER(LoessModel), C.POINTER(C.c_double)],
+    "adh_stage_fragments_columns": [C.c_void_p, C.POINTER(Fragments), C.POINTER(LoessModel), C.POINTER(C.c_double)],
+    "adh_staged_fragments_read": [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64],
+}
+
+
 def declare(lib) -> None:
-    """Argument types of the entries listed in RESIDENT_PROTOTYPES, STAGE_PART_PROTOTYPES, APPEND_PROTOTYPES and
-    QUANT_PROTOTYPES (the others are called with explicit casts)."""
-    for name, argtypes in {**RESIDENT_PROTOTYPES, **STAGE_PART_PROTOTYPES, **APPEND_PROTOTYPES, **QUANT_PROTOTYPES}.items():
+    """Argument types of the entries listed in RESIDENT_PROTOTYPES, STAGE_PART_PROTOTYPES, APPEND_PROTOTYPES,
+    QUANT_PROTOTYPES and STAGE_LIB_PROTOTYPES (the others are called with explicit casts)."""
+    for name, argtypes in {**RESIDENT_PROTOTYPES, **STAGE_PART_PROTOTYPES, **APPEND_PROTOTYPES, **QUANT_PROTOTYPES,
+                           **STAGE_LIB_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = C.c_int

@@ -7,6 +7,7 @@ Drop-in for the reference's ``CalibrationManager`` (alphadia/workflow/managers/c
 degree reduction, the 0.1 / 99.9 percentile trim, uniform or density intervals, the design matrix in the input's
 dtype).  The prediction touches every library row - the batch library at every optimisation step, the whole library
 once the loop ends - and runs in a HIP kernel (``adh_calibration_predict``, csrc/adh_calibration.hip).
+``HipCalibrationManager.predict_staged`` also leaves the calibrated fragment m/z in the library staged in HBM.
 
 Only ``LOESSRegression`` models are supported, the only model the default configuration names; any other model name
 raises ``NotImplementedError`` when the estimators are set up.  Plots are not drawn.
@@ -415,6 +416,46 @@ class HipCalibrationManager:
         for estimator in self.estimator_groups[group_name].values():
             self.reporter.log_string(f"Predicting estimator '{estimator.name}' in calibration group '{group_name}' ..")
             estimator.predict(df, inplace=True)
+
+    def predict_staged(self, fragment_df: pd.DataFrame, group_name: str = "fragment", device: int | None = None,
+                       only_if_staged: bool = False) -> str:
+        """``predict(fragment_df, group_name)`` for the fragment m/z, with the calibrated column also put where the
+        next selection or scoring constructor looks for it: in the library staged in HBM.  Returns the path taken:
+
+        ``"skipped"``   the estimator is not fitted: as ``predict`` (a warning, nothing written, nothing staged);
+        ``"in_place"``  the library staged on the context was staged from this frame's other eight columns: its
+                        ``mz`` is rewritten in HBM (``adh_calibrate_staged_fragments``), nothing is uploaded;
+        ``"staged"``    otherwise: the library is staged from the frame's columns and calibrated while its records are
+                        packed (``adh_stage_fragments_columns``);
+        ``"host"``      otherwise, with ``only_if_staged``: plain ``predict``, nothing staged.
+
+        In every case the frame gets the ``mz_calibrated`` column ``predict`` gives it, bit for bit; after
+        ``"in_place"`` and ``"staged"`` the context has adopted ``fragment_columns(fragment_df, "mz_calibrated")``, so
+        staging those columns again is skipped."""
+        from alphadia_amd import runtime
+        from alphadia_amd.scoring import fragment_columns
+
+        estimator = self.get_estimator(group_name, "mz")
+        if estimator is None or not estimator.is_fitted:
+            self.predict(fragment_df, group_name)
+            return "skipped"
+        if not estimator._has_columns(fragment_df, estimator.input_columns):  # noqa: SLF001
+            raise ValueError(f"{estimator.name} calibration prediction: failed input validation")
+        self.reporter.log_string(f"Predicting estimator '{estimator.name}' in calibration group '{group_name}' ..")
+        source, output = estimator.input_columns[0], estimator._output_columns[0]  # noqa: SLF001
+        ctx = runtime.get_context(device)
+        columns = fragment_columns(fragment_df, source)
+        eight = columns[:1] + columns[2:]
+        if ctx.staged_from(*eight):
+            values, path = ctx.calibrate_staged_fragments(estimator.model), "in_place"
+        elif only_if_staged:
+            estimator.predict(fragment_df, inplace=True)
+            return "host"
+        else:
+            values, path = ctx.stage_fragments_calibrated(estimator.model, *eight), "staged"
+        fragment_df[output] = values  # (before the columns are adopted: the key is taken from the frame's own column)
+        ctx.adopt_fragment_columns(*fragment_columns(fragment_df, output))
+        return path
 
     # -- persistence -------------------------------------------------------
     def _state(self) -> dict:

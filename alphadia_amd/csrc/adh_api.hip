@@ -428,6 +428,7 @@ struct adh_handle {
         hipEvent_t done = nullptr, k0 = nullptr, k1 = nullptr;
     };
     CalibSlot calib[2];
+    CalibSlot lib_slots[2];  // adh_stage_fragments_columns (adh_stage_lib.hip): a chunk's columns up, its predictions back
     double calib_kernel_ms = 0.0;
 };
 
@@ -658,12 +659,14 @@ int adh_destroy(adh_handle_t *h) {
         }
         if (l.st) (void)hipStreamDestroy(l.st);
     }
-    for (adh_handle::CalibSlot &s : h->calib) {
-        if (s.host) (void)hipHostFree(s.host);
-        if (s.dev) (void)hipFree(s.dev);
-        for (hipEvent_t e : {s.done, s.k0, s.k1})
-            if (e) (void)hipEventDestroy(e);
-    }
+    for (adh_handle::CalibSlot *pair : {h->calib, h->lib_slots})
+        for (int k = 0; k < 2; ++k) {
+            adh_handle::CalibSlot &s = pair[k];
+            if (s.host) (void)hipHostFree(s.host);
+            if (s.dev) (void)hipFree(s.dev);
+            for (hipEvent_t e : {s.done, s.k0, s.k1})
+                if (e) (void)hipEventDestroy(e);
+        }
     if (h->cop_scan) (void)hipFree(h->cop_scan);
     if (h->cmp_dev) (void)hipFree(h->cmp_dev);
     if (h->cmp_scan) (void)hipFree(h->cmp_scan);
@@ -1940,6 +1943,7 @@ int adh_fragcomp_stats(adh_handle_t *h, double *kernel_ms, int64_t *pairs, int64
 #include "adh_mlp.hip"
 #include "adh_fdr_device.hip"
 #include "adh_calibration.hip"
+#include "adh_stage_lib.hip"
 #include "adh_take_rows.hip"
 #include "adh_resident_append.hip"
 #include "adh_quant.hip"

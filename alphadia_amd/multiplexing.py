@@ -39,7 +39,11 @@ class HipMultiplexingRequantificationHandler:
         mp = self._config["multiplexing"]
         if self._calibration is not None:  # calibrated columns of the unfiltered library (handler :45-50)
             self._calibration.predict(self._library.precursor_df_unfiltered, "precursor")
-            self._calibration.predict(self._library._fragment_df, "fragment")
+            predict_staged = getattr(self._calibration, "predict_staged", None)
+            if predict_staged is not None:  # (a library that is staged is recalibrated in HBM)
+                predict_staged(self._library._fragment_df, "fragment", device=self._device, only_if_staged=True)
+            else:
+                self._calibration.predict(self._library._fragment_df, "fragment")
         # every channel that occurs anywhere: identified, reference, targets, decoy (handler :60-93)
         channels = sorted({*psm_df["channel"].unique().tolist(), mp["reference_channel"], mp["decoy_channel"],
                            *(int(c) for c in str(mp["target_channels"]).split(","))})

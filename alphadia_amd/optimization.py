@@ -99,6 +99,7 @@ class HipOptimizationLock:
         self._resident_groups = np.zeros(0, dtype=np.int64)  # elution groups of its valid rows
         self.total_elution_groups = 0
         self.fallbacks_logged: set[str] = set()  # (the workflow creates an extraction handler per step)
+        self.last_fragment_calibration: str | None = None  # path of the last update_with_calibration (predict_staged)
 
     # ------------------------------------------------------------------ accumulated rows
     def _clear(self):
@@ -199,7 +200,14 @@ class HipOptimizationLock:
     def update_with_calibration(self, calibration_manager):
         """Recalibrate the batch library.  Rows accumulated before keep the values they were scored with."""
         calibration_manager.predict(self.batch_library._precursor_df, "precursor")  # (CalibrationGroups.PRECURSOR)
-        calibration_manager.predict(self.batch_library._fragment_df, "fragment")  # (CalibrationGroups.FRAGMENT)
+        # (CalibrationGroups.FRAGMENT) the batch that was just scored is staged: its m/z is recalibrated in HBM
+        predict_staged = getattr(calibration_manager, "predict_staged", None)
+        if predict_staged is not None:
+            self.last_fragment_calibration = predict_staged(self.batch_library._fragment_df, "fragment",
+                                                            device=self._device, only_if_staged=True)
+        else:
+            calibration_manager.predict(self.batch_library._fragment_df, "fragment")
+            self.last_fragment_calibration = "host"
 
     def increase_batch_idx(self):
         self.batch_idx += 1

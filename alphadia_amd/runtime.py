@@ -92,6 +92,9 @@ EXPORTED_SYMBOLS = [
     "adh_quant_set_matrix",
     "adh_quant_filter",
     "adh_quant_time_ms",
+    "adh_calibrate_staged_fragments",
+    "adh_stage_fragments_columns",
+    "adh_staged_fragments_read",
 ]
 
 
@@ -705,9 +708,81 @@ class Context:
             return False
         m = _abi.pack_fragments(*columns)
         _check(lib.adh_stage_fragments(self._h, m.ref()), "adh_stage_fragments")
-        self._lib_key = key
-        self._lib_keepalive = columns
+        self._staged_library(columns, m.struct.n, key)
         return True
+
+    def _staged_library(self, columns, n: int, key) -> None:
+        """Bookkeeping of a staged library: the key of the nine columns it equals (None: no host column set), the key
+        of the eight columns it was staged from, the columns themselves (their addresses are part of the keys)."""
+        self._lib_key = key
+        if key is not None:  # (a key holds one entry per column)
+            self._lib_source = key[:1] + key[2:]
+        else:
+            self._lib_source = self._key(*columns[:1], *columns[2:]) if len(columns) == 9 else self._key(*columns)
+        self._lib_keepalive = columns
+        self._n_lib = int(n)
+
+    def stage_fragments_columns(self, *columns) -> None:
+        """``adh_stage_fragments_columns`` without a model: what ``stage_fragments(*columns, force=True)`` stages, the
+        records packed by a kernel from the uploaded columns."""
+        m = _abi.pack_fragments(*columns)
+        self._lib_key = None
+        _check(lib.adh_stage_fragments_columns(self._h, m.ref(), None, None), "adh_stage_fragments_columns")
+        self._staged_library(columns, m.struct.n, self._key(*columns))
+
+    def stage_fragments_calibrated(self, model, mz_library, intensity, type, loss_type, charge, number, position,  # noqa: A002
+                                   cardinality) -> np.ndarray:
+        """Stage the library from its eight columns with ``mz`` = float32 of the fitted ``model`` over ``mz_library``,
+        evaluated while the records are packed in HBM.  Returns the float64 predictions (the ``mz_calibrated`` column
+        of the frame).  The staged library then equals no host column set: ``adopt_fragment_columns`` names one."""
+        packed = _abi.pack_loess_model(model.scale_mean, model.scale_max, model.beta)
+        columns = (mz_library, intensity, type, loss_type, charge, number, position, cardinality)
+        m = _abi.pack_fragments_calibrated(*columns)
+        y = np.empty(int(m.struct.n), dtype=np.float64)
+        self._lib_key = None
+        _check(lib.adh_stage_fragments_columns(self._h, m.ref(), C.byref(packed), y.ctypes.data_as(C.POINTER(C.c_double))),
+               "adh_stage_fragments_columns")
+        self._staged_library(columns, m.struct.n, None)
+        return y
+
+    def calibrate_staged_fragments(self, model) -> np.ndarray:
+        """``adh_calibrate_staged_fragments``: rewrite ``mz`` of the staged library, in HBM, as float32 of the fitted
+        ``model`` over the staged ``mz_library``.  Returns the float64 predictions.  The staged library then equals
+        no host column set (a later ``stage_fragments`` with the old columns stages again) until
+        ``adopt_fragment_columns`` names one."""
+        packed = _abi.pack_loess_model(model.scale_mean, model.scale_max, model.beta)
+        y = np.empty(getattr(self, "_n_lib", 0), dtype=np.float64)  # (no library: the call says so)
+        self._lib_key = None
+        _check(lib.adh_calibrate_staged_fragments(self._h, C.byref(packed), y.ctypes.data_as(C.POINTER(C.c_double))),
+               "adh_calibrate_staged_fragments")
+        return y
+
+    def adopt_fragment_columns(self, *columns) -> None:
+        """Declare that the staged library equals these nine host columns (``fragment_columns(df, "mz_calibrated")``
+        after the calibrated column was written into the frame): the next ``stage_fragments`` with them skips.
+        Copies nothing."""
+        if len(columns) != 9:
+            raise ValueError("adopt_fragment_columns takes the nine fragment columns")
+        n = getattr(self, "_n_lib", None)
+        if n is None:
+            raise HipBackendError("no fragment library staged")
+        if any(np.asarray(c).shape != (n,) for c in columns):
+            raise ValueError(f"fragment columns do not have the staged library's {n} rows")
+        self._staged_library(columns, n, self._key(*columns))
+
+    def staged_from(self, mz_library, intensity, type, loss_type, charge, number, position, cardinality) -> bool:  # noqa: A002
+        """Whether the staged library was staged from these columns: its key matches them in every position but the
+        m/z one."""
+        source = getattr(self, "_lib_source", None)
+        return source is not None and source == self._key(mz_library, intensity, type, loss_type, charge, number,
+                                                          position, cardinality)
+
+    def staged_fragment_records(self, host_mirror: bool = False) -> np.ndarray:
+        """The raw records of the staged library (``_abi.LIB_RECORD_DTYPE``), from HBM or from the host mirror."""
+        out = np.empty(getattr(self, "_n_lib", 0), dtype=_abi.LIB_RECORD_DTYPE)
+        _check(lib.adh_staged_fragments_read(self._h, C.c_int32(int(bool(host_mirror))), C.c_void_p(out.ctypes.data),
+                                             C.c_int64(out.shape[0])), "adh_staged_fragments_read")
+        return out
 
     # -- scoring ---------------------------------------------------------
     def score_host(self, cands: _abi.Marshalled, cfg_jit, with_stats: bool = False,

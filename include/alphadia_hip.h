@@ -753,8 +753,41 @@ typedef struct adh_loess_model {
  */
 int adh_calibration_predict(adh_handle_t *handle, const adh_loess_model_t *model, const void *x, int32_t x_is_f64,
                             int64_t n, double *y);
-/* Summed HIP-event duration (ms) of the kernels of the last adh_calibration_predict call. */
+/* Summed HIP-event duration (ms) of the kernels of the last adh_calibration_predict, adh_calibrate_staged_fragments
+ * or adh_stage_fragments_columns call. */
 int adh_calibration_time_ms(adh_handle_t *handle, double *kernel_ms);
+
+/*
+ * Calibrate the staged fragment library where it lies: for every record i, mz = float32 (round to nearest even) of
+ * the model over its mz_library (a float32 column: x_is_f64 = 0 above), the same row evaluation as
+ * adh_calibration_predict.  Only that field is written, in HBM and in the host copy of the records; nothing is
+ * uploaded.  mz_out (may be NULL) receives the n float64 predictions, through the page-locked slots of
+ * adh_calibration_predict and counted by adh_transfer_counters as there.  The library changes, so the call settles
+ * what adh_stage_fragments settles: the last call's device tables are completed first and stop being current
+ * (accumulated resident tables keep the values they were scored with), an uploaded candidate table is dropped.
+ * Errors: no staged library -> ADH_ERR_NOT_STAGED; the model limits of adh_calibration_predict.  An empty library
+ * is fine.
+ */
+int adh_calibrate_staged_fragments(adh_handle_t *handle, const adh_loess_model_t *model, double *mz_out);
+
+/*
+ * adh_stage_fragments from the nine columns without the host pack loop: the columns go up as columns (14 or 18
+ * bytes per row) in chunks of ADH_CALIBRATION_CHUNK_ROWS rows through two page-locked slots, a kernel builds the
+ * 32-byte records in HBM (pad bytes zero), the host team (adh_host_threads) builds the identical host copy.
+ * model == NULL: fragments->mz is copied.  model != NULL: fragments->mz may be NULL and is ignored, mz is the
+ * calibrated value as adh_calibrate_staged_fragments computes it from mz_library, and mz_out (may be NULL) receives
+ * the float64 predictions.  Same limits, errors and effects on the handle as adh_stage_fragments.
+ */
+int adh_stage_fragments_columns(adh_handle_t *handle, const adh_fragments_t *fragments, const adh_loess_model_t *model,
+                                double *mz_out);
+
+/*
+ * For tests and tools: the raw 32-byte records of the staged library, from HBM (host_mirror = 0) or from the
+ * handle's host copy (host_mirror = 1).  Byte offsets: mz_library 0, mz 4, intensity 8 (float32); type 12,
+ * loss_type 13, charge 14, number 15, position 16, cardinality 17 (uint8); 18 .. 31 zero.  n must be the staged
+ * library's fragment count.
+ */
+int adh_staged_fragments_read(adh_handle_t *handle, int32_t host_mirror, void *records, int64_t n);
 
 /* ------------------------------------------------------------------------------------------
  * Cross-run fragment quantity matrices of label-free quantification
