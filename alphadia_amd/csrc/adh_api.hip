@@ -1506,6 +1506,41 @@ int adh_select_candidates(adh_handle_t *h, const adh_precursors_t *pc, const adh
     caps.k_rows = k_rows;
     caps.k_cols = k_cols;
     const int L = h->run.cycle_len;
+    // The kernel keeps sel::MAX_ROWS cycle rows per group (rows overlapping the isotope range, MS1 rows) and the
+    // reference sums every row: a cycle with more is refused here, before anything is launched, as scoring refuses
+    // more than ADH_MAX_OBS observations.  Rows overlapping [a, b] = #(lower <= b) - #(upper < a) for rows with
+    // lower <= upper (an MS1 row (-1, -1) counts in both terms): two searches per precursor.
+    {
+        if (h->run.n_ms1_obs > sel::MAX_ROWS)
+            return fail(ADH_ERR_UNSUPPORTED, "candidate selection: more than 16 cycle rows are MS1 rows");
+        std::vector<double> lower((size_t)L), upper((size_t)L);
+        for (int row = 0; row < L; ++row) {
+            lower[(size_t)row] = h->h_cycle[2 * (size_t)row];
+            upper[(size_t)row] = h->h_cycle[2 * (size_t)row + 1];
+            if (!(lower[(size_t)row] <= upper[(size_t)row])) return fail(ADH_ERR_INVALID_ARGUMENT, "cycle row with lower > upper m/z");
+        }
+        std::sort(lower.begin(), lower.end());
+        std::sort(upper.begin(), upper.end());
+        // a bound first, from the cycle alone: no range as wide as the widest isotope range (charge 1) overlaps more
+        // rows than the best one that starts at a row's upper edge.  Only a cycle that fails it is walked per precursor.
+        const double widest = (double)std::max(caps.n_iso - 1, 0) * 1.0033548350700006 + 0.01;
+        int64_t bound = 0;
+        for (int row = 0; row < L && L > sel::MAX_ROWS; ++row) {
+            const double a = upper[(size_t)row];
+            bound = std::max<int64_t>(bound, (std::upper_bound(lower.begin(), lower.end(), a + widest) - lower.begin()) -
+                                                 (std::lower_bound(upper.begin(), upper.end(), a) - upper.begin()));
+        }
+        for (int64_t i = 0; i < n && caps.n_iso > 0 && bound > sel::MAX_ROWS; ++i) {
+            if (pc->charge[i] == 0) continue;  // (refused below)
+            // the isotope range exactly as adh_select_kernel computes it (assemble_isotope_mz)
+            const double a = (double)pc->mz[i];
+            const double b = (double)(float)((double)pc->mz[i] + (double)(caps.n_iso - 1) * 1.0033548350700006 / (double)pc->charge[i]);
+            const int64_t hit = (std::upper_bound(lower.begin(), lower.end(), b) - lower.begin()) -
+                                (std::lower_bound(upper.begin(), upper.end(), a) - upper.begin());
+            if (hit > sel::MAX_ROWS)
+                return fail(ADH_ERR_UNSUPPORTED, "candidate selection: a precursor's isotope range overlaps more than 16 cycle rows");
+        }
+    }
     size_t off = 0;
     auto carve = [&](size_t bytes) {
         const size_t at = off;

@@ -582,7 +582,9 @@ typedef struct adh_candidate_table {
  * (GaussianKernel.get_dense_matrix, selection/kernel.py:141-218; the reference
  * does it by FFT, selection/fft.py:119-212), log-sum score, peak picking and
  * symmetric limits (selection/utils.py:46-312).  Host buffers in and out; `out`
- * is zero-filled by the call.
+ * is zero-filled by the call.  ADH_ERR_UNSUPPORTED, before anything is launched,
+ * when more than 16 cycle rows are MS1 rows or overlap the isotope range of one
+ * precursor (the kernel sums at most 16 rows per group, the reference all).
  */
 int adh_select_candidates(adh_handle_t *handle, const adh_precursors_t *precursors,
                           const adh_selection_config_t *config, const float *kernel,

@@ -602,6 +602,9 @@ bool process_candidate(const RunView &rv, const adh_fragments_t &lib, const Cand
     if (df.v.empty() && df.F == 0) return false; /* candidate.py:230 (also the empty timsTOF result) */
     if (df.F == 0) return false;
     if (df.K <= 1) return false;
+    /* no cycle row overlaps the isolation range: the reference raises on the empty observation list
+     * (quadrupole.py:296); the row stays invalid and nothing is gathered for it, MS1 included */
+    if (df.O == 0) return false;
 
     Dense dp_raw;
     if (rv.im())

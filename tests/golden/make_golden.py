@@ -1041,6 +1041,289 @@ def golden_timstof():
           f"mean f29 {np.nanmean(out.features[v][:, 29]):.3f}")
 
 
+# --------------------------------------------------------------------------- general cycles
+# Cycles that the touching windows of syn.make_cycle cannot express: overlapping and staggered windows, several MS1
+# rows per cycle (also none at row 0), a stretch of m/z no window covers.  Runs are sized so that a fixture stays
+# below 1 MiB: more cycle rows, fewer noise peaks per row.
+# The config_ids (seeds) are chosen so that no row of a fixture sits on a knife edge of the shim: NumPy's exp differs
+# from libm's in the last bit for one argument in twenty, which now and then moves a float32 mass error by an ulp; a
+# tie of two observation importances (quant_all off) or of two candidate scores is broken by the summation order.  With
+# such a row the Numba-typed and the NumPy-typed restatement cannot both equal the fixture.
+CYCLE_GEOMETRIES = {
+    "staggered": dict(cycle=lambda: syn.make_staggered_cycle(400.0, 480.0, 10.0), config_id=141, ms1_peaks=400, ms2_peaks=70),
+    "multi_ms1": dict(cycle=lambda: syn.make_multi_ms1_cycle(8, 400.0, 480.0, ms1_first=True), config_id=142,
+                      ms1_peaks=300, ms2_peaks=110),
+    "multi_ms1_twin": dict(cycle=lambda: syn.make_multi_ms1_cycle(8, 400.0, 480.0, ms1_first=False), config_id=153,
+                           ms1_peaks=300, ms2_peaks=110, n_precursors=200),
+    "dense_overlap": dict(cycle=lambda: syn.make_dense_overlap_cycle(400.0, 480.0), config_id=154, ms1_peaks=200,
+                          ms2_peaks=28),
+    # both at once, for candidate selection: two rows in each of its groups of cycle rows
+    "staggered_multi_ms1": dict(cycle=lambda: staggered_multi_ms1_cycle(), config_id=148, ms1_peaks=150, ms2_peaks=35,
+                                amplitude=0.5),
+}
+# fixture -> (geometry, scoring settings, extra arguments of small_case)
+CYCLE_SCORING = {
+    "staggered": ("staggered", SCORING_CONFIGS["handler_default"], {}),
+    "multi_ms1": ("multi_ms1", SCORING_CONFIGS["handler_default"], {}),
+    "multi_ms1_twin": ("multi_ms1_twin", SCORING_CONFIGS["handler_default"], {}),
+    "dense_overlap": ("dense_overlap", SCORING_CONFIGS["handler_default"], {}),
+    "dense_overlap_class": ("dense_overlap", SCORING_CONFIGS["class_default"], {}),
+    "multi_ms1_manyfrag": ("multi_ms1", MANYFRAG_CONFIGS["manyfrag"],
+                           dict(config_id=145, n_precursors=140, k_fragments=(5, 40), frag_mz_hi=500, ms2_mz_range=(195, 505))),
+}
+
+
+def staggered_multi_ms1_cycle() -> np.ndarray:
+    """The staggered windows with a second MS1 row in the middle of the cycle."""
+    rows = syn.make_staggered_cycle(400.0, 480.0, 10.0)[0, :, 0, :]
+    half = 1 + (len(rows) - 1) // 2
+    return syn.cycle_from_rows(np.concatenate([rows[:half], [[-1.0, -1.0]], rows[half:]]))
+
+
+def geometry_case(geometry: str, **kw) -> syn.SyntheticCase:
+    args = dict(CYCLE_GEOMETRIES[geometry])
+    args["cycle"] = args["cycle"]()
+    args.update(kw)
+    return small_case(**args)
+
+
+def run_scoring_tolerant(case, cfg_updates):
+    """run_scoring, one score group at a time: a candidate whose precursor range no window overlaps makes the
+    reference raise (quadrupole_transfer_function_single on an empty observation list); such a row stays
+    ``valid = False`` in the output and is listed in ``raised``."""
+    cfg = CandidateScoringConfig()
+    cfg.update(cfg_updates)
+    dia = DuckDia(case.dia)
+    cs = ref_scoring.CandidateScoring(
+        dia_data=dia, precursors_flat=case.library.precursor_df.copy(), fragments_flat=case.library.fragment_df.copy(),
+        rt_column="rt_library", mobility_column="mobility_library", precursor_mz_column="mz_library",
+        fragment_mz_column="mz_library", config=cfg,
+    )
+    cands = case.candidates_df.copy()
+    fragment_container = cs.assemble_fragments()
+    sgc = cs.assemble_score_group_container(cands)
+    out = OutputPsmDF(sgc.get_candidate_count(), cs.config.top_k_fragments)
+    raised = []
+    for g in range(len(sgc)):
+        try:
+            ref_scoring._process_score_groups(range(g, g + 1), sgc, out, fragment_container, dia.to_jitclass(),
+                                              cs.config.to_jitclass(), cs.quadrupole_calibration.jit, False)
+        except Exception as e:  # noqa: BLE001
+            raised.append((g, type(e).__name__))
+    opidx = np.array([c.precursor_idx for sg in sgc.score_groups for c in sg.candidates], dtype=np.uint32)
+    orank = np.array([c.rank for sg in sgc.score_groups for c in sg.candidates], dtype=np.uint8)
+    return out, opidx, orank, cs.config, raised
+
+
+def n_windows_of(case, top_k_isotopes: int) -> np.ndarray:
+    """Cycle rows the quadrupole range of every candidate overlaps (candidate.py:151-163,203-205 with
+    alpharaw_jit.py:46-48), in candidate order."""
+    pdf = case.library.precursor_df.set_index("precursor_idx")
+    mz = pdf.loc[case.candidates_df["precursor_idx"].values, "mz_library"].values.astype(np.float32)
+    ch = pdf.loc[case.candidates_df["precursor_idx"].values, "charge"].values.astype(np.float64)
+    iso = (np.arange(min(int(top_k_isotopes), 4))[None, :] * 1.0033548350700006 / ch[:, None]).astype(np.float32) + mz[:, None]
+    lo = (iso.min(axis=1) - 0.5).astype(np.float32)
+    hi = (iso.max(axis=1) + 0.5).astype(np.float32)
+    flat = case.dia.cycle.reshape(-1, 2)
+    return ((lo[:, None] <= flat[None, :, 1]) & (hi[:, None] >= flat[None, :, 0])).sum(axis=1)
+
+
+def golden_scoring_cycles(which=None):
+    for name, (geometry, upd, kw) in CYCLE_SCORING.items():
+        if which is not None and name not in which:
+            continue
+        case = geometry_case(geometry, **kw)
+        out, opidx, orank, cfg, raised = run_scoring_tolerant(case, upd)
+        d = case_to_dict(case)
+        od = out_to_dict(out)
+        lens = (case.library.precursor_df["flat_frag_stop_idx"].values.astype(np.int64)
+                - case.library.precursor_df["flat_frag_start_idx"].values.astype(np.int64))
+        width = int(min(int(cfg.top_k_fragments), lens.max()))
+        for k, v in od.items():
+            if v.ndim == 2 and k != "out_features" and v.shape[1] > width:
+                assert not v[:, width:].any(), k
+                od[k] = np.ascontiguousarray(v[:, :width])
+        d.update(od)
+        d["order_precursor_idx"] = opidx
+        d["order_rank"] = orank
+        d["raised_groups"] = np.array([g for g, _ in raised], dtype=np.int64)
+        cfgj = cfg.to_jitclass()
+        for k in (
+            "collect_fragments score_grouped exclude_shared_ions top_k_fragments top_k_isotopes "
+            "reference_channel quant_window quant_all precursor_mz_tolerance "
+            "fragment_mz_tolerance experimental_xic"
+        ).split():
+            d["cfg_" + k] = np.asarray(getattr(cfgj, k))
+        d["caveat"] = np.asarray(CAVEAT)
+        # ---- what the fixture is for
+        v = np.asarray(out.valid).astype(bool)
+        nobs = np.asarray(out.features)[v][:, 17]
+        nwin = n_windows_of(case, cfg.top_k_isotopes)
+        n_ms1 = len(syn.ms1_rows_of(case.dia.cycle))
+        hist = {int(o): int((nobs == o).sum()) for o in np.unique(nobs)}
+        if geometry == "staggered":
+            assert hist.get(2, 0) >= 20 and hist.get(3, 0) >= 20 and set(hist) <= {2, 3}, hist
+        if geometry.startswith("multi_ms1"):
+            assert n_ms1 == 2 and hist.get(1, 0) >= 20, (n_ms1, hist)
+        if geometry == "dense_overlap":
+            assert n_ms1 == 3 and hist.get(3, 0) >= 20 and sum(c for o, c in hist.items() if o >= 4) >= 20, hist
+            assert (nwin == 0).sum() >= 1, "no candidate outside every window"
+        # the reference raises on the candidates no window overlaps, and only on them (those with three fragments or
+        # fewer leave before): such rows stay valid = False
+        key_in = case.candidates_df["precursor_idx"].values.astype(np.int64) * 256 + case.candidates_df["rank"].values
+        key_out = opidx.astype(np.int64) * 256 + orank
+        outside = np.isin(key_out, key_in[nwin == 0])
+        assert outside[[g for g, _ in raised]].all() and not np.asarray(out.valid)[outside].any(), raised
+        assert len(raised) >= 1 or geometry != "dense_overlap"
+        d["cand_n_windows"] = nwin.astype(np.int64)
+        path = os.path.join(OUT_DIR, f"scoring_{name}.npz")
+        np.savez_compressed(path, **d)
+        print(f"{path}: {v.sum()}/{len(v)} valid, n_observations {hist}, MS1 rows {n_ms1}, windows==0: {(nwin == 0).sum()}, "
+              f"raised {raised[:3]}{'...' if len(raised) > 3 else ''} ({len(raised)}), {os.path.getsize(path)/2**20:.2f} MiB")
+
+
+def golden_get_dense_cycles():
+    """AlphaRawJIT.get_dense on the general cycles: per geometry a small run and, alternating, fragment queries
+    (quadrupole ranges as wide as a precursor's isotope range +- 0.5) and MS1 queries (quadrupole (-1, -1))."""
+    d = {"caveat": np.asarray(CAVEAT)}
+    names = ["staggered", "multi_ms1", "multi_ms1_twin", "dense_overlap"]
+    d["geometries"] = np.array(names, dtype="U")
+    n_cases = 10
+    frag_lens, ms1_lens = [], []
+    for gi, name in enumerate(names):
+        case = geometry_case(name, n_precursors=40, n_cycles=30, ms1_peaks=120, ms2_peaks=30, config_id=150 + gi)
+        jit = to_jit(case.dia)
+        rng = np.random.default_rng(31 + gi)
+        L = case.dia.cycle_len
+        for k, v in dia_to_dict(case.dia).items():
+            d[f"{name}_{k}"] = v
+        for i in range(n_cases):
+            c0 = int(rng.integers(0, 14))
+            nc = int(rng.integers(1, 16))
+            frame_limits = np.array([[c0 * L, (c0 + nc) * L, 1]], dtype=np.uint64)
+            k = int(rng.integers(2, 13))
+            if i % 2 == 1:
+                mzq = np.sort(rng.uniform(400, 480, k)).astype(np.float32)
+                quad = np.array([[-1.0, -1.0]])
+                tol = np.float32(10)
+            else:
+                mzq = np.sort(rng.uniform(200, 350, k)).astype(np.float32)
+                lo = 441.0 if (name == "dense_overlap" and i == 0) else rng.uniform(399, 478)  # (441..442.5: no window)
+                quad = np.array([[lo, lo + (1.5 if i == 0 else rng.uniform(1.5, 2.6))]], dtype=np.float32)
+                tol = np.float32(15)
+            if i % 5 == 4:  # the real m/z of peaks, so that windows are hit for sure
+                rows = jit.get_dense(frame_limits, np.array([[0, 1, 1]], dtype=np.uint64), mzq, tol, quad, absolute_masses=True)[1]
+                if len(rows):
+                    sp = int(rows[0]) + c0 * L
+                    a, b = case.dia.peak_start_idx_list[sp], case.dia.peak_stop_idx_list[sp]
+                    mzq = np.sort(rng.choice(case.dia.mz_values[a:b], size=min(k, b - a), replace=False)).astype(np.float32)
+            dense, pidx = jit.get_dense(frame_limits, np.array([[0, 1, 1]], dtype=np.uint64), mzq, tol, quad,
+                                        absolute_masses=True)
+            (ms1_lens if i % 2 == 1 else frag_lens).append(len(pidx))
+            q = f"{name}_q{i}_"
+            d[q + "frame_limits"] = frame_limits
+            d[q + "mz"] = mzq
+            d[q + "tol"] = np.asarray(tol)
+            d[q + "quad"] = np.asarray(quad, dtype=np.float64)
+            d[q + "dense"] = dense
+            d[q + "pidx"] = np.asarray(pidx, dtype=np.int64)
+    d["n_cases"] = np.asarray(n_cases)
+    # what the fixture is for: MS1 lists of 2 and 3 rows, fragment lists of 0, 2, 3 and 4 or more rows
+    assert {2, 3} <= set(ms1_lens) and {0, 2, 3} <= set(frag_lens) and max(frag_lens) >= 4, (ms1_lens, frag_lens)
+    path = os.path.join(OUT_DIR, "get_dense_cycles.npz")
+    np.savez_compressed(path, **d)
+    print(path, "MS1 lists", sorted(set(ms1_lens)), "fragment lists", sorted(set(frag_lens)), f"{os.path.getsize(path)/2**20:.2f} MiB")
+
+
+def golden_selection_cycles():
+    """CandidateSelection.__call__ (as golden_selection, same FFT stand-in) on staggered windows with two MS1 rows:
+    every precursor sums two or three fragment rows and two MS1 rows per cycle."""
+    import ref_shim
+
+    ref_shim.install_selection_glue()
+    from alphadia.search.selection import selection as ref_sel
+    from alphadia.search.selection.config_df import CandidateSelectionConfig
+
+    case = geometry_case("staggered_multi_ms1", n_precursors=200, n_cycles=100, per_precursor=1, planted_fraction=0.7)
+    d = case_to_dict(case)
+    d["caveat"] = np.asarray(CAVEAT)
+    name = "cycles"
+    cfg = CandidateSelectionConfig()
+    cfg.update(dict(rt_tolerance=30.0, candidate_count=3, min_size_rt=3))
+    dia = DuckDia(case.dia)
+    cs = ref_sel.CandidateSelection(
+        dia, case.library.precursor_df.copy(), case.library.fragment_df.copy(), cfg,
+        rt_column="rt_library", mobility_column="mobility_library",
+        precursor_mz_column="mz_library", fragment_mz_column="mz_library",
+        fwhm_rt=cfg.peak_len_rt, fwhm_mobility=cfg.peak_len_mobility,
+    )
+    df = cs(thread_count=1)
+    d[f"{name}_kernel"] = np.asarray(cs.kernel, dtype=np.float32)
+    cj = cs.config_jit
+    for k in ("rt_tolerance precursor_mz_tolerance fragment_mz_tolerance candidate_count "
+              "top_k_precursors exclude_shared_ions kernel_size f_mobility f_rt center_fraction "
+              "min_size_mobility min_size_rt max_size_mobility max_size_rt use_weighted_score "
+              "join_close_candidates join_close_candidates_scan_threshold "
+              "join_close_candidates_cycle_threshold").split():
+        d[f"{name}_cfg_{k}"] = np.asarray(getattr(cj, k))
+    for k in ("feature_mean", "feature_std", "feature_weight"):
+        d[f"{name}_cfg_{k}"] = np.asarray(getattr(cj, k), dtype=np.float64)
+    for c in ("precursor_idx rank score scan_center scan_start scan_stop frame_center frame_start "
+              "frame_stop elution_group_idx decoy").split():
+        d[f"{name}_out_{c}"] = df[c].values
+    assert len(syn.ms1_rows_of(case.dia.cycle)) == 2 and len(df) > 300
+    path = os.path.join(OUT_DIR, "selection_cycles.npz")
+    np.savez_compressed(path, **d)
+    print(path, len(df), "candidates for", df["precursor_idx"].nunique(), "precursors; ranks", np.bincount(df["rank"].values),
+          f"{os.path.getsize(path)/2**20:.2f} MiB")
+
+
+def golden_timstof_cycles():
+    """Full scoring (handler defaults) on an ion-mobility run with two MS1 frames per cycle and every MS2 frame
+    three times per cycle: two unfragmented observations, three and more fragment observations per candidate."""
+    S = 64
+    cycle = syn.make_timstof_cycle(3, 2, S, 400.0, 480.0, n_ms1_frames=2, repeats=3)
+    case = syn.make_timstof_case(n_precursors=90, n_cycles=30, config_id=49, scan_max_index=S, n_tof=24000,
+                                 events_per_push=6.0, candidates_on_window=True, cycle=cycle)
+    d = {"tims_" + c: getattr(case.dia, c) for c in TIMS_COLS}
+    d["tims_scan_max_index"] = np.asarray(case.dia.scan_max_index)
+    d["tims_zeroth_frame"] = np.asarray(case.dia.zeroth_frame)
+    for c in FRAG_COLS:
+        d["frag_" + c] = case.library.fragment_df[c].values
+    for c in PREC_NUM_COLS:
+        d["prec_" + c] = case.library.precursor_df[c].values
+    for c in CAND_COLS:
+        d["cand_" + c] = case.candidates_df[c].values
+    cfg = CandidateScoringConfig()
+    cfg.update(SCORING_CONFIGS["handler_default"])
+    dia = DuckTims(case.dia)
+    cs = ref_scoring.CandidateScoring(
+        dia_data=dia, precursors_flat=case.library.precursor_df.copy(), fragments_flat=case.library.fragment_df.copy(),
+        rt_column="rt_library", mobility_column="mobility_library", precursor_mz_column="mz_library",
+        fragment_mz_column="mz_library", config=cfg,
+    )
+    cands = case.candidates_df.copy()
+    fragment_container = cs.assemble_fragments()
+    sgc = cs.assemble_score_group_container(cands)
+    out = OutputPsmDF(sgc.get_candidate_count(), cs.config.top_k_fragments)
+    ref_scoring._process_score_groups(range(len(sgc)), sgc, out, fragment_container, dia.to_jitclass(),
+                                      cs.config.to_jitclass(), cs.quadrupole_calibration.jit, False)
+    d.update(out_to_dict(out))
+    cfgj = cfg.to_jitclass()
+    for kk in ("collect_fragments score_grouped exclude_shared_ions top_k_fragments top_k_isotopes "
+               "reference_channel quant_window quant_all precursor_mz_tolerance "
+               "fragment_mz_tolerance experimental_xic").split():
+        d["cfg_" + kk] = np.asarray(getattr(cfgj, kk))
+    d["caveat"] = np.asarray(CAVEAT)
+    v = np.asarray(out.valid).astype(bool)
+    nobs = np.asarray(out.features)[v][:, 17]
+    hist = {int(o): int((nobs == o).sum()) for o in np.unique(nobs)}
+    assert sum(c for o, c in hist.items() if o >= 3) >= 20 and v.sum() >= 40, hist
+    path = os.path.join(OUT_DIR, "scoring_timstof_cycles.npz")
+    np.savez_compressed(path, **d)
+    print(f"{path}: {v.sum()}/{len(v)} valid, n_observations {hist}, {os.path.getsize(path)/2**20:.2f} MiB")
+
+
 if __name__ == "__main__":
     if "--timstof-only" in sys.argv:
         golden_timstof()
@@ -1074,6 +1357,18 @@ if __name__ == "__main__":
     if "--host-helpers-only" in sys.argv:
         golden_host_helpers()
         sys.exit(0)
+    if "--cycles-only" in sys.argv:  # optionally followed by the fixtures to make
+        rest = [a for a in sys.argv[sys.argv.index("--cycles-only") + 1:] if not a.startswith("--") and a != OUT_DIR]
+        scoring = [a for a in rest if a in CYCLE_SCORING]
+        if not rest or scoring:
+            golden_scoring_cycles(which=scoring or None)
+        if not rest or "get_dense" in rest:
+            golden_get_dense_cycles()
+        if not rest or "selection" in rest:
+            golden_selection_cycles()
+        if not rest or "timstof" in rest:
+            golden_timstof_cycles()
+        sys.exit(0)
     if "--manyfrag-only" in sys.argv:
         golden_scoring(which=MANYFRAG_CONFIGS)
         sys.exit(0)
@@ -1089,3 +1384,7 @@ if __name__ == "__main__":
     golden_selection_timstof()
     golden_transpose()
     golden_timstof()
+    golden_scoring_cycles()
+    golden_get_dense_cycles()
+    golden_selection_cycles()
+    golden_timstof_cycles()

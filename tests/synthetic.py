@@ -100,6 +100,84 @@ def make_cycle(n_ms2: int = 60, mz_lo: float = 400.0, mz_hi: float = 1000.0) -> 
     return cycle
 
 
+def cycle_from_rows(rows) -> np.ndarray:
+    """A cycle array (1, L, 1, 2) from a list of (lower, upper) rows; an MS1 row is (-1, -1)."""
+    cycle = np.asarray(rows, dtype=np.float64).reshape(1, -1, 1, 2)
+    return np.ascontiguousarray(cycle)
+
+
+def ms1_rows_of(cycle: np.ndarray) -> np.ndarray:
+    """Rows of a non-ion-mobility cycle that are MS1 spectra, i.e. (-1, -1)."""
+    flat = cycle[0, :, 0, :]
+    return np.flatnonzero((flat[:, 0] == -1.0) & (flat[:, 1] == -1.0))
+
+
+def make_staggered_cycle(mz_lo: float = 400.0, mz_hi: float = 480.0, width: float = 10.0) -> np.ndarray:
+    """One MS1 row, ``width`` windows over [mz_lo, mz_hi], then a second set offset by half a window that
+    reaches half a window past both ends: every m/z in the range lies in two windows, and a quadrupole range
+    that crosses an edge touches three."""
+    n = int(round((mz_hi - mz_lo) / width))
+    rows = [(-1.0, -1.0)]
+    rows += [(mz_lo + width * k, mz_lo + width * (k + 1)) for k in range(n)]
+    rows += [(mz_lo + width * (k - 0.5), mz_lo + width * (k + 0.5)) for k in range(n + 1)]
+    return cycle_from_rows(rows)
+
+
+def make_multi_ms1_cycle(n_ms2: int = 8, mz_lo: float = 400.0, mz_hi: float = 480.0, ms1_first: bool = True) -> np.ndarray:
+    """Touching windows with two MS1 rows: at row 0 and in the middle of the cycle (``ms1_first``), or - the
+    twin - in the middle and at the last row, so that row 0 is a window."""
+    edges = np.linspace(mz_lo, mz_hi, n_ms2 + 1)
+    wins = [(edges[k], edges[k + 1]) for k in range(n_ms2)]
+    half = n_ms2 // 2
+    ms1 = (-1.0, -1.0)
+    rows = ([ms1] + wins[:half] + [ms1] + wins[half:]) if ms1_first else (wins[:half] + [ms1] + wins[half:] + [ms1])
+    return cycle_from_rows(rows)
+
+
+def make_dense_overlap_cycle(mz_lo: float = 400.0, mz_hi: float = 480.0, width: float = 9.0, step: float = 3.0,
+                             gap: tuple = (440.0, 444.0)) -> np.ndarray:
+    """Windows of ``width`` every ``step`` (two thirds overlap: three windows hold an m/z, a quadrupole range
+    touches three to five), three MS1 rows (first, middle, last) and the stretch ``gap`` that no window covers:
+    the windows below it end at gap[0], those above it start at gap[1].
+
+    (Width 9: with the default quadrupole calibration, sigma 0.2 Th, a window that holds an isotope more than
+    3.3 Th inside both edges transmits it with 1 - 6e-8 or more, i.e. 1.0 in float32; two such observations of one
+    precursor tie in their importance and the summation order picks the "best" one.  Windows of 9 Th every 3 Th
+    cannot hold the isotopes of a precursor that deep inside twice.)"""
+    below = []
+    hi = gap[0]
+    while hi > mz_lo:
+        below.append((hi - width, hi))
+        hi -= step
+    wins = below[::-1]
+    lo = gap[1]
+    while lo < mz_hi:
+        wins.append((lo, lo + width))
+        lo += step
+    half = len(wins) // 2
+    ms1 = (-1.0, -1.0)
+    return cycle_from_rows([ms1] + wins[:half] + [ms1] + wins[half:] + [ms1])
+
+
+def make_random_cycle(rng: np.random.Generator, mz_lo: float = 400.0, mz_hi: float = 480.0, width: float = 10.0) -> np.ndarray:
+    """A drawn geometry: windows of ``width`` overlapping by 0-0.7 of a window, 1-3 MS1 rows at random rows and,
+    half of the time, a 4 Th stretch that no window covers."""
+    overlap = float(rng.uniform(0.0, 0.7))
+    step = width * (1.0 - overlap)
+    gap_lo = float(rng.uniform(mz_lo + 2 * width, mz_hi - 2 * width)) if rng.random() < 0.5 else None
+    segments = [(mz_lo, mz_hi)] if gap_lo is None else [(mz_lo, gap_lo), (gap_lo + 4.0, mz_hi)]
+    wins = []
+    for a, b in segments:
+        lo = a
+        while lo < b:
+            wins.append((lo, lo + width if b == mz_hi else min(lo + width, b)))  # windows stop at the uncovered stretch
+            lo += step
+    rows = list(wins)
+    for _ in range(int(rng.integers(1, 4))):
+        rows.insert(int(rng.integers(0, len(rows) + 1)), (-1.0, -1.0))
+    return cycle_from_rows(rows)
+
+
 def make_library(
     n_precursors: int,
     seed: int,
@@ -217,9 +295,11 @@ def plant_peptides(
     half_width: int = 8,
     n_isotopes: int = 3,
     apex: np.ndarray | None = None,
+    amplitude: float = 1.0,
 ) -> PlantedPeaks:
     """Gaussian elution profiles for ``fraction`` of the target precursors (or for the precursors
-    whose entry of ``apex`` is a cycle >= 0: label channels of one peptide elute together)."""
+    whose entry of ``apex`` is a cycle >= 0: label channels of one peptide elute together).  ``amplitude`` scales
+    every planted peak (a cycle that observes a precursor in several rows sums them in candidate selection)."""
     rng = np.random.default_rng([seed, 2])
     pdf, fdf = library.precursor_df, library.fragment_df
     n = len(pdf)
@@ -234,8 +314,12 @@ def plant_peptides(
         lo, hi = 16, max(17, n_cycles - 16)
         apex[chosen] = rng.integers(lo, hi, chosen.size)
 
-    win_lo = cycle[0, 1:, 0, 0]
-    win_hi = cycle[0, 1:, 0, 1]
+    # MS1 rows are the (-1, -1) rows, wherever they sit; every other row is an isolation window
+    ms1_rows = ms1_rows_of(cycle)
+    win_rows = np.setdiff1d(np.arange(L), ms1_rows)
+    win_lo = cycle[0, win_rows, 0, 0]
+    win_hi = cycle[0, win_rows, 0, 1]
+    legacy = ms1_rows.size == 1 and ms1_rows[0] == 0  # one MS1 row in front: the cycle of make_cycle
 
     spec_parts, mz_parts, int_parts = [], [], []
     offs = np.arange(-half_width, half_width + 1)
@@ -247,21 +331,30 @@ def plant_peptides(
     cyc = p_apex[:, None] + offs[None, :]  # (P, W)
     ok = (cyc >= 0) & (cyc < n_cycles)
 
-    # MS1 isotopes
+    # MS1 isotopes, in every MS1 row of the cycle (every row with its own mass errors)
     for i in range(n_isotopes):
         iso_int = pdf[f"i_{i}"].values.astype(np.float64)[chosen]
         iso_mz = p_mz + i * ISOTOPE_DELTA / p_ch
-        ppm = rng.normal(2.0, 1.0, cyc.shape)
-        mzv = iso_mz[:, None] * (1.0 + ppm * 1e-6)
-        inten = 2e4 * iso_int[:, None] * gauss[None, :]
-        spec = cyc * L
-        spec_parts.append(spec[ok])
-        mz_parts.append(mzv[ok])
-        int_parts.append(inten[ok])
+        for row in ms1_rows:
+            ppm = rng.normal(2.0, 1.0, cyc.shape)
+            mzv = iso_mz[:, None] * (1.0 + ppm * 1e-6)
+            inten = amplitude * 2e4 * iso_int[:, None] * gauss[None, :]
+            spec = cyc * L + int(row)
+            spec_parts.append(spec[ok])
+            mz_parts.append(mzv[ok])
+            int_parts.append(inten[ok])
 
-    # MS2 fragments in the window that contains the precursor m/z
-    w = np.searchsorted(win_hi, p_mz, side="right")
-    w = np.clip(w, 0, len(win_lo) - 1)
+    # MS2 fragments in every window row whose range holds the precursor m/z
+    member = (win_lo[None, :] <= p_mz[:, None]) & (p_mz[:, None] < win_hi[None, :])  # (P, n_windows)
+    if legacy and win_rows.size:
+        # (the touching windows of make_cycle: a precursor outside all of them goes to the nearest one)
+        w = np.clip(np.searchsorted(win_hi, p_mz, side="right"), 0, len(win_lo) - 1)
+        none = ~member.any(axis=1)
+        member[np.flatnonzero(none), w[none]] = True
+    n_member = member.sum(axis=1)
+    max_member = int(n_member.max()) if chosen.size else 0
+    # the m-th window row of every precursor (first row where it has fewer)
+    order_w = np.argsort(~member, axis=1, kind="stable")
     fstart = pdf["flat_frag_start_idx"].values.astype(np.int64)[chosen]
     fstop = pdf["flat_frag_stop_idx"].values.astype(np.int64)[chosen]
     kmax = int((fstop - fstart).max()) if chosen.size else 0
@@ -272,14 +365,15 @@ def plant_peptides(
         idx = np.where(has, fstart + k, fstart)
         fmz = fmz_all[idx].astype(np.float64)
         fin = fint_all[idx].astype(np.float64)
-        ppm = rng.normal(2.0, 1.0, cyc.shape)
-        mzv = fmz[:, None] * (1.0 + ppm * 1e-6)
-        inten = 8e3 * fin[:, None] * gauss[None, :]
-        spec = cyc * L + 1 + w[:, None]
-        m = ok & has[:, None]
-        spec_parts.append(spec[m])
-        mz_parts.append(mzv[m])
-        int_parts.append(inten[m])
+        for m in range(max_member):
+            ppm = rng.normal(2.0, 1.0, cyc.shape)
+            mzv = fmz[:, None] * (1.0 + ppm * 1e-6)
+            inten = amplitude * 8e3 * fin[:, None] * gauss[None, :]
+            spec = cyc * L + win_rows[order_w[:, m]][:, None]
+            sel = ok & (has & (n_member > m))[:, None]
+            spec_parts.append(spec[sel])
+            mz_parts.append(mzv[sel])
+            int_parts.append(inten[sel])
 
     if spec_parts:
         spec_idx = np.concatenate(spec_parts).astype(np.int64)
@@ -293,16 +387,16 @@ def plant_peptides(
 
 
 def _gen_chunk(args):
-    (seed, chunk_id, c0, c1, L, ms1_peaks, ms2_peaks, p_spec, p_mz, p_int, r1, r2) = args
+    (seed, chunk_id, c0, c1, L, ms1_peaks, ms2_peaks, p_spec, p_mz, p_int, r1, r2, ms1_rows) = args
     rng = np.random.default_rng([seed, 3, chunk_id])
     n_cyc = c1 - c0
     n_spec = n_cyc * L
     per_spec = np.full(L, ms2_peaks, dtype=np.int64)
-    per_spec[0] = ms1_peaks
+    per_spec[ms1_rows] = ms1_peaks  # noise density by row type
     counts = np.tile(per_spec, n_cyc)
     n_noise = int(counts.sum())
     spec_local = np.repeat(np.arange(n_spec, dtype=np.int64), counts)
-    is_ms1 = (spec_local % L) == 0
+    is_ms1 = np.isin(spec_local % L, ms1_rows)
     u = rng.random(n_noise, dtype=np.float32)
     mz = np.where(is_ms1, r1[0] + (r1[1] - r1[0]) * u, r2[0] + (r2[1] - r2[0]) * u).astype(np.float32)
     inten = np.exp(rng.standard_normal(n_noise, dtype=np.float32) + np.float32(3.0)).astype(
@@ -337,6 +431,7 @@ def make_thermo_run(
     if cycle is None:
         cycle = make_cycle()
     L = cycle.shape[1]
+    ms1_rows = ms1_rows_of(cycle)
     n_spec = n_cycles * L
     rt = (np.arange(n_spec, dtype=np.float64) * (cycle_time / L)).astype(np.float32)
 
@@ -355,7 +450,7 @@ def make_thermo_run(
         b = np.searchsorted(ps, c1 * L, side="left")
         jobs.append(
             (seed, cid, c0, c1, L, ms1_peaks, ms2_peaks, ps[a:b], pm[a:b], pi[a:b],
-             ms1_mz_range, ms2_mz_range)
+             ms1_mz_range, ms2_mz_range, ms1_rows)
         )
 
     if threads > 1 and len(jobs) > 1:
@@ -457,11 +552,15 @@ def make_case(
     ms2_mz_range: tuple = (150.0, 1600.0),
     k_fragments: int | tuple = 12,
     run: bool = True,
+    cycle: np.ndarray | None = None,
+    amplitude: float = 1.0,
 ) -> SyntheticCase:
     """One full synthetic workload (run + library + candidates).  ``run=False`` leaves the run out
-    (``dia`` is None): library, planted apexes and candidates are the same as with it."""
+    (``dia`` is None): library, planted apexes and candidates are the same as with it.  ``cycle``: any cycle array
+    (MS1 rows anywhere, overlapping windows, gaps) instead of the touching windows of ``make_cycle``."""
     seed = BASE_SEED + config_id if seed is None else seed
-    cycle = make_cycle(n_ms2=n_ms2, mz_lo=mz_lo, mz_hi=mz_hi)
+    if cycle is None:
+        cycle = make_cycle(n_ms2=n_ms2, mz_lo=mz_lo, mz_hi=mz_hi)
     lib = make_library(
         n_precursors,
         seed,
@@ -473,7 +572,7 @@ def make_case(
         frag_mz_hi=frag_mz_hi,
         k_fragments=k_fragments,
     )
-    planted = plant_peptides(lib, cycle, n_cycles, seed, fraction=planted_fraction)
+    planted = plant_peptides(lib, cycle, n_cycles, seed, fraction=planted_fraction, amplitude=amplitude)
     dia = make_thermo_run(
         n_cycles,
         seed,
@@ -629,9 +728,21 @@ class TimsTOFArrays:
 
 
 def make_timstof_cycle(n_ms2_frames: int, windows_per_frame: int, scan_max_index: int,
-                       mz_lo: float, mz_hi: float, uncovered_scans: int = 2) -> np.ndarray:
+                       mz_lo: float, mz_hi: float, uncovered_scans: int = 2, n_ms1_frames: int = 1,
+                       repeats: int = 1) -> np.ndarray:
     """diaPASEF-like cycle: frame 0 = MS1 (all scans -1), every MS2 frame carries
-    ``windows_per_frame`` isolation windows stacked over scan ranges."""
+    ``windows_per_frame`` isolation windows stacked over scan ranges.
+
+    ``repeats`` > 1 appends the MS2 frames that many times in all (the same m/z window at the same scans in
+    several frames of a cycle: every precursor is seen ``repeats`` times); ``n_ms1_frames`` = 2 puts a second
+    MS1 frame into the middle of the cycle, further ones go to its end."""
+    if n_ms1_frames != 1 or repeats != 1:
+        base = make_timstof_cycle(n_ms2_frames, windows_per_frame, scan_max_index, mz_lo, mz_hi, uncovered_scans)
+        ms2 = [base[0, 1 + (j % n_ms2_frames)] for j in range(n_ms2_frames * repeats)]
+        ms1 = base[0, 0]
+        half = len(ms2) // 2
+        frames = [ms1] + ms2[:half] + ([ms1] if n_ms1_frames >= 2 else []) + ms2[half:] + [ms1] * max(n_ms1_frames - 2, 0)
+        return np.ascontiguousarray(np.stack(frames)[None])
     L = n_ms2_frames + 1
     cycle = np.full((1, L, scan_max_index, 2), -1.0, dtype=np.float64)
     n_win = n_ms2_frames * windows_per_frame
@@ -707,6 +818,7 @@ def make_timstof_case(
     candidates_on_window: bool = False,
     sorted_noise: bool = False,
     threads: int = 16,
+    cycle: np.ndarray | None = None,
 ) -> TimsTOFCase:
     """Run "B" of SURVEY.md section 8(d) at a configurable (test) scale.
 
@@ -716,7 +828,9 @@ def make_timstof_case(
     random stream, hence another run: the committed fixtures use the default."""
     seed = BASE_SEED + config_id if seed is None else seed
     rng = np.random.default_rng([seed, 7])
-    cycle = make_timstof_cycle(n_ms2_frames, windows_per_frame, scan_max_index, mz_lo, mz_hi)
+    if cycle is None:
+        cycle = make_timstof_cycle(n_ms2_frames, windows_per_frame, scan_max_index, mz_lo, mz_hi)
+    assert cycle.shape[2] == scan_max_index
     L = cycle.shape[1]
     S = scan_max_index
     n_frames = n_cycles * L + 1  # frame 0 is alphatims' empty zeroth frame
@@ -754,8 +868,8 @@ def make_timstof_case(
         if todo.size == 0:
             break
         sc_try = rng.integers(0, S, todo.size)
-        lo = cycle[0, 1:, sc_try, 0]  # (todo, L-1)
-        hi = cycle[0, 1:, sc_try, 1]
+        lo = cycle[0, :, sc_try, 0]  # (todo, L); an MS1 row (-1, -1) holds no precursor m/z
+        hi = cycle[0, :, sc_try, 1]
         ok = ((lo <= p_mz_all[todo, None]) & (hi > p_mz_all[todo, None])).any(axis=1)
         home_scan[todo[ok]] = sc_try[ok]
         todo = todo[~ok]
@@ -785,15 +899,18 @@ def make_timstof_case(
                 parts.append((push[keep], np.clip(np.searchsorted(mz_table, mzv), 0, n_tof - 1),
                               np.clip(amp[keep].astype(np.int64), 1, 60000)))
 
-        push1 = (cell_c * L + 1) * S + cell_s  # the MS1 frame of the cycle (frame 0 is the empty zeroth frame)
+        # every MS1 frame of the cycle (frame 0 of the run is the empty zeroth frame)
+        ms1_frames = np.flatnonzero((cycle[0, :, :, 0] == -1.0).all(axis=1) & (cycle[0, :, :, 1] == -1.0).all(axis=1))
         for i in range(3):
-            emit(push1, cell_mz + i * ISOTOPE_DELTA / charge, 3000.0 * pdf[f"i_{i}"].values.astype(np.float64)[cell_p] * cell_g)
+            for fr in ms1_frames:
+                push1 = (cell_c * L + 1 + int(fr)) * S + cell_s
+                emit(push1, cell_mz + i * ISOTOPE_DELTA / charge, 3000.0 * pdf[f"i_{i}"].values.astype(np.float64)[cell_p] * cell_g)
         f_start = pdf["flat_frag_start_idx"].values.astype(np.int64)
         f_stop = pdf["flat_frag_stop_idx"].values.astype(np.int64)
         f_mz = fdf["mz_library"].values.astype(np.float64)
         f_int = fdf["intensity"].values.astype(np.float64)
         k_max = int((f_stop - f_start)[chosen].max())
-        for fr in range(1, L):  # fragments in every MS2 frame row of this scan that isolates the precursor
+        for fr in range(L):  # fragments in every MS2 frame row of this scan that isolates the precursor
             sel = (cycle[0, fr, cell_s, 0] <= cell_mz) & (cell_mz < cycle[0, fr, cell_s, 1])
             if not sel.any():
                 continue

@@ -9,6 +9,10 @@ import helpers as H
 
 PPM_FEATURES = [8, 9, 41, 42, 45]
 EXACT_FEATURES = [17, 20, 21, 28, 35, 37, 43]
+# general cycles (tests/golden/make_golden.py, CYCLE_SCORING): staggered and overlapping windows, several MS1 rows
+# per cycle (the twin: none at row 0), a stretch of m/z outside every window
+CYCLE_GOLDENS = ["staggered", "multi_ms1", "multi_ms1_twin", "dense_overlap", "dense_overlap_class", "multi_ms1_manyfrag"]
+GET_DENSE_GEOMETRIES = ["staggered", "multi_ms1", "multi_ms1_twin", "dense_overlap"]
 INT_TABLES = ("fragment_precursor_idx fragment_rank fragment_position fragment_number "
               "fragment_type fragment_charge fragment_loss_type").split()
 
@@ -42,7 +46,7 @@ def _compare(got, exp, ppm_tol, rel_tol, corr_abs):
 
 
 @pytest.mark.parametrize("name", ["handler_default", "class_default", "topk6", "multiplex", "edges", "manyfrag", "manyfrag_class",
-                                  "fitted_quadrupole"])
+                                  "fitted_quadrupole", *CYCLE_GOLDENS])
 def test_oracle_numba_typing_vs_reference_goldens(oracle_lib, name):
     """Production (Numba) typing vs goldens captured under NumPy typing: validity, every
     integer table and the row order are exact; float features within 1e-4 relative except the
@@ -56,7 +60,7 @@ def test_oracle_numba_typing_vs_reference_goldens(oracle_lib, name):
 
 
 @pytest.mark.parametrize("name", ["handler_default", "class_default", "topk6", "multiplex", "edges", "manyfrag", "manyfrag_class",
-                                  "fitted_quadrupole"])
+                                  "fitted_quadrupole", *CYCLE_GOLDENS])
 def test_oracle_numpy_typing_pins_every_table(oracle_lib, name):
     """The goldens were produced by the reference running under NumPy (the shim), whose typing
     differs from Numba's at four places: the float32 MS1 collapse, the float32 normalisation of
@@ -113,6 +117,74 @@ def test_get_dense_matches_reference(oracle_lib):
             assert np.allclose(dense[1], e[1], rtol=0, atol=2e-3)
         n_hits += int((e[0] > 0).sum())
     assert n_hits > 100
+
+
+@pytest.mark.parametrize("geometry", GET_DENSE_GEOMETRIES)
+def test_get_dense_matches_reference_on_general_cycles(oracle_lib, geometry):
+    """test_get_dense_matches_reference on cycles with overlapping windows and several MS1 rows: the observation
+    list and both planes (all queries with absolute masses, the mode scoring uses) bit for bit."""
+    z = np.load(H.golden_path("get_dense_cycles.npz"))
+    dia = H.dia_from_npz({k[len(geometry) + 1:]: z[k] for k in z.files if k.startswith(geometry + "_dia_")})
+    n_hits = 0
+    for i in range(int(z["n_cases"])):
+        q = f"{geometry}_q{i}_"
+        fl, quad = z[q + "frame_limits"], z[q + "quad"]
+        dense, pidx = oracle_lib.get_dense(dia, fl[0, 0], fl[0, 1], z[q + "mz"], z[q + "tol"], quad[0, 0], quad[0, 1], True)
+        e = z[q + "dense"]
+        assert dense.shape == e.shape
+        assert np.array_equal(pidx, z[q + "pidx"])
+        assert np.array_equal(dense, e), f"case {i}"
+        n_hits += int((e[0] > 0).sum())
+    assert n_hits > 30
+
+
+def test_golden_cases_cover_the_issue():
+    """The fixtures of the general cycles contain what they are for: each of n_observations (feature 17) 1, 2, 3 and
+    >= 4 on at least 20 valid rows, MS1 observation lists of 2 and 3 rows, a candidate no window overlaps (the
+    reference raises on it: the row stays invalid), more than one MS1 row per cycle, an MS1 row that is not row 0."""
+    import synthetic as syn
+
+    counts = {1: 0, 2: 0, 3: 0, 4: 0}
+    ms1_rows, cycle_len, outside = {}, {}, 0
+    for name in CYCLE_GOLDENS:
+        z = np.load(H.golden_path(f"scoring_{name}.npz"))
+        v = z["out_valid"].astype(bool)
+        nobs = z["out_features"][v][:, 17]
+        if name != "dense_overlap_class":  # (the same run as dense_overlap: counted once)
+            for o in (1, 2, 3):
+                counts[o] += int((nobs == o).sum())
+            counts[4] += int((nobs >= 4).sum())
+        ms1_rows[name] = syn.ms1_rows_of(z["dia_cycle"]).tolist()
+        cycle_len[name] = int(z["dia_cycle"].shape[1])
+        if name == "staggered":  # two windows everywhere, three where the isotope range +- 0.5 crosses an edge
+            assert set(np.unique(nobs)) == {2.0, 3.0}
+        if name.startswith("dense_overlap"):
+            nwin = z["cand_n_windows"]
+            assert (nwin == 0).sum() >= len(z["raised_groups"]) >= 1
+            # rows of the output are in score-group order: find the candidates outside every window there
+            key_out = z["order_precursor_idx"].astype(np.int64) * 256 + z["order_rank"]
+            key_in = z["cand_precursor_idx"].astype(np.int64) * 256 + z["cand_rank"]
+            assert not v[np.isin(key_out, key_in[nwin == 0])].any()
+            outside += int((nwin == 0).sum())
+            assert nobs.max() <= 8 and (nobs >= 3).sum() >= 20
+    assert all(c >= 20 for c in counts.values()), counts
+    assert outside >= 1
+    assert ms1_rows["staggered"] == [0] and len(ms1_rows["multi_ms1"]) == 2 and ms1_rows["multi_ms1"][0] == 0
+    assert len(ms1_rows["multi_ms1_twin"]) == 2 and ms1_rows["multi_ms1_twin"][0] != 0
+    assert ms1_rows["multi_ms1_twin"][-1] == cycle_len["multi_ms1_twin"] - 1 and len(ms1_rows["dense_overlap"]) == 3
+    z = np.load(H.golden_path("get_dense_cycles.npz"))
+    ms1_lens, frag_lens = set(), set()
+    for g in GET_DENSE_GEOMETRIES:
+        for i in range(int(z["n_cases"])):
+            (ms1_lens if z[f"{g}_q{i}_quad"][0, 0] == -1.0 else frag_lens).add(len(z[f"{g}_q{i}_pidx"]))
+    assert {2, 3} <= ms1_lens and {0, 2, 3} <= frag_lens and max(frag_lens) >= 4, (ms1_lens, frag_lens)
+    z = np.load(H.golden_path("scoring_timstof_cycles.npz"))
+    v = z["out_valid"].astype(bool)
+    assert (z["out_features"][v][:, 17] >= 3).sum() >= 20
+    ms1_frames = np.flatnonzero((z["tims_cycle"][0, :, :, 0] == -1.0).all(axis=1))
+    assert len(ms1_frames) == 2
+    z = np.load(H.golden_path("selection_cycles.npz"))
+    assert len(syn.ms1_rows_of(z["dia_cycle"])) == 2 and z["dia_cycle"].shape[1] == 19
 
 
 def test_fragcomp_matches_reference(oracle_lib):
@@ -239,13 +311,13 @@ def test_threads_do_not_change_results(oracle_lib):
 
 # ---- ion-mobility (timsTOF) layout ---------------------------------------------------
 
-def _tims_golden():
+def _tims_golden(name="scoring_timstof.npz"):
     import pandas as pd
 
     import synthetic as syn
     from alphadia_amd.scoring import CandidateScoringConfig
 
-    z = np.load(H.golden_path("scoring_timstof.npz"))
+    z = np.load(H.golden_path(name))
     dia = syn.TimsTOFArrays(
         cycle=z["tims_cycle"], dia_precursor_cycle=z["tims_dia_precursor_cycle"],
         rt_values=z["tims_rt_values"], mobility_values=z["tims_mobility_values"],
@@ -279,15 +351,15 @@ def test_timstof_get_dense_matches_reference(oracle_lib):
     assert hits > 20
 
 
-def test_oracle_numpy_typing_pins_timstof(oracle_lib):
-    """The NumPy-typing pin of test_oracle_numpy_typing_pins_every_table for the ion-mobility layout
+def _numpy_typing_pins_timstof(oracle_lib, name):
+    """(test_oracle_numpy_typing_pins_timstof) The NumPy-typing pin of test_oracle_numpy_typing_pins_every_table for the ion-mobility layout
     (scoring_timstof.npz).  One more typing site shows here: the outer sum of the observation importance,
     np.sum(np.sum(template, axis=-1), axis=-1), runs over the scan axis - two slots on the AlphaRaw layout,
     18 and more here, where NumPy sums pairwise.  With it the restatement reproduces the reference bit for
     bit on every m/z and mass-error quantity, on heights and areas, and to one float32 ulp elsewhere."""
     from alphadia_amd.scoring import assemble_candidates, fragment_columns, pack_assembled
 
-    z, dia, fragment_df, precursor_df, cand, cfg = _tims_golden()
+    z, dia, fragment_df, precursor_df, cand, cfg = _tims_golden(name)
     soa = assemble_candidates(cand, precursor_df, "mz_library")
     oracle_lib.set_numpy_typing(True)
     try:
@@ -312,6 +384,34 @@ def test_oracle_numpy_typing_pins_timstof(oracle_lib):
     assert rel.max() <= 1e-6, (rel.max(), np.unravel_index(rel.argmax(), rel.shape))
     a, b = got["fragment_correlation"][v].astype(np.float64), exp["fragment_correlation"][v].astype(np.float64)
     assert np.abs(a - b).max() <= 2e-6
+    return exp
+
+
+def test_oracle_numpy_typing_pins_timstof(oracle_lib):
+    _numpy_typing_pins_timstof(oracle_lib, "scoring_timstof.npz")
+
+
+def test_oracle_numpy_typing_pins_timstof_cycles(oracle_lib):
+    """The same pin on a cycle with two MS1 frames and every MS2 frame three times: the collapse of two unfragmented
+    observations and three to six fragment observations per candidate."""
+    exp = _numpy_typing_pins_timstof(oracle_lib, "scoring_timstof_cycles.npz")
+    v = exp["valid"].astype(bool)
+    assert (exp["features"][v][:, 17] >= 3).sum() >= 20
+
+
+def test_timstof_scoring_matches_reference_cycles(oracle_lib):
+    """test_timstof_scoring_matches_reference on the cycle with two MS1 frames and repeated MS2 frames."""
+    from alphadia_amd.scoring import assemble_candidates, fragment_columns, pack_assembled
+
+    z, dia, fragment_df, precursor_df, cand, cfg = _tims_golden("scoring_timstof_cycles.npz")
+    soa = assemble_candidates(cand, precursor_df, "mz_library")
+    got = oracle_lib.score_timstof(
+        dia, fragment_columns(fragment_df, "mz_library"), pack_assembled(soa), cfg.to_jitclass()
+    )
+    exp = {n: z["out_" + n] for n in H.OUT_NAMES}
+    _compare(got, exp, ppm_tol=0.15, rel_tol=1e-4, corr_abs=1e-3)
+    v = exp["valid"].astype(bool)
+    assert v.sum() >= 40 and (exp["features"][v][:, 17] >= 3).sum() >= 20 and (exp["features"][v][:, 29] != 0).sum() > 20
 
 
 def test_timstof_scoring_matches_reference(oracle_lib):

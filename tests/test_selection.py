@@ -30,8 +30,10 @@ from alphadia_amd.selection import CANDIDATE_COLUMNS, CandidateSelectionConfig, 
 BOX = ["scan_center", "scan_start", "scan_stop", "frame_center", "frame_start", "frame_stop"]
 
 
-def _load():
-    z = np.load(H.golden_path("selection.npz"))
+def _load(name=None):
+    # "cycles": staggered windows with two MS1 rows per cycle (two or three rows in each group of cycle rows that
+    # selection sums); every other name lives in selection.npz
+    z = np.load(H.golden_path("selection_cycles.npz" if name == "cycles" else "selection.npz"))
     dia = H.dia_from_npz(z)
     fdf = pd.DataFrame({c: z["frag_" + c] for c in H.FRAG_COLS})
     pdf = pd.DataFrame({c: z["prec_" + c] for c in H.PREC_COLS})
@@ -85,7 +87,7 @@ def golden_fft_smooth_log(kernel):
 
 def _golden_case(kind, name):
     if kind == "raw":
-        z, dia, fdf, pdf = _load()
+        z, dia, fdf, pdf = _load(name)
         return z, dia, fdf, pdf, _cfg(z, name), z[name + "_kernel"], name + "_out_"
     z, dia, fdf, pdf, cfg = _load_tims()
     return z, dia, fdf, pdf, cfg, z["kernel"], "out_"
@@ -150,7 +152,7 @@ def _compare_with_golden(got: pd.DataFrame, z, name, oracle=None, kind="raw", pr
     return len(both), len(diff)
 
 
-@pytest.mark.parametrize("kind,name", [("raw", "default"), ("raw", "wide"), ("tims", None)])
+@pytest.mark.parametrize("kind,name", [("raw", "default"), ("raw", "wide"), ("tims", None), ("raw", "cycles")])
 def test_oracle_with_the_goldens_smoothing_reproduces_the_golden_exactly(oracle_lib, kind, name):
     """Everything behind the smoothing is pinned bit for bit: with the float32 FFT smoothing the golden was made with
     plugged into the restatement, every row of the golden comes out - boxes, ranks and the bits of the score."""
@@ -169,7 +171,7 @@ def test_oracle_with_the_goldens_smoothing_reproduces_the_golden_exactly(oracle_
         assert np.array_equal(got[c].to_numpy(), exp[c].to_numpy()), c
 
 
-@pytest.mark.parametrize("kind,name,n_diff", [("raw", "default", 9), ("raw", "wide", 4), ("tims", None, 8)])
+@pytest.mark.parametrize("kind,name,n_diff", [("raw", "default", 9), ("raw", "wide", 4), ("tims", None, 8), ("raw", "cycles", 34)])
 def test_every_box_that_differs_from_the_reference_is_a_near_tie(oracle_lib, kind, name, n_diff):
     """The exact convolution against the golden: the rows that differ are counted, each sits in a precursor whose score
     matrix the two smoothings move apart by <= NEAR_TIE_SCORE, none is a best candidate; every other precursor's rows
@@ -194,13 +196,13 @@ def test_kernel_matches_reference_kernel():
     assert k.dtype == np.float32 and np.array_equal(k, z["default_kernel"])
 
 
-@pytest.mark.parametrize("name", ["default", "wide"])
+@pytest.mark.parametrize("name", ["default", "wide", "cycles"])
 def test_oracle_selection_vs_reference_golden(oracle_lib, name):
-    z, dia, fdf, pdf = _load()
+    z, dia, fdf, pdf = _load(name)
     got = oracle_lib.select(dia, fragment_columns(fdf, "mz_library"), _pack(pdf), _cfg(z, name),
                             z[name + "_kernel"], n_threads=4)
     n_both, n_missing = _compare_with_golden(_frame(got), z, name)
-    assert n_both > 600
+    assert n_both > (400 if name == "cycles" else 600)  # (the "cycles" golden holds 503 rows)
 
 
 def test_selection_config_defaults_match_reference_golden():
