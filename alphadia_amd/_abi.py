@@ -731,11 +731,18 @@ STAGE_LIB_PROTOTYPES = {
 }
 
 
+# ... and of the per-class candidate counts of the launched plans (the class table in include/alphadia_hip.h)
+N_PLAN_CLASSES = 37
+PLAN_PROTOTYPES = {
+    "adh_plan_class_counts": [C.c_void_p, C.POINTER(C.c_int64), C.c_int32],
+}
+
+
 def declare(lib) -> None:
     """Argument types of the entries listed in RESIDENT_PROTOTYPES, STAGE_PART_PROTOTYPES, APPEND_PROTOTYPES,
-    QUANT_PROTOTYPES and STAGE_LIB_PROTOTYPES (the others are called with explicit casts)."""
+    QUANT_PROTOTYPES, STAGE_LIB_PROTOTYPES and PLAN_PROTOTYPES (the others are called with explicit casts)."""
     for name, argtypes in {**RESIDENT_PROTOTYPES, **STAGE_PART_PROTOTYPES, **APPEND_PROTOTYPES, **QUANT_PROTOTYPES,
-                           **STAGE_LIB_PROTOTYPES}.items():
+                           **STAGE_LIB_PROTOTYPES, **PLAN_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = C.c_int

@@ -414,6 +414,7 @@ struct adh_handle {
     double sum_gather_ms = 0.0, sum_feature_ms = 0.0;
     int64_t n_timed = 0;
     uint64_t d2h_bytes = 0;  // bytes this library copied device -> host (adh_transfer_counters)
+    int64_t class_counts[ADH_N_CLASSES] = {0};  // candidates per kernel class of every launched plan (adh_plan_class_counts)
     // page-locked staging of upload_staged (H2D of a caller's pageable arrays): per lane two buffers, their events, a stream
     struct UpLane {
         void *buf[2] = {nullptr, nullptr};

@@ -699,6 +699,7 @@ int launch_scoring_im(adh_handle *h, Plan &p, const adh_scoring_config_t *cfg, a
 int launch_scoring(adh_handle *h, Plan &p, const adh_scoring_config_t *cfg, adh_output_t *out, hipStream_t st) {
     if (h->timed.size() > 48) fold_timed(h, false);
     if (p.n == 0) return ADH_OK;
+    for (int c = 0; c < ADH_N_CLASSES; ++c) h->class_counts[c] += p.n_class[c];
     if (h->tims_staged) return launch_scoring_im(h, p, cfg, out, st);
     if (cfg->collect_fragments && p.caps_all.k > out->top_k)
         return fail(ADH_ERR_INVALID_ARGUMENT, "output top_k smaller than config.top_k_fragments");
@@ -1108,6 +1109,15 @@ int adh_kernel_time_ms(adh_handle_t *h, double *gather_ms, double *feature_ms, i
     if (reset) {
         h->sum_gather_ms = h->sum_feature_ms = 0.0;
         h->n_timed = 0;
+    }
+    return ADH_OK;
+}
+
+int adh_plan_class_counts(adh_handle_t *h, int64_t *counts, int32_t reset) {
+    if (!h || !counts) return fail(ADH_ERR_INVALID_ARGUMENT, "NULL argument");
+    for (int c = 0; c < ADH_N_CLASSES; ++c) {
+        counts[c] = h->class_counts[c];
+        if (reset) h->class_counts[c] = 0;
     }
     return ADH_OK;
 }

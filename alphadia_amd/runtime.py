@@ -95,6 +95,7 @@ EXPORTED_SYMBOLS = [
     "adh_calibrate_staged_fragments",
     "adh_stage_fragments_columns",
     "adh_staged_fragments_read",
+    "adh_plan_class_counts",
 ]
 
 
@@ -962,6 +963,16 @@ class Context:
             "adh_kernel_time_ms",
         )
         return g.value, f.value, n.value
+
+    def plan_class_counts(self, reset: bool = False) -> np.ndarray:
+        """Candidates per kernel class (the table in include/alphadia_hip.h) of every plan launched on this handle
+        since the last reset, over all chunks and scoring entry points."""
+        counts = np.zeros(_abi.N_PLAN_CLASSES, dtype=np.int64)
+        _check(
+            lib.adh_plan_class_counts(self._h, counts.ctypes.data_as(C.POINTER(C.c_int64)), C.c_int32(int(reset))),
+            "adh_plan_class_counts",
+        )
+        return counts
 
     # -- fragment competition -------------------------------------------
     def select_candidates(self, precursors: _abi.Marshalled, cfg, kernel) -> dict:

@@ -442,6 +442,24 @@ int adh_synchronize(adh_handle_t *handle);
 int adh_kernel_time_ms(adh_handle_t *handle, double *gather_ms, double *feature_ms,
                        int64_t *launches, int reset);
 
+/*
+ * Candidates per kernel class (`counts[37]`) of every plan whose scoring kernels were launched on the
+ * handle since the last reset, summed over the chunks of all scoring entry points.  Read-only host
+ * counters: tests pin the routing with them.  Classes of an AlphaRaw plan, in processing order:
+ *    0 ..  6  fused gather + feature kernel, one observation, FM = 8, 12, ..., 32 cycle registers
+ *    7 .. 13  the same for two observations
+ *   14 .. 16  register kernels for two observations (FM = 16, 24, 32) behind the gather kernel: shapes
+ *             the fused kernel does not take (more than 12 fragments kept, library slices beyond 64)
+ *   17 .. 23  register kernels for one observation (FM = 8 ... 32) behind the gather kernel, likewise
+ *   24 .. 26  the 64-lane register kernels (FM = 16, 24, 32), two observations, 33 ... 64 fragments kept
+ *   27 .. 29  the same for one observation
+ *   30 .. 32  the 32-lane register kernels, two observations, 17 ... 32 fragments kept
+ *   33 .. 35  the same for one observation
+ *   36        the generic LDS kernel behind the gather kernel (also rows flagged to be skipped)
+ * Ion-mobility plans use classes 0 (one observation), 1 (two), 2 (one observation, small tile) and 36.
+ */
+int adh_plan_class_counts(adh_handle_t *handle, int64_t *counts, int32_t reset);
+
 /* ------------------------------------------------------------------------
  * Multi-GPU: one process per GPU, candidates sharded by contiguous score-group ranges
  * (score groups are independent, search/scoring/containers/score_group.py:66-75), ONE RCCL

@@ -633,6 +633,73 @@ def golden_edges():
           f"n_obs of 0..3: {np.asarray(out.features)[:4, 17]}")
 
 
+class _ScalarExpThroughLibm:
+    """The numpy module with ``exp`` of a float64 SCALAR evaluated by libm, as Numba compiles it.  NumPy's own float64
+    exp differs from libm's in the last bit for 2 - 3 % of its arguments; in ``weighted_center_mean``
+    (features_utils.py:21) that moves a float64 mean m/z by 1e-16 relative, and the float32 rounding of the mass
+    error in ppm by one ulp on about one fragment in 15 000."""
+
+    def __getattr__(self, name):
+        return getattr(np, name)
+
+    @staticmethod
+    def exp(x):
+        import math
+
+        return np.float64(math.exp(float(x))) if np.ndim(x) == 0 else np.exp(x)
+
+
+def golden_boxes():
+    """Candidate shapes at the limits of the scoring kernel classes (tests/box_sweep.py, the thinned sweep): boxes of
+    2 ... 36 cycles with the centre on their first / middle / last cycle, at both ends of a run that ends inside a
+    cycle, one and two observations - on a 12-fragment library under the handler's settings with quant_window = 5,
+    and on library slices of 1 ... 200 fragments with every fragment kept and quant_all off."""
+    import alphadia.search.scoring.features.features_utils as features_utils
+    import box_sweep as bs
+
+    features_utils.np = _ScalarExpThroughLibm()  # (this recipe only: the other fixtures were made with NumPy's exp)
+    variants = (
+        ("boxes", False, dict(SCORING_CONFIGS["handler_default"], quant_window=5)),
+        ("boxes_ragged", True, dict(SCORING_CONFIGS["handler_default"], top_k_fragments=9999, quant_all=False)),
+    )
+    for name, ragged, upd in variants:
+        case = bs.sweep_case(ragged, golden=True)
+        out, fdf, frdf, opidx, orank, cfg = run_scoring(case, upd)
+        d = case_to_dict(case)
+        od = out_to_dict(out)
+        # the reference allocates top_k_fragments columns; keep those a library slice can fill (as "manyfrag")
+        lens = (case.library.precursor_df["flat_frag_stop_idx"].values.astype(np.int64)
+                - case.library.precursor_df["flat_frag_start_idx"].values.astype(np.int64))
+        width = int(min(int(cfg.top_k_fragments), lens.max()))
+        for k, v in od.items():
+            if v.ndim == 2 and k != "out_features":
+                assert not v[:, width:].any(), k
+                od[k] = np.ascontiguousarray(v[:, :width])
+        d.update(od)
+        d["order_precursor_idx"] = opidx
+        d["order_rank"] = orank
+        cfgj = cfg.to_jitclass()
+        for k in (
+            "collect_fragments score_grouped exclude_shared_ions top_k_fragments top_k_isotopes "
+            "reference_channel quant_window quant_all precursor_mz_tolerance "
+            "fragment_mz_tolerance experimental_xic"
+        ).split():
+            d["cfg_" + k] = np.asarray(getattr(cfgj, k))
+        # (no features_df_columns / fragments_df_columns here: their order follows a set and changes from run to run)
+        d["features_df_precursor_idx"] = fdf["precursor_idx"].values
+        d["features_df_rank"] = fdf["rank"].values
+        d["features_df_delta_rt"] = fdf["delta_rt"].values
+        d["fragments_df_precursor_idx"] = frdf["precursor_idx"].values
+        d["fragments_df_mz_observed"] = frdf["mz_observed"].values
+        d["fragments_df_n"] = np.asarray(len(frdf))
+        d["caveat"] = np.asarray(CAVEAT)
+        path = os.path.join(OUT_DIR, f"scoring_{name}.npz")
+        np.savez_compressed(path, **d)
+        v = np.asarray(out.valid)
+        print(f"{path}: {v.sum()}/{len(v)} valid, {os.path.getsize(path)/1e6:.2f} MB")
+    features_utils.np = np
+
+
 def golden_selection():
     """Next-row golden: CandidateSelection.__call__ on a small AlphaRaw run.
 
@@ -1348,6 +1415,9 @@ if __name__ == "__main__":
     if "--edges-only" in sys.argv:
         golden_edges()
         sys.exit(0)
+    if "--boxes-only" in sys.argv:
+        golden_boxes()
+        sys.exit(0)
     if "--multiplex-only" in sys.argv:
         golden_multiplex()
         sys.exit(0)
@@ -1379,6 +1449,7 @@ if __name__ == "__main__":
     golden_host_helpers()
     golden_staging()
     golden_edges()
+    golden_boxes()
     golden_selection()
     golden_selection_kats()
     golden_selection_timstof()

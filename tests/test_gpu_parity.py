@@ -129,7 +129,7 @@ def compare(got, exp, ppm_tol, rel_tol=REL_TOL, corr_abs=0.0):
 
 
 @pytest.mark.parametrize("name", ["handler_default", "class_default", "topk6", "multiplex", "edges", "manyfrag", "manyfrag_class",
-                                  "fitted_quadrupole"])
+                                  "fitted_quadrupole", "boxes", "boxes_ragged"])
 def test_hip_matches_oracle_on_golden_inputs(ctx, oracle_lib, name):
     g = H.load_scoring_golden(name)
     got, soa = hip_score(ctx, g, g.config)
@@ -155,7 +155,7 @@ def test_library_columns_rebuilt_from_slots(ctx, name):
 
 
 @pytest.mark.parametrize("name", ["handler_default", "class_default", "topk6", "multiplex", "edges", "manyfrag", "manyfrag_class",
-                                  "fitted_quadrupole"])
+                                  "fitted_quadrupole", "boxes", "boxes_ragged"])
 def test_hip_matches_reference_goldens(ctx, name):
     g = H.load_scoring_golden(name)
     got, _ = hip_score(ctx, g, g.config)

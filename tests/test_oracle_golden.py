@@ -12,6 +12,8 @@ EXACT_FEATURES = [17, 20, 21, 28, 35, 37, 43]
 # general cycles (tests/golden/make_golden.py, CYCLE_SCORING): staggered and overlapping windows, several MS1 rows
 # per cycle (the twin: none at row 0), a stretch of m/z outside every window
 CYCLE_GOLDENS = ["staggered", "multi_ms1", "multi_ms1_twin", "dense_overlap", "dense_overlap_class", "multi_ms1_manyfrag"]
+# candidate shapes at the limits of the kernel classes (tests/box_sweep.py; make_golden.py, golden_boxes)
+BOX_GOLDENS = ["boxes", "boxes_ragged"]
 GET_DENSE_GEOMETRIES = ["staggered", "multi_ms1", "multi_ms1_twin", "dense_overlap"]
 INT_TABLES = ("fragment_precursor_idx fragment_rank fragment_position fragment_number "
               "fragment_type fragment_charge fragment_loss_type").split()
@@ -46,7 +48,7 @@ def _compare(got, exp, ppm_tol, rel_tol, corr_abs):
 
 
 @pytest.mark.parametrize("name", ["handler_default", "class_default", "topk6", "multiplex", "edges", "manyfrag", "manyfrag_class",
-                                  "fitted_quadrupole", *CYCLE_GOLDENS])
+                                  "fitted_quadrupole", *CYCLE_GOLDENS, *BOX_GOLDENS])
 def test_oracle_numba_typing_vs_reference_goldens(oracle_lib, name):
     """Production (Numba) typing vs goldens captured under NumPy typing: validity, every
     integer table and the row order are exact; float features within 1e-4 relative except the
@@ -60,7 +62,7 @@ def test_oracle_numba_typing_vs_reference_goldens(oracle_lib, name):
 
 
 @pytest.mark.parametrize("name", ["handler_default", "class_default", "topk6", "multiplex", "edges", "manyfrag", "manyfrag_class",
-                                  "fitted_quadrupole", *CYCLE_GOLDENS])
+                                  "fitted_quadrupole", *CYCLE_GOLDENS, *BOX_GOLDENS])
 def test_oracle_numpy_typing_pins_every_table(oracle_lib, name):
     """The goldens were produced by the reference running under NumPy (the shim), whose typing
     differs from Numba's at four places: the float32 MS1 collapse, the float32 normalisation of
@@ -69,7 +71,9 @@ def test_oracle_numpy_typing_pins_every_table(oracle_lib, name):
     shim executed, the restatement reproduces the reference BIT FOR BIT on every m/z and mass
     error quantity (features 8, 9, 10, 41, 42, 45, fragment_mz_observed, fragment_mass_error,
     fragment_height; one and several observations) and to one float32 ulp on everything else
-    (the remaining pairwise sums of the shim are not modelled): the restatement itself is pinned."""
+    (the remaining pairwise sums of the shim are not modelled): the restatement itself is pinned.
+    (The two fixtures of the kernel-class limits come from a reference run with libm's float64 ``exp`` in
+    ``weighted_center_mean``, which is what Numba compiles and the oracle calls: DESIGN.md section 8.)"""
     g = H.load_scoring_golden(name)
     oracle_lib.set_numpy_typing(True)
     try:
