@@ -723,6 +723,18 @@ QUANT_PROTOTYPES = {
 }
 
 
+# ... and of protein inference (adh_pg_*, adh_grouping.hip)
+_i32p = C.POINTER(C.c_int32)
+PG_PROTOTYPES = {
+    "adh_pg_create": [C.c_void_p, C.POINTER(C.c_void_p)],
+    "adh_pg_destroy": [C.c_void_p],
+    "adh_pg_solve": [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, _i32p, _i32p, _i32p, _i32p, _i32p],
+    "adh_pg_filter": [C.c_void_p, C.c_int32, _i32p, _i32p, _i32p, _i32p, C.POINTER(C.c_int64)],
+    "adh_pg_stats": [C.c_void_p, _i32p, _i32p, _i32p],
+    "adh_pg_time_ms": [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)],
+}
+
+
 # ... and of the library staged from its columns and calibrated in HBM (adh_stage_lib.hip, adh_calibration.hip)
 STAGE_LIB_PROTOTYPES = {
     "adh_calibrate_staged_fragments": [C.c_void_p, C.POINTER(LoessModel), C.POINTER(C.c_double)],
@@ -740,9 +752,9 @@ PLAN_PROTOTYPES = {
 
 def declare(lib) -> None:
     """Argument types of the entries listed in RESIDENT_PROTOTYPES, STAGE_PART_PROTOTYPES, APPEND_PROTOTYPES,
-    QUANT_PROTOTYPES, STAGE_LIB_PROTOTYPES and PLAN_PROTOTYPES (the others are called with explicit casts)."""
+    QUANT_PROTOTYPES, PG_PROTOTYPES, STAGE_LIB_PROTOTYPES and PLAN_PROTOTYPES (the others are called with explicit casts)."""
     for name, argtypes in {**RESIDENT_PROTOTYPES, **STAGE_PART_PROTOTYPES, **APPEND_PROTOTYPES, **QUANT_PROTOTYPES,
-                           **STAGE_LIB_PROTOTYPES, **PLAN_PROTOTYPES}.items():
+                           **PG_PROTOTYPES, **STAGE_LIB_PROTOTYPES, **PLAN_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = C.c_int

@@ -1983,3 +1983,4 @@ int adh_fragcomp_stats(adh_handle_t *h, double *kernel_ms, int64_t *pairs, int64
 #include "adh_take_rows.hip"
 #include "adh_resident_append.hip"
 #include "adh_quant.hip"
+#include "adh_grouping.hip"

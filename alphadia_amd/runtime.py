@@ -96,6 +96,12 @@ EXPORTED_SYMBOLS = [
     "adh_stage_fragments_columns",
     "adh_staged_fragments_read",
     "adh_plan_class_counts",
+    "adh_pg_create",
+    "adh_pg_destroy",
+    "adh_pg_solve",
+    "adh_pg_filter",
+    "adh_pg_stats",
+    "adh_pg_time_ms",
 ]
 
 
@@ -1171,6 +1177,11 @@ class Context:
         rows whose precursor is in ``psm_precursor_idx``."""
         return DeviceQuant(self, n_columns, psm_precursor_idx)
 
+    # -- protein inference ------------------------------------------------
+    def protein_groups(self) -> DeviceProteinGroups:
+        """An ``adh_pg_t``: the greedy set cover of protein inference, one cover per connected component."""
+        return DeviceProteinGroups(self)
+
 
 class DeviceMlp:
     """An ``adh_mlp_t``: the classifier network with its parameters, optimiser moments and the
@@ -1412,6 +1423,68 @@ class DeviceQuant:
         a, b = C.c_double(0.0), C.c_double(0.0)
         _check(lib.adh_quant_time_ms(self._q, C.byref(a), C.byref(b)), "adh_quant_time_ms")
         return float(a.value), float(b.value)
+
+
+class DeviceProteinGroups:
+    """An ``adh_pg_t``: the set cover of protein inference over (pattern, id) edges and its heuristic filter
+    (include/alphadia_hip.h: adh_pg_*)."""
+
+    def __init__(self, ctx: Context):
+        self._ctx = ctx  # keeps the handle alive
+        self._g = C.c_void_p()
+        _check(lib.adh_pg_create(ctx._h, C.byref(self._g)), "adh_pg_create")
+        self.n_patterns = self.n_ids = self.n_edges = 0
+
+    def close(self):
+        if self._g:
+            lib.adh_pg_destroy(self._g)
+            self._g = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _p(a):
+        return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+    def solve(self, edge_pattern, edge_id, weight, n_ids: int):
+        """``(pattern_master, id_emptied_by)`` of ``adh_pg_solve``: one weight per pattern, ``n_ids`` id codes."""
+        ep, ei, w = (_abi.as_c(x, np.int32) for x in (edge_pattern, edge_id, weight))
+        if ep.ndim != 1 or ep.shape != ei.shape or w.ndim != 1:
+            raise ValueError("solve: one pattern and one id per edge, one weight per pattern")
+        master = np.empty(w.shape[0], np.int32)
+        emptied = np.empty(max(int(n_ids), 0), np.int32)
+        _check(lib.adh_pg_solve(self._g, w.shape[0], int(n_ids), ep.shape[0], self._p(ep), self._p(ei), self._p(w),
+                                self._p(master), self._p(emptied)), "adh_pg_solve")
+        self.n_patterns, self.n_ids, self.n_edges = w.shape[0], int(n_ids), ep.shape[0]
+        return master, emptied
+
+    def filter(self, id_string, id_rank, n_strings: int):
+        """``(offsets, ids)`` of ``adh_pg_filter``: per pattern, its ids whose string a master carries, by rank."""
+        s, r = _abi.as_c(id_string, np.int32), _abi.as_c(id_rank, np.int32)
+        if s.shape != (self.n_ids,) or r.shape != (self.n_ids,):
+            raise ValueError("filter: one string code and one rank per id of the last solve")
+        off = np.empty(self.n_patterns + 1, np.int32)
+        ids = np.empty(max(self.n_edges, 1), np.int32)
+        kept = C.c_int64(0)
+        _check(lib.adh_pg_filter(self._g, int(n_strings), self._p(s), self._p(r), self._p(off), self._p(ids),
+                                 C.byref(kept)), "adh_pg_filter")
+        return off, ids[: int(kept.value)]
+
+    def stats(self) -> tuple[int, int, int]:
+        """(components, components of more than 64 ids, labelling rounds) of the last solve."""
+        a, b, c = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        _check(lib.adh_pg_stats(self._g, C.byref(a), C.byref(b), C.byref(c)), "adh_pg_stats")
+        return int(a.value), int(b.value), int(c.value)
+
+    def time_ms(self) -> tuple[float, float, float]:
+        """HIP-event times (ms) of the component labelling, the cover and the filter."""
+        a, b, c = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
+        _check(lib.adh_pg_time_ms(self._g, C.byref(a), C.byref(b), C.byref(c)), "adh_pg_time_ms")
+        return float(a.value), float(b.value), float(c.value)
 
 
 _contexts: dict[int, Context] = {}

@@ -855,6 +855,39 @@ int adh_quant_filter(adh_quant_t *quant, int32_t column, const int32_t *group, i
 /* HIP-event times (ms) of the device work of adh_quant_build and of the last adh_quant_filter */
 int adh_quant_time_ms(adh_quant_t *quant, double *build_ms, double *filter_ms);
 
+/* ------------------------------------------------------------------------------------------
+ * Protein inference: the greedy set cover of perform_grouping (outputtransform/grouping.py:8-194).
+ * The host sends the distinct id strings of a precursor table as "patterns" weighted by their
+ * number of precursors, and the deduplicated edge list (pattern, id code); id codes number the
+ * ids in their order of first appearance, the two decoy classes with disjoint codes.  The device
+ * labels the connected components of that graph and runs one cover per component: repeatedly the
+ * id with the largest weight of uncovered patterns (the smallest code on a tie) becomes the master
+ * of those patterns.  Strings stay on the host.
+ * ------------------------------------------------------------------------------------------ */
+
+typedef struct adh_pg adh_pg_t;
+
+int adh_pg_create(adh_handle_t *handle, adh_pg_t **pg);
+int adh_pg_destroy(adh_pg_t *pg);
+/* One cover over n_edges distinct edges (edge_pattern[e] in [0, n_patterns), edge_id[e] in [0, n_ids)) and
+ * weight[n_patterns] >= 0 (their sum below 2^31).  pattern_master[p]: the id that covers pattern p (-1: a pattern
+ * no id with a positive weight holds); id_emptied_by[i]: the master whose claim took the last uncovered pattern of
+ * id i (-1: none; masters themselves have -1).  Codes out of range, a negative weight or an edge count that the
+ * sizes cannot hold fail with ADH_ERR_INVALID_ARGUMENT before anything is launched; the component labelling gives
+ * up with ADH_ERR_HIP after a fixed number of rounds. */
+int adh_pg_solve(adh_pg_t *pg, int32_t n_patterns, int32_t n_ids, int64_t n_edges, const int32_t *edge_pattern,
+                 const int32_t *edge_id, const int32_t *weight, int32_t *pattern_master, int32_t *id_emptied_by);
+/* The heuristic filter over the last cover: a string is allowed if an id that carries it (id_string[n_ids], codes in
+ * [0, n_strings)) is a master; offsets[n_patterns + 1] and ids[*n_kept] (room for n_edges) give, per pattern, its ids
+ * with an allowed string by ascending id_rank[n_ids]. */
+int adh_pg_filter(adh_pg_t *pg, int32_t n_strings, const int32_t *id_string, const int32_t *id_rank, int32_t *offsets,
+                  int32_t *ids, int64_t *n_kept);
+/* components of the last cover, those of more than 64 ids among them, and the rounds the labelling took */
+int adh_pg_stats(adh_pg_t *pg, int32_t *n_components, int32_t *n_large, int32_t *rounds);
+/* HIP-event times (ms) of the last cover's component labelling (with the CSR build) and cover kernels, and of the
+ * last filter */
+int adh_pg_time_ms(adh_pg_t *pg, double *label_ms, double *cover_ms, double *filter_ms);
+
 #ifdef __cplusplus
 }
 #endif
