@@ -23,24 +23,20 @@ __global__ void adh_slot_count_kernel(const uint16_t *__restrict__ lib_slot, int
     cnt[i] = k;  // (entry n: 0, so that the scan's last entry is the total)
 }
 
-// a chunk's block of R rows and S filled slots: [offsets u32 x (R + 1) | fragment_lib_slot u16 x S | mz_observed, height,
-// intensity, mass_error, correlation f32 x S]; every column starts on a multiple of 16 bytes
-struct PadBlock {
-    size_t slot, f[5], total;
-    __host__ __device__ PadBlock(uint64_t R, uint64_t S) {
-        size_t o = ((R + 1) * 4 + 15) & ~(size_t)15;
-        slot = o, o += (S * 2 + 15) & ~(size_t)15;
-        for (int j = 0; j < 5; ++j) f[j] = o, o += (S * 4 + 15) & ~(size_t)15;
-        total = o;
-    }
-};
+#include "adh_fill_host.h"  // PadBlock, SparseBlock, fill_host_rows
+
 // where the block of the chunk that starts at row a sits in the staging buffers (device and host alike): room for every
-// slot filled, and 64 bytes of slack behind the last block (the host reads a row's 12 floats unmasked)
+// slot filled - with every flag set a sparse block is a dense one plus its header and anchors, 8 bytes per anchored row
+// (at most R / kAnchorRows + 1 of a chunk's R rows), so a block's place moves by 8 bytes per kAnchorRows rows in front
+// of it on either wire - and 64 bytes of slack behind the last block (the host reads a row's 12 floats unmasked)
 struct PadLayout {
     size_t per_row, total;
     PadLayout(int64_t n, int top_k, int64_t n_chunks)
-        : per_row(4 + (size_t)top_k * 22), total((size_t)n * per_row + (size_t)(n_chunks + 1) * 1024 + 64) {}
-    size_t base(int64_t a, int64_t ci) const { return ((size_t)a * per_row + (size_t)ci * 1024 + 255) & ~(size_t)255; }
+        : per_row(4 + (size_t)top_k * 22), total(base(n, n_chunks + 1, 4 + (size_t)top_k * 22) + 64) {}
+    size_t base(int64_t a, int64_t ci) const { return base(a, ci, per_row); }
+    static size_t base(int64_t a, int64_t ci, size_t per_row_) {
+        return ((size_t)a * per_row_ + ((size_t)(a / kAnchorRows) + (size_t)ci) * 8 + (size_t)ci * 1024 + 255) & ~(size_t)255;
+    }
 };
 
 // one thread per (row, slot) of the chunk; the offsets (block + 0) are the scanned counts
@@ -64,6 +60,108 @@ __global__ void adh_pad_pack_kernel(DevOut t, int64_t row0, int64_t n, int top_k
     reinterpret_cast<float *>(block + L.f[2])[dst] = t.fragment_intensity[src];
     reinterpret_cast<float *>(block + L.f[3])[dst] = t.fragment_mass_error[src];
     reinterpret_cast<float *>(block + L.f[4])[dst] = t.fragment_correlation[src];
+}
+
+// ---- the sparse-slot wire of the same block (SparseBlock, adh_fill_host.h): fragment_intensity and
+// fragment_correlation travel as streams of their non-zero words.  Per row the count kernel also counts those words
+// among the row's filled slots (and the slot values that leave no room for the flags), ONE exclusive scan of the four
+// counts gives a row's place in the slot columns and in both streams, and the pack kernel writes offsets, anchors,
+// flagged slot words, the three dense columns and the two streams - count, scan, pack, as on the dense wire.
+struct alignas(16) SlotCnt {
+    uint32_t s, i, c, big;  // filled slots, non-zero intensity words, non-zero correlation words, slot values >= big_from
+};
+struct SlotCntSum {
+    __host__ __device__ SlotCnt operator()(const SlotCnt &a, const SlotCnt &b) const {
+        return SlotCnt{a.s + b.s, a.i + b.i, a.c + b.c, a.big + b.big};
+    }
+};
+
+// one thread per row, as adh_slot_count_kernel: 0.048 - 0.052 ms per 500 000-row chunk against that kernel's 0.009 (three
+// columns walked at 24- and 48-byte strides).  Measured and dropped: one thread per slot with the lanes of a row voting
+// and the lane of slot 0 counting the votes - coalesced loads, but of all 12 slots of a row where 4.6 are filled:
+// 0.069 - 0.071 ms (profiles/sparse_slots.json, `count_by_votes`).
+__global__ void adh_slot_count_nz_kernel(const uint16_t *__restrict__ lib_slot, const uint32_t *__restrict__ intensity,
+                                         const uint32_t *__restrict__ correlation, int64_t row0, int64_t n, int top_k,
+                                         uint32_t big_from, SlotCnt *__restrict__ cnt) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > n) return;
+    SlotCnt v{0, 0, 0, 0};
+    if (i < n) {
+        const int64_t r0 = (row0 + i) * (int64_t)top_k;
+        const uint16_t *s = lib_slot + r0;
+        for (; v.s < (uint32_t)top_k && s[v.s]; ++v.s) {  // (filled slots are the leading ones: candidate.py:403-442)
+            v.i += intensity[r0 + v.s] != 0u;
+            v.c += correlation[r0 + v.s] != 0u;
+            v.big += s[v.s] >= big_from;
+        }
+    }
+    cnt[i] = v;  // (entry n: zeros, so that the scan's last entry holds the totals)
+}
+
+// one thread per (row, slot) of the chunk; `scan`: the scanned counts.  Thread 0 stores the totals and the block's
+// format into page-locked memory (totals[0 .. 3]) and into the block's header.  A slot's place in a stream comes from
+// the votes of the lanes below it: 0.054 - 0.060 ms per 500 000-row chunk, against 0.066 - 0.068 with every thread reading the
+// row's slots in front of its own (profiles/sparse_slots.json, `pack_by_loop`) and the 0.032 of adh_pad_pack_kernel.
+__global__ void adh_pad_pack_sparse_kernel(DevOut t, int64_t row0, int64_t n, int top_k, const SlotCnt *__restrict__ scan,
+                                           unsigned char *__restrict__ block, uint32_t *__restrict__ totals) {
+    const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const SlotCnt tot = scan[n];
+    const bool sparse = tot.big == 0;
+    const SparseBlock L((uint64_t)row0, (uint64_t)n, tot.s, tot.i, tot.c, sparse);
+    uint32_t *const off = reinterpret_cast<uint32_t *>(block + L.off);
+    if (id == 0) {
+        const uint32_t head[4] = {sparse ? kWireSparse : kWireDense, tot.s, tot.i, tot.c};
+        for (int q = 0; q < 4; ++q) reinterpret_cast<uint32_t *>(block)[q] = head[q], totals[q] = head[q];  // (totals: page-locked host memory)
+        off[n] = tot.s;
+    }
+    const bool in_table = id < n * top_k;
+    const int64_t i = in_table ? id / top_k : 0;
+    const int j = in_table ? (int)(id - i * top_k) : 0;
+    SlotCnt a{0, 0, 0, 0};
+    uint32_t k = 0;
+    if (in_table) {
+        a = scan[i];
+        k = scan[i + 1].s - a.s;
+        if (j == 0) {
+            off[i] = a.s;
+            if (sparse && (row0 + i) % kAnchorRows == 0) {  // (anchors sit on the table's row numbers)
+                uint32_t *anchor = reinterpret_cast<uint32_t *>(block + L.anchor) +
+                                   2 * ((row0 + i) / kAnchorRows - (int64_t)SparseBlock::anchor_row0((uint64_t)row0));
+                anchor[0] = a.i, anchor[1] = a.c;
+            }
+        }
+    }
+    const bool filled = in_table && (uint32_t)j < k;
+    const int64_t src = (row0 + i) * (int64_t)top_k + j;
+    const uint32_t *const intensity = reinterpret_cast<const uint32_t *>(t.fragment_intensity);
+    const uint32_t *const correlation = reinterpret_cast<const uint32_t *>(t.fragment_correlation);
+    const uint32_t vi = filled ? intensity[src] : 0u, vc = filled ? correlation[src] : 0u;
+    // (every lane of the wavefront votes: a row's slots sit in consecutive lanes)
+    const uint64_t nz_i = __ballot(vi != 0u), nz_c = __ballot(vc != 0u);
+    if (!filled) return;
+    const size_t dst = (size_t)a.s + (size_t)j;
+    uint16_t word = t.fragment_lib_slot[src];
+    size_t di = dst, dc = dst;
+    if (sparse) {
+        // the slot's place in a stream: the row's, plus the non-zero words of the row's j slots in front of this one -
+        // the votes of the j lanes below this one, or, where the row began in the wavefront before, the words themselves
+        uint32_t pi = a.i, pc = a.c;
+        const int lane = (int)(threadIdx.x & (ADH_WAVE - 1));
+        if (j <= lane) {
+            const uint64_t before = ((1ull << j) - 1ull) << (lane - j);
+            pi += (uint32_t)__popcll(nz_i & before), pc += (uint32_t)__popcll(nz_c & before);
+        } else {
+            for (int q = 0; q < j; ++q) pi += intensity[src - j + q] != 0u, pc += correlation[src - j + q] != 0u;
+        }
+        di = pi, dc = pc;
+        word |= (vi ? kHasIntensity : 0u) | (vc ? kHasCorrelation : 0u);
+    }
+    reinterpret_cast<uint16_t *>(block + L.slot)[dst] = word;
+    reinterpret_cast<float *>(block + L.f[0])[dst] = t.fragment_mz_observed[src];
+    reinterpret_cast<float *>(block + L.f[1])[dst] = t.fragment_height[src];
+    reinterpret_cast<float *>(block + L.f[3])[dst] = t.fragment_mass_error[src];
+    if (!sparse || vi) reinterpret_cast<uint32_t *>(block + L.f[2])[di] = vi;
+    if (!sparse || vc) reinterpret_cast<uint32_t *>(block + L.f[4])[dc] = vc;
 }
 
 // ---- compacted, column-major copy-out of the operator path (round 5, adh_score_candidates_compact).  What the
@@ -259,154 +357,6 @@ void rebuild_host_rows(const adh_handle *h, const adh_candidates_t *c, adh_outpu
     }
 }
 
-// rows [lo, hi) of the chunk that starts at row a0 and has R rows, from its packed block (host copy): ONE pass that
-// writes every host column of a row - precursor_idx and rank, the five computed fragment columns and fragment_lib_slot
-// (when the caller asked for it) from the block, the library / id columns of the row's K filled slots from the host copy
-// of the library - with zeros behind the K filled slots.  Byte for byte what the copy of the padded tables plus
-// rebuild_host_rows write (skipped rows have no filled slot: zeros everywhere).
-void fill_host_rows(const adh_handle *h, const adh_candidates_t *c, adh_output_t *out, const unsigned char *blk, int64_t R,
-                    int64_t a0, int64_t lo, int64_t hi) {
-    const int top_k = out->top_k;
-    const LibRec *lib = h->h_lib.data();
-    const uint32_t *off = reinterpret_cast<const uint32_t *>(blk);
-    const PadBlock L((uint64_t)R, (uint64_t)off[R]);
-    const uint16_t *src_s = reinterpret_cast<const uint16_t *>(blk + L.slot);
-    const float *src[5];
-    for (int j = 0; j < 5; ++j) src[j] = reinterpret_cast<const float *>(blk + L.f[j]);
-    float *const dst[5] = {out->fragment_mz_observed, out->fragment_height, out->fragment_intensity, out->fragment_mass_error,
-                           out->fragment_correlation};
-    uint16_t *const slot_out = out->fragment_lib_slot;  // (NULL: the caller did not ask for the slots)
-    uint8_t *const u8col[6] = {out->fragment_rank, out->fragment_position, out->fragment_number, out->fragment_type,
-                               out->fragment_charge, out->fragment_loss_type};
-    if (top_k == 12) {
-        // the usual width (default.yaml:185), in tiles of 16 rows.  A tile's rows of every column are assembled in local
-        // buffers first, then each column's part of the tile leaves as one run of streaming stores (768 bytes of a 4-byte
-        // column, 192 of a byte column: whole cache lines, as tiles start on multiples of 16 rows) - one column after the
-        // other.  (Storing a row's 14 columns side by side with streaming stores left the core's write-combining buffers
-        // to be flushed half-filled: the host team took 2x as long as the copies it replaces.)  The packed source is
-        // read unmasked (a column has slack behind its last entry, the buffer behind its last block) and cut to the
-        // row's k entries with a mask.
-        alignas(16) static const uint32_t kMask[13][12] = {
-#define ADH_M(k) {k > 0 ? ~0u : 0u, k > 1 ? ~0u : 0u, k > 2 ? ~0u : 0u, k > 3 ? ~0u : 0u, k > 4 ? ~0u : 0u, k > 5 ? ~0u : 0u, \
-                  k > 6 ? ~0u : 0u, k > 7 ? ~0u : 0u, k > 8 ? ~0u : 0u, k > 9 ? ~0u : 0u, k > 10 ? ~0u : 0u, k > 11 ? ~0u : 0u}
-            ADH_M(0), ADH_M(1), ADH_M(2), ADH_M(3), ADH_M(4), ADH_M(5), ADH_M(6), ADH_M(7), ADH_M(8), ADH_M(9), ADH_M(10), ADH_M(11), ADH_M(12)
-#undef ADH_M
-        };
-        constexpr int TR = 16;
-        alignas(64) float tf[8][TR * 12];    // 5 computed columns, mz_library, mz, fragment_precursor_idx (as bits)
-        alignas(64) uint8_t tb[6][TR * 12];  // fragment_rank, position, number, type, charge, loss_type
-        alignas(64) uint16_t ts[TR * 12];
-        alignas(64) uint32_t tp[TR];
-        alignas(64) uint8_t tr[TR];
-        float *const dstf[8] = {dst[0], dst[1], dst[2], dst[3], dst[4], out->fragment_mz_library, out->fragment_mz,
-                                reinterpret_cast<float *>(out->fragment_precursor_idx)};
-        auto put = [](void *d, const void *src_, size_t bytes, bool nt) {
-            if (nt && (reinterpret_cast<uintptr_t>(d) & 15u) == 0 && bytes % 16 == 0) {
-                for (size_t q = 0; q < bytes; q += 16)
-                    _mm_stream_si128(reinterpret_cast<__m128i *>(static_cast<char *>(d) + q),
-                                     _mm_load_si128(reinterpret_cast<const __m128i *>(static_cast<const char *>(src_) + q)));
-            } else {
-                memcpy(d, src_, bytes);
-            }
-        };
-        for (int64_t t0 = lo; t0 < hi;) {
-            const int64_t t1 = std::min<int64_t>(hi, (t0 / TR + 1) * TR);
-            const int m = (int)(t1 - t0);
-            const bool full = m == TR;
-            memset(tf[5], 0, sizeof(tf[5]) * 2);
-            memset(tb, 0, sizeof(tb));
-            memset(ts, 0, sizeof(ts));
-            for (int q = 0; q < m; ++q) {
-                const int64_t i = t0 + q;
-                const bool skip = c->flags && (c->flags[i] & ADH_FLAG_SKIP);
-                const uint32_t p = skip ? 0u : c->precursor_idx[i];
-                const uint8_t r = skip ? (uint8_t)0 : c->rank[i];
-                tp[q] = p;
-                tr[q] = r;
-                const uint32_t o = off[i - a0];
-                const uint32_t k = std::min<uint32_t>(off[i - a0 + 1] - o, 12u);
-                const __m128 m0 = _mm_load_ps(reinterpret_cast<const float *>(kMask[k]));
-                const __m128 m1 = _mm_load_ps(reinterpret_cast<const float *>(kMask[k] + 4));
-                const __m128 m2 = _mm_load_ps(reinterpret_cast<const float *>(kMask[k] + 8));
-                for (int j = 0; j < 5; ++j) {
-                    const float *sp = src[j] + o;
-                    float *row = tf[j] + q * 12;
-                    _mm_store_ps(row, _mm_and_ps(_mm_loadu_ps(sp), m0));
-                    _mm_store_ps(row + 4, _mm_and_ps(_mm_loadu_ps(sp + 4), m1));
-                    _mm_store_ps(row + 8, _mm_and_ps(_mm_loadu_ps(sp + 8), m2));
-                }
-                const __m128 pv = _mm_castsi128_ps(_mm_set1_epi32((int)p));
-                _mm_store_ps(tf[7] + q * 12, _mm_and_ps(pv, m0));
-                _mm_store_ps(tf[7] + q * 12 + 4, _mm_and_ps(pv, m1));
-                _mm_store_ps(tf[7] + q * 12 + 8, _mm_and_ps(pv, m2));
-                // the library columns of the k filled slots (zeros behind: the buffers were cleared)
-                const LibRec *base = lib + c->frag_start_idx[i];
-                for (uint32_t u = 0; u < k; ++u) {
-                    const int e = q * 12 + (int)u;
-                    const uint16_t sl = src_s[o + u];
-                    const LibRec &l = base[sl - 1];
-                    ts[e] = sl;
-                    tf[5][e] = l.mz_library;
-                    tf[6][e] = l.mz;
-                    tb[0][e] = r;
-                    tb[1][e] = l.position;
-                    tb[2][e] = l.number;
-                    tb[3][e] = l.type;
-                    tb[4][e] = l.charge;
-                    tb[5][e] = l.loss_type;
-                }
-            }
-            const size_t r0 = (size_t)t0 * 12;
-            for (int j = 0; j < 8; ++j) put(dstf[j] + r0, tf[j], (size_t)m * 48, full);
-            for (int j = 0; j < 6; ++j) put(u8col[j] + r0, tb[j], (size_t)m * 12, full);
-            if (slot_out) put(slot_out + r0, ts, (size_t)m * 24, full);
-            put(out->precursor_idx + t0, tp, (size_t)m * 4, full);
-            put(out->rank + t0, tr, (size_t)m, false);  // (16 bytes: a quarter of a line)
-            t0 = t1;
-        }
-        _mm_sfence();
-        return;
-    }
-    // any other width: plain loops
-    for (int64_t i = lo; i < hi; ++i) {
-        const bool skip = c->flags && (c->flags[i] & ADH_FLAG_SKIP);
-        const uint32_t p = skip ? 0u : c->precursor_idx[i];
-        const uint8_t r = skip ? (uint8_t)0 : c->rank[i];
-        out->precursor_idx[i] = p;
-        out->rank[i] = r;
-        const uint32_t o = off[i - a0];
-        const int k = (int)std::min<uint32_t>(off[i - a0 + 1] - o, (uint32_t)top_k);
-        const size_t r0 = (size_t)i * (size_t)top_k;
-        const LibRec *base = lib + c->frag_start_idx[i];
-        int t = 0;
-        for (; t < k; ++t) {
-            const size_t d = r0 + (size_t)t;
-            const uint16_t s = src_s[o + t];
-            const LibRec &l = base[s - 1];
-            for (int j = 0; j < 5; ++j) dst[j][d] = src[j][o + t];
-            if (slot_out) slot_out[d] = s;
-            out->fragment_precursor_idx[d] = p;
-            out->fragment_rank[d] = r;
-            out->fragment_mz_library[d] = l.mz_library;
-            out->fragment_mz[d] = l.mz;
-            out->fragment_position[d] = l.position;
-            out->fragment_number[d] = l.number;
-            out->fragment_type[d] = l.type;
-            out->fragment_charge[d] = l.charge;
-            out->fragment_loss_type[d] = l.loss_type;
-        }
-        const size_t rest = (size_t)(top_k - t);
-        if (!rest) continue;
-        const size_t d = r0 + (size_t)t;
-        for (int j = 0; j < 5; ++j) memset(dst[j] + d, 0, rest * 4);
-        if (slot_out) memset(slot_out + d, 0, rest * 2);
-        memset(out->fragment_precursor_idx + d, 0, rest * 4);
-        memset(out->fragment_mz_library + d, 0, rest * 4);
-        memset(out->fragment_mz + d, 0, rest * 4);
-        for (int j = 0; j < 6; ++j) memset(u8col[j] + d, 0, rest);
-    }
-}
-
 // this rank's share of the host: at most 16 threads, and of the cores this process may use (host_cpu_budget: quota,
 // affinity, hardware) only the LOCAL_WORLD_SIZE-th part - the ranks of a node run side by side under ONE quota
 int host_thread_share() {
@@ -447,6 +397,18 @@ bool compact_copy_out_pays(int64_t n) {
     int64_t least_rows = 1000000;
     if (const char *env = getenv("ADH_COMPACT_MIN_ROWS")) least_rows = atoll(env);
     return host_thread_share() >= 12 && n >= least_rows;
+}
+
+// Do the packed blocks of that copy-out carry fragment_intensity and fragment_correlation as streams of their non-zero
+// words (the sparse-slot wire: SparseBlock)?  1.47 of the 5 float words of a filled slot are zeros on the headline, 9 %
+// of the call's bytes on the link; the host team reads fewer bytes and writes the same ones.  That pays where the call
+// waits for the link: tables of ADH_SPARSE_SLOTS_MIN_ROWS rows (default 1 000 000) and more.  ADH_SPARSE_SLOTS=1 / =0
+// forces it on / off; it only ever applies to a call that takes the compacted copy-out.
+bool sparse_slots_pay(int64_t n) {
+    if (const char *env = getenv("ADH_SPARSE_SLOTS")) return atoi(env) != 0;
+    int64_t least_rows = 1000000;
+    if (const char *env = getenv("ADH_SPARSE_SLOTS_MIN_ROWS")) least_rows = atoll(env);
+    return n >= least_rows;
 }
 
 // The hand-off of landed blocks to a host team (the compacted copy-outs).  The enqueue thread only appends the event
@@ -529,6 +491,13 @@ int grow_scan_scratch(void **p, size_t *bytes, int64_t items, hipStream_t st) {
     HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, (Word *)nullptr, (Word *)nullptr, (int)items, st));
     return grow_device(p, bytes, need, 256);
 }
+// ... and of the scan over the four counts of the sparse-slot wire
+int grow_slot_cnt_scratch(void **p, size_t *bytes, int64_t items, hipStream_t st) {
+    size_t need = 0;
+    HIP_TRY(hipcub::DeviceScan::ExclusiveScan(nullptr, need, (SlotCnt *)nullptr, (SlotCnt *)nullptr, SlotCntSum(),
+                                              SlotCnt{0, 0, 0, 0}, (int)items, st));
+    return grow_device(p, bytes, need, 256);
+}
 
 // has the caller passed every array of a compact output?
 bool compact_output_complete(const adh_compact_output_t *o) {
@@ -580,6 +549,7 @@ struct PipelineTrace {
     // and thread: each thread writes its own)
     int T = 0;
     std::vector<double> tot_seen, told, stripe_done, stripe_took;
+    std::vector<uint64_t> blk_bytes, blk_dense_bytes;  // a block's copy, and what the dense block (PadBlock) of the chunk holds
 
     static double now() {
         return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -594,6 +564,7 @@ struct PipelineTrace {
         if (!events) return;
         T = threads;
         tot_seen.assign((size_t)n_chunks, 0.0), told.assign((size_t)n_chunks, 0.0);
+        blk_bytes.assign((size_t)n_chunks, 0), blk_dense_bytes.assign((size_t)n_chunks, 0);
         stripe_done.assign((size_t)n_chunks * (size_t)T, 0.0), stripe_took.assign((size_t)n_chunks * (size_t)T, 0.0);
     }
     hipEvent_t stamp(hipStream_t st) const {  // (a time stamp on a stream; NULL with the switch off)
@@ -608,6 +579,9 @@ struct PipelineTrace {
         if (events) spans.push_back(stamp(so)), span_bytes.back() = d2h_bytes - span_bytes.back();
     }
     void total_seen(int64_t ci) { if (events) tot_seen[(size_t)ci] = since(); }
+    void block_sent(int64_t ci, uint64_t bytes, uint64_t dense) {
+        if (events && (size_t)ci < blk_bytes.size()) blk_bytes[(size_t)ci] = bytes, blk_dense_bytes[(size_t)ci] = dense;
+    }
     void team_told(int64_t ci) { if (events) told[(size_t)ci] = since(); }
     double stripe_begin() const { return events ? now() : 0.0; }
     void stripe_end(int64_t ci, int w, double t_in) {
@@ -648,8 +622,11 @@ struct PipelineTrace {
                 took_hi = std::max(took_hi, stripe_took[ci * (size_t)T + (size_t)w]);
             }
             fprintf(stderr, "[adh]   block %zu: total seen %.2f ms after the call began, copy ended %.2f, team told %.2f (lag %.2f), "
-                            "last thread done %.2f (a stripe took %.2f - %.2f ms)\n",
+                            "last thread done %.2f (a stripe took %.2f - %.2f ms)",
                     ci, tot_seen[ci], last_landed, told[ci], told[ci] - last_landed, team_done, took_lo, took_hi);
+            if (ci < blk_bytes.size() && blk_bytes[ci])
+                fprintf(stderr, "; %.2f MB copied, %.2f MB as a dense block", (double)blk_bytes[ci] / 1e6, (double)blk_dense_bytes[ci] / 1e6);
+            fprintf(stderr, "\n");
         }
         if (packed && start)
             fprintf(stderr, "[adh]   tail: the call returns %.2f ms after it began, %.2f ms after the last copy ended\n", t_ret,
@@ -831,6 +808,11 @@ struct PlainCopyOut : CopyOut {
 struct PackedCopyOut : PlainCopyOut {
     const PadLayout lay;
     const int T;
+    const bool sparse;  // the sparse-slot wire (sparse_slots_pay): blocks are SparseBlocks, four totals per chunk
+    // the smallest slot value that leaves no room for the flags (ADH_DEBUG_SPARSE_BIG_FROM, developer switch: a
+    // smaller one, so that a test reaches the dense block of such a chunk)
+    uint32_t big_from = kSlotFlagFrom;
+    uint64_t wire_slots = 0, wire_nz_i = 0, wire_nz_c = 0;  // (the call's totals, for the ADH_DEBUG_TIMING line)
     unsigned char *dev_blocks = nullptr, *host_blocks = nullptr;
     // A chunk is handed out in tiles of kFillTile rows (on multiples of it: fill_host_rows works in aligned groups of 16
     // rows), claimed one by one.  With one fixed stripe per thread a chunk took as long as its slowest thread: of the 16
@@ -842,16 +824,27 @@ struct PackedCopyOut : PlainCopyOut {
     BlockHandoff handoff;
     HandoffTeam team{handoff};
     PackedCopyOut(const CopyOut &call, adh_output_t *out_)
-        : PlainCopyOut(call, out_, true), lay(n, top_k, n_chunks), T(host_threads_for(n)), next_tile((size_t)n_chunks),
-          handoff(n_chunks, h->device) {}
+        : PlainCopyOut(call, out_, true), lay(n, top_k, n_chunks), T(host_threads_for(n)), sparse(sparse_slots_pay(n)),
+          next_tile((size_t)n_chunks), handoff(n_chunks, h->device) {}
 
     int prepare() override {
         int rc = PlainCopyOut::prepare();
         if (rc == ADH_OK) rc = grow_device(&h->cmp_dev, &h->cmp_dev_bytes, lay.total, lay.total / 8);
         if (rc == ADH_OK) rc = grow_pinned(&h->cmp_host, &h->cmp_host_bytes, lay.total, lay.total / 8);
         if (rc != ADH_OK) return rc;
-        if (!h->cmp_tot_pinned) HIP_TRY(hipHostMalloc((void **)&h->cmp_tot_pinned, 4096 * 4, hipHostMallocDefault));
-        rc = grow_scan_scratch<uint32_t>(&h->cmp_scan, &h->cmp_scan_bytes, longest_chunk() + 1, h->stream);
+        if (!h->cmp_tot_pinned) HIP_TRY(hipHostMalloc((void **)&h->cmp_tot_pinned, 4096 * 16, hipHostMallocDefault));
+        if (sparse) {
+            if (const char *env = getenv("ADH_DEBUG_SPARSE_BIG_FROM")) {  // (anything but a number in 1 .. 0x4000 is ignored)
+                char *end = nullptr;
+                const long v = strtol(env, &end, 0);
+                if (end != env && *end == '\0' && v >= 1 && v <= (long)kSlotFlagFrom) big_from = (uint32_t)v;
+            }
+            const size_t cnt_bytes = (size_t)(longest_chunk() + 1) * sizeof(SlotCnt);
+            rc = grow_device(&h->cmp_cnt, &h->cmp_cnt_bytes, cnt_bytes, cnt_bytes / 8);
+            if (rc == ADH_OK) rc = grow_slot_cnt_scratch(&h->cmp_scan, &h->cmp_scan_bytes, longest_chunk() + 1, h->stream);
+        } else {
+            rc = grow_scan_scratch<uint32_t>(&h->cmp_scan, &h->cmp_scan_bytes, longest_chunk() + 1, h->stream);
+        }
         if (rc != ADH_OK) return rc;
         dev_blocks = static_cast<unsigned char *>(h->cmp_dev), host_blocks = static_cast<unsigned char *>(h->cmp_host);
         for (std::atomic<int64_t> &next : next_tile) next.store(0, std::memory_order_relaxed);
@@ -866,7 +859,7 @@ struct PackedCopyOut : PlainCopyOut {
             const int64_t t = a / kFillTile + next_tile[(size_t)ci].fetch_add(1, std::memory_order_relaxed);
             const int64_t lo = std::max(a, t * kFillTile), hi = std::min(b, (t + 1) * kFillTile);
             if (lo >= b) break;
-            fill_host_rows(h, c, out, host_blocks + lay.base(a, ci), b - a, a, lo, hi);
+            fill_host_rows(h->h_lib.data(), c, out, host_blocks + lay.base(a, ci), b - a, a, lo, hi, sparse);
         }
         trace.stripe_end(ci, w, t_in);
     }
@@ -878,6 +871,19 @@ struct PackedCopyOut : PlainCopyOut {
         const int64_t a = cut[(size_t)ci], nr = cut[(size_t)ci + 1] - a;
         hipStream_t sk = h->stream;
         unsigned char *blk = dev_blocks + lay.base(a, ci);
+        if (sparse) {
+            SlotCnt *cnt = static_cast<SlotCnt *>(h->cmp_cnt);
+            hipLaunchKernelGGL(adh_slot_count_nz_kernel, dim3((unsigned)((nr + 256) / 256)), dim3(256), 0, sk, dev.fragment_lib_slot,
+                               reinterpret_cast<const uint32_t *>(dev.fragment_intensity),
+                               reinterpret_cast<const uint32_t *>(dev.fragment_correlation), a, nr, top_k, big_from, cnt);
+            size_t scan_bytes = h->cmp_scan_bytes;
+            HIP_TRY(hipcub::DeviceScan::ExclusiveScan(h->cmp_scan, scan_bytes, cnt, cnt, SlotCntSum(), SlotCnt{0, 0, 0, 0},
+                                                      (int)(nr + 1), sk));
+            hipLaunchKernelGGL(adh_pad_pack_sparse_kernel, dim3((unsigned)((nr * top_k + 255) / 256)), dim3(256), 0, sk, dev, a, nr,
+                               top_k, cnt, blk, h->cmp_tot_pinned + 4 * ci);
+            HIP_TRY(hipGetLastError());
+            return record(sk, tot_ready);  // (when the totals can be read)
+        }
         uint32_t *d_off = reinterpret_cast<uint32_t *>(blk);
         hipLaunchKernelGGL(adh_slot_count_kernel, dim3((unsigned)((nr + 256) / 256)), dim3(256), 0, sk, dev.fragment_lib_slot, a,
                            nr, top_k, d_off);
@@ -895,10 +901,18 @@ struct PackedCopyOut : PlainCopyOut {
         const int64_t a = cut[(size_t)ci], b = cut[(size_t)ci + 1];
         HIP_TRY(hipEventSynchronize(tot_ready[(size_t)ci]));
         trace.total_seen(ci);
-        const PadBlock L((uint64_t)(b - a), (uint64_t)h->cmp_tot_pinned[ci]);
         const size_t base = lay.base(a, ci);
-        h->d2h_bytes += L.total;
-        return send_block(handoff, host_blocks + base, dev_blocks + base, L.total);
+        size_t bytes = 0;
+        if (sparse) {
+            const uint32_t *tot = h->cmp_tot_pinned + 4 * ci;  // (format, slots, non-zero intensity / correlation words)
+            bytes = SparseBlock((uint64_t)a, (uint64_t)(b - a), tot[1], tot[2], tot[3], tot[0] == kWireSparse).total;
+            wire_slots += tot[1], wire_nz_i += tot[0] == kWireSparse ? tot[2] : tot[1], wire_nz_c += tot[0] == kWireSparse ? tot[3] : tot[1];
+        } else {
+            bytes = PadBlock((uint64_t)(b - a), (uint64_t)h->cmp_tot_pinned[ci]).total;
+        }
+        h->d2h_bytes += bytes;
+        trace.block_sent(ci, bytes, PadBlock((uint64_t)(b - a), sparse ? h->cmp_tot_pinned[4 * ci + 1] : h->cmp_tot_pinned[ci]).total);
+        return send_block(handoff, host_blocks + base, dev_blocks + base, bytes);
     }
     // The packed block of a chunk goes AHEAD of its valid / features rows (from chunk 1 on: the link is busy with chunk
     // ci - 1 when the kernels of chunk ci end, so that the host enqueues both only once it knows the block's length
@@ -924,6 +938,9 @@ struct PackedCopyOut : PlainCopyOut {
         team.join_all();
         if (trace.timing)
             fprintf(stderr, "[adh]   compacted copy-out: host team done %.2f ms after the call began (%d threads)\n", trace.since(), T);
+        if (trace.timing && sparse)
+            fprintf(stderr, "[adh]   sparse-slot wire: %llu filled slots, %llu intensity words and %llu correlation words sent\n",
+                    (unsigned long long)wire_slots, (unsigned long long)wire_nz_i, (unsigned long long)wire_nz_c);
         return ADH_OK;
     }
 };

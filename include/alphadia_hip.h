@@ -217,6 +217,11 @@ int adh_stage_fragments(adh_handle_t *handle, const adh_fragments_t *fragments);
  * download).  Replaces the pjit loop `_process_score_groups`
  * (scoring.py:114-137,634-643), i.e. ScoreGroup.process -> Candidate.process
  * for every candidate.  `out` buffers are zero-filled by the call.
+ * How the tables cross PCIe is a matter of policy (INTEGRATION.md lists every switch): tables of
+ * ADH_COMPACT_MIN_ROWS rows and more send the filled fragment slots as one packed block per chunk
+ * (ADH_COMPACT_COPY_OUT=1 / =0 forces that on / off), and in such a block tables of ADH_SPARSE_SLOTS_MIN_ROWS
+ * rows and more (default 1 000 000) send fragment_intensity and fragment_correlation as streams of their non-zero
+ * words (ADH_SPARSE_SLOTS=1 / =0 forces that on / off).  The caller's tables hold the same bytes either way.
  */
 int adh_score_candidates(adh_handle_t *handle, const adh_candidates_t *candidates,
                          const adh_scoring_config_t *config, adh_output_t *out);
