@@ -738,7 +738,10 @@ __device__ __forceinline__ void adh_im_profiles_body(
         sm += P[RC - 1];
         sm += P[RC];
         sm += P[RC + 1];
-        const double cn = (double)sm / 3.0;
+        // (the mean is over the cycles the slice centre - 1 : centre + 2 holds: three, but two in a box of two cycles and
+        // one in a box of one - a launch may hold such boxes whatever its longest one)
+        const int n_win = max(min(F, F / 2 + 2) - max(F / 2 - 1, 0), 1);
+        const double cn = (double)sm / (double)n_win;
         const bool cpos = cn > 0;
         // median over fragments per cycle (scoring_utils.py:120-152): 16 x 16 transposes via LDS
 #pragma unroll

@@ -304,6 +304,15 @@ void get_dense_timstof(const adh_timstof_t &d, int64_t frame_start, int64_t fram
                         int64_t frame = d.push_indices[idx] / S_max, scan = d.push_indices[idx] % S_max;
                         int cyc = (int)((frame - d.zeroth_frame) / L - c0);
                         int rs = (int)(scan - scan_start);
+                        /* A frame_stop that is not on a cycle boundary (clipped to the last frame of a run that ends
+                         * inside a cycle) leaves pushes of cycle F in the query.  The reference indexes its
+                         * dense_output[..., precursor_cycle_len] with them (bruker_jit.py:436-451, 486-501): an
+                         * IndexError in NumPy, a write past the array under Numba.  Here, as in the kernels
+                         * (adh_gather_im.hip: push_hi), the events of the incomplete cycle are left out. */
+                        if (cyc >= F) {
+                            ++idx;
+                            continue;
+                        }
                         float acc_int = out.at(0, j, rel[i], rs, cyc);
                         float acc_d1 = out.at(1, j, rel[i], rs, cyc);
                         int64_t ni = d.intensity_values[idx];

@@ -1391,7 +1391,55 @@ def golden_timstof_cycles():
     print(f"{path}: {v.sum()}/{len(v)} valid, n_observations {hist}, {os.path.getsize(path)/2**20:.2f} MiB")
 
 
+def golden_boxes_timstof():
+    """Full scoring (the settings of tests/box_sweep_im.py) of the thinned ion-mobility shape sweep: boxes of 2 ... 36
+    cycles x 2 ... 48 scans at every edge of the run, centres on the first, middle and last cycle / scan, one to four
+    observations (box_sweep_im.golden_spec, cycle "mixed").  The path of golden_timstof()."""
+    import box_sweep_im as bi
+
+    case = bi.sweep_case(golden=True)
+    d = {"tims_" + c: getattr(case.dia, c) for c in TIMS_COLS}
+    d["tims_scan_max_index"] = np.asarray(case.dia.scan_max_index)
+    d["tims_zeroth_frame"] = np.asarray(case.dia.zeroth_frame)
+    for c in FRAG_COLS:
+        d["frag_" + c] = case.library.fragment_df[c].values
+    for c in PREC_NUM_COLS:
+        d["prec_" + c] = case.library.precursor_df[c].values
+    for c in CAND_COLS:
+        d["cand_" + c] = case.candidates_df[c].values
+    cfg = CandidateScoringConfig()
+    cfg.update(bi.HANDLER)
+    dia = DuckTims(case.dia)
+    cs = ref_scoring.CandidateScoring(
+        dia_data=dia, precursors_flat=case.library.precursor_df.copy(), fragments_flat=case.library.fragment_df.copy(),
+        rt_column="rt_library", mobility_column="mobility_library", precursor_mz_column="mz_library",
+        fragment_mz_column="mz_library", config=cfg,
+    )
+    cands = case.candidates_df.copy()
+    fragment_container = cs.assemble_fragments()
+    sgc = cs.assemble_score_group_container(cands)
+    out = OutputPsmDF(sgc.get_candidate_count(), cs.config.top_k_fragments)
+    ref_scoring._process_score_groups(range(len(sgc)), sgc, out, fragment_container, dia.to_jitclass(),
+                                      cs.config.to_jitclass(), cs.quadrupole_calibration.jit, False)
+    d.update(out_to_dict(out))
+    cfgj = cfg.to_jitclass()
+    for kk in ("collect_fragments score_grouped exclude_shared_ions top_k_fragments top_k_isotopes "
+               "reference_channel quant_window quant_all precursor_mz_tolerance "
+               "fragment_mz_tolerance experimental_xic").split():
+        d["cfg_" + kk] = np.asarray(getattr(cfgj, kk))
+    d["caveat"] = np.asarray(CAVEAT)
+    v = np.asarray(out.valid).astype(bool)
+    nobs = np.asarray(out.features)[v][:, 17]
+    path = os.path.join(OUT_DIR, "scoring_boxes_timstof.npz")
+    np.savez_compressed(path, **d)
+    print(f"{path}: {v.sum()}/{len(v)} valid, n_observations {dict(zip(*np.unique(nobs, return_counts=True)))}, "
+          f"{os.path.getsize(path)/2**20:.2f} MiB")
+
+
 if __name__ == "__main__":
+    if "--boxes-timstof-only" in sys.argv:
+        golden_boxes_timstof()
+        sys.exit(0)
     if "--timstof-only" in sys.argv:
         golden_timstof()
         sys.exit(0)
@@ -1459,3 +1507,4 @@ if __name__ == "__main__":
     golden_get_dense_cycles()
     golden_selection_cycles()
     golden_timstof_cycles()
+    golden_boxes_timstof()
