@@ -735,6 +735,22 @@ PG_PROTOTYPES = {
 }
 
 
+# ... and of the protein-group FDR (adh_pfdr_*, adh_protein_fdr.hip)
+_f64p = C.POINTER(C.c_double)
+PFDR_PROTOTYPES = {
+    "adh_pfdr_create": [C.c_void_p, C.POINTER(C.c_void_p)],
+    "adh_pfdr_destroy": [C.c_void_p],
+    "adh_pfdr_features": [C.c_void_p, C.c_int64, _i32p, C.POINTER(C.c_uint8), C.POINTER(C.c_int64), _i32p, _i32p,
+                          C.c_void_p, C.c_int32, C.POINTER(C.c_int64)],
+    "adh_pfdr_read_features": [C.c_void_p, _i32p, C.POINTER(C.c_uint8), _f64p, _i32p],
+    "adh_pfdr_fit_begin": [C.c_void_p, C.c_int64, _f64p, C.POINTER(C.c_uint8), _f64p],
+    "adh_pfdr_epoch": [C.c_void_p, _i32p, C.c_int32, _f64p, _f64p],
+    "adh_pfdr_predict": [C.c_void_p, C.c_int64, _f64p, _f64p],
+    "adh_pfdr_gather": [C.c_void_p, C.c_int64, _f64p, _f64p],
+    "adh_pfdr_time_ms": [C.c_void_p, _f64p, _f64p, _f64p, _f64p],
+}
+
+
 # ... and of the library staged from its columns and calibrated in HBM (adh_stage_lib.hip, adh_calibration.hip)
 STAGE_LIB_PROTOTYPES = {
     "adh_calibrate_staged_fragments": [C.c_void_p, C.POINTER(LoessModel), C.POINTER(C.c_double)],
@@ -752,9 +768,9 @@ PLAN_PROTOTYPES = {
 
 def declare(lib) -> None:
     """Argument types of the entries listed in RESIDENT_PROTOTYPES, STAGE_PART_PROTOTYPES, APPEND_PROTOTYPES,
-    QUANT_PROTOTYPES, PG_PROTOTYPES, STAGE_LIB_PROTOTYPES and PLAN_PROTOTYPES (the others are called with explicit casts)."""
+    QUANT_PROTOTYPES, PG_PROTOTYPES, PFDR_PROTOTYPES, STAGE_LIB_PROTOTYPES and PLAN_PROTOTYPES (the others are called with explicit casts)."""
     for name, argtypes in {**RESIDENT_PROTOTYPES, **STAGE_PART_PROTOTYPES, **APPEND_PROTOTYPES, **QUANT_PROTOTYPES,
-                           **PG_PROTOTYPES, **STAGE_LIB_PROTOTYPES, **PLAN_PROTOTYPES}.items():
+                           **PG_PROTOTYPES, **PFDR_PROTOTYPES, **STAGE_LIB_PROTOTYPES, **PLAN_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = C.c_int

@@ -1988,3 +1988,4 @@ int adh_fragcomp_stats(adh_handle_t *h, double *kernel_ms, int64_t *pairs, int64
 #include "adh_resident_append.hip"
 #include "adh_quant.hip"
 #include "adh_grouping.hip"
+#include "adh_protein_fdr.hip"

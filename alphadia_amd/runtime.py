@@ -102,6 +102,15 @@ EXPORTED_SYMBOLS = [
     "adh_pg_filter",
     "adh_pg_stats",
     "adh_pg_time_ms",
+    "adh_pfdr_create",
+    "adh_pfdr_destroy",
+    "adh_pfdr_features",
+    "adh_pfdr_read_features",
+    "adh_pfdr_fit_begin",
+    "adh_pfdr_epoch",
+    "adh_pfdr_predict",
+    "adh_pfdr_gather",
+    "adh_pfdr_time_ms",
 ]
 
 
@@ -1182,6 +1191,11 @@ class Context:
         """An ``adh_pg_t``: the greedy set cover of protein inference, one cover per connected component."""
         return DeviceProteinGroups(self)
 
+    # -- protein-group FDR ------------------------------------------------
+    def protein_fdr(self) -> DeviceProteinFdr:
+        """An ``adh_pfdr_t``: group features, the classifier and the gather of the protein-group FDR."""
+        return DeviceProteinFdr(self)
+
 
 class DeviceMlp:
     """An ``adh_mlp_t``: the classifier network with its parameters, optimiser moments and the
@@ -1485,6 +1499,106 @@ class DeviceProteinGroups:
         a, b, c = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
         _check(lib.adh_pg_time_ms(self._g, C.byref(a), C.byref(b), C.byref(c)), "adh_pg_time_ms")
         return float(a.value), float(b.value), float(c.value)
+
+
+class DeviceProteinFdr:
+    """An ``adh_pfdr_t``: the (pg, decoy) group features of a precursor table, sklearn's MLPClassifier trained one
+    epoch per launch, and the gather of a per-group value to the rows (include/alphadia_hip.h: adh_pfdr_*)."""
+
+    N_FEATURES = 7
+    N_PARAMS = 901
+
+    def __init__(self, ctx: Context):
+        self._ctx = ctx  # keeps the handle alive
+        self._g = C.c_void_p()
+        _check(lib.adh_pfdr_create(ctx._h, C.byref(self._g)), "adh_pfdr_create")
+        self.n_rows = self.n_groups = self.n_train = 0
+
+    def close(self):
+        if self._g:
+            lib.adh_pfdr_destroy(self._g)
+            self._g = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _p(a, t):
+        return a.ctypes.data_as(C.POINTER(t))
+
+    def features(self, pg, decoy, precursor_idx, sequence, run, proba, with_row_group: bool = False):
+        """``(group_pg, group_decoy, features [groups, 7])`` of ``adh_pfdr_features``, the groups ascending by
+        (pg, decoy); with ``with_row_group`` also the group of every row (-1: none)."""
+        pg, seq, rn = (_abi.as_c(x, np.int32) for x in (pg, sequence, run))
+        de = _abi.as_c(decoy, np.uint8)
+        pi = _abi.as_c(precursor_idx, np.int64)
+        pr = np.asarray(proba)
+        pr = np.ascontiguousarray(pr, dtype=np.float32 if pr.dtype == np.float32 else np.float64)
+        n = pg.shape[0]
+        if pg.ndim != 1 or any(a.shape != (n,) for a in (seq, rn, de, pi, pr)):
+            raise ValueError("features: one value of every column per row")
+        groups = C.c_int64(0)
+        _check(lib.adh_pfdr_features(self._g, n, self._p(pg, C.c_int32), self._p(de, C.c_uint8), self._p(pi, C.c_int64),
+                                     self._p(seq, C.c_int32), self._p(rn, C.c_int32), C.c_void_p(pr.ctypes.data),
+                                     int(pr.dtype == np.float64), C.byref(groups)), "adh_pfdr_features")
+        self.n_rows, self.n_groups = n, int(groups.value)
+        gpg = np.empty(self.n_groups, np.int32)
+        gde = np.empty(self.n_groups, np.uint8)
+        x = np.empty((self.n_groups, self.N_FEATURES), np.float64)
+        row_group = np.empty(n, np.int32) if with_row_group else None
+        _check(lib.adh_pfdr_read_features(self._g, self._p(gpg, C.c_int32), self._p(gde, C.c_uint8), self._p(x, C.c_double),
+                                          self._p(row_group, C.c_int32) if with_row_group else None),
+               "adh_pfdr_read_features")
+        return (gpg, gde, x, row_group) if with_row_group else (gpg, gde, x)
+
+    def fit_begin(self, x_train, y_train, params) -> None:
+        """``adh_pfdr_fit_begin``: the scaled training matrix, its 0 / 1 labels and the 901 initial parameters."""
+        x = _abi.as_c(x_train, np.float64)
+        y = _abi.as_c(y_train, np.uint8)
+        p = _abi.as_c(params, np.float64)
+        if x.ndim != 2 or x.shape[1] != self.N_FEATURES or y.shape != (x.shape[0],) or p.shape != (self.N_PARAMS,):
+            raise ValueError("fit_begin: x [rows, 7], one label per row, 901 parameters")
+        _check(lib.adh_pfdr_fit_begin(self._g, x.shape[0], self._p(x, C.c_double), self._p(y, C.c_uint8),
+                                      self._p(p, C.c_double)), "adh_pfdr_fit_begin")
+        self.n_train = x.shape[0]
+
+    def epoch(self, order, step_size) -> float:
+        """``adh_pfdr_epoch``: one epoch over the rows in ``order``, one Adam step size per batch; the epoch's loss."""
+        o = _abi.as_c(order, np.int32)
+        lr = _abi.as_c(step_size, np.float64)
+        if o.shape != (self.n_train,) or lr.ndim != 1:
+            raise ValueError("epoch: one position per training row, one step size per batch")
+        loss = C.c_double(0.0)
+        _check(lib.adh_pfdr_epoch(self._g, self._p(o, C.c_int32), lr.shape[0], self._p(lr, C.c_double), C.byref(loss)),
+               "adh_pfdr_epoch")
+        return float(loss.value)
+
+    def predict(self, x) -> np.ndarray:
+        x = _abi.as_c(x, np.float64)
+        if x.ndim != 2 or x.shape[1] != self.N_FEATURES:
+            raise ValueError("predict: x [rows, 7]")
+        out = np.empty(x.shape[0], np.float64)
+        _check(lib.adh_pfdr_predict(self._g, x.shape[0], self._p(x, C.c_double), self._p(out, C.c_double)),
+               "adh_pfdr_predict")
+        return out
+
+    def gather(self, group_value) -> np.ndarray:
+        """``adh_pfdr_gather``: every row's group value, NaN for the rows of no group."""
+        v = _abi.as_c(group_value, np.float64)
+        if v.shape != (self.n_groups,):
+            raise ValueError("gather: one value per group of the last features call")
+        out = np.empty(self.n_rows, np.float64)
+        _check(lib.adh_pfdr_gather(self._g, v.shape[0], self._p(v, C.c_double), self._p(out, C.c_double)), "adh_pfdr_gather")
+        return out
+
+    def time_ms(self) -> tuple[float, float, float, float]:
+        """HIP-event times (ms) of the features, all epochs of the last fit, the last predict and the last gather."""
+        t = [C.c_double(0.0) for _ in range(4)]
+        _check(lib.adh_pfdr_time_ms(self._g, *(C.byref(x) for x in t)), "adh_pfdr_time_ms")
+        return tuple(float(x.value) for x in t)
 
 
 _contexts: dict[int, Context] = {}

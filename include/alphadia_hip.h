@@ -893,6 +893,47 @@ int adh_pg_stats(adh_pg_t *pg, int32_t *n_components, int32_t *n_large, int32_t 
  * last filter */
 int adh_pg_time_ms(adh_pg_t *pg, double *label_ms, double *cover_ms, double *filter_ms);
 
+/* ------------------------------------------------------------------------------------------
+ * Protein-group FDR: perform_protein_fdr (outputtransform/protein_fdr.py:15-112).  The host
+ * factorises the strings: pg[i] is the rank of row i's protein group among the sorted distinct
+ * groups (-1: the row has none), sequence[i] and run[i] are codes of any numbering.  The device
+ * computes the features of every (pg, decoy) group, trains sklearn's MLPClassifier (float64,
+ * 7 -> 100 ReLU -> 1 logistic, Adam) one epoch per call from parameters and row orders the host
+ * draws, scores all groups, and hands a per-group value back to the rows.
+ * ------------------------------------------------------------------------------------------ */
+
+typedef struct adh_pfdr adh_pfdr_t;
+
+int adh_pfdr_create(adh_handle_t *handle, adh_pfdr_t **pfdr);
+int adh_pfdr_destroy(adh_pfdr_t *pfdr);
+/* Groups the n_rows rows by (pg, decoy), ascending, and keeps per group in HBM: count, mean of proba, distinct
+ * sequences, distinct precursor_idx, distinct runs, minimum and maximum of proba - the column order of the
+ * reference's feature matrix.  proba is float32 (proba_is_f64 == 0) or float64; the mean is np.add.reduce over the
+ * group's rows in table order (chunks of 8 192 elements added in order, pairwise inside a chunk) divided by the
+ * count, both in proba's own type.  A pg code of 2^30 or more,
+ * a decoy flag above 1 or a non-finite proba in a row that has a pg fail with ADH_ERR_INVALID_ARGUMENT /
+ * ADH_ERR_UNSUPPORTED before anything is launched. */
+int adh_pfdr_features(adh_pfdr_t *pfdr, int64_t n_rows, const int32_t *pg, const uint8_t *decoy,
+                      const int64_t *precursor_idx, const int32_t *sequence, const int32_t *run, const void *proba,
+                      int32_t proba_is_f64, int64_t *n_groups);
+/* group_pg[n_groups], group_decoy[n_groups], features[n_groups * 7] (row-major) and, unless NULL,
+ * row_group[n_rows] (-1: no group) of the last adh_pfdr_features */
+int adh_pfdr_read_features(adh_pfdr_t *pfdr, int32_t *group_pg, uint8_t *group_decoy, double *features,
+                           int32_t *row_group);
+/* Stages x[n_train * 7] (row-major, scaled), the labels y[n_train] (0 / 1) and the 901 initial parameters
+ * (W1 [7][100] row-major, b1 [100], W2 [100], b2); zeroes the Adam moments. */
+int adh_pfdr_fit_begin(adh_pfdr_t *pfdr, int64_t n_train, const double *x, const uint8_t *y, const double *params);
+/* One epoch in one launch on one workgroup: batches of min(200, n_train) rows in the order order[n_train] gives,
+ * step k with Adam's step size step_size[k] (n_steps = the number of batches); *loss is the epoch's mean loss
+ * (log-loss on clipped probabilities + 0.5 alpha |W|^2 / batch rows, alpha = 1e-4).  Every sum runs in a fixed order. */
+int adh_pfdr_epoch(adh_pfdr_t *pfdr, const int32_t *order, int32_t n_steps, const double *step_size, double *loss);
+/* proba[n]: the network's output for x[n * 7] under the current parameters; a row's value depends on that row only */
+int adh_pfdr_predict(adh_pfdr_t *pfdr, int64_t n, const double *x, double *proba);
+/* row_value[n_rows] = group_value[group of the row], NaN for a row of no group (the last adh_pfdr_features) */
+int adh_pfdr_gather(adh_pfdr_t *pfdr, int64_t n_groups, const double *group_value, double *row_value);
+/* HIP-event times (ms): the last adh_pfdr_features, all epochs since adh_pfdr_fit_begin, the last predict and gather */
+int adh_pfdr_time_ms(adh_pfdr_t *pfdr, double *features_ms, double *epochs_ms, double *predict_ms, double *gather_ms);
+
 #ifdef __cplusplus
 }
 #endif
