@@ -751,6 +751,25 @@ PFDR_PROTOTYPES = {
 }
 
 
+# ... and of the transfer-learning library (adh_tl_*, adh_transfer_library.hip)
+TL_MAX_MATRICES = 4
+TL_QC_SLICE = 512
+TL_PROTOTYPES = {
+    "adh_tl_create": [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)],
+    "adh_tl_destroy": [C.c_void_p],
+    "adh_tl_scatter": [C.c_void_p, C.c_int64, C.c_int64, _i64p, _i32p, _f32p, _f32p, _f32p, _i32p],
+    "adh_tl_update": [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, _i64p, _i64p, _i64p,
+                      C.c_int64, C.POINTER(_f32p), _i64p, _i64p],
+    "adh_tl_read_kept": [C.c_void_p, _i64p, _i64p, _i64p],
+    "adh_tl_read_matrix": [C.c_void_p, C.c_int32, _f32p],
+    "adh_tl_time_ms": [C.c_void_p, _f64p, _f64p, _f64p],
+    "adh_tl_qc": [C.c_void_p, C.c_int64, _i64p, _i64p, C.c_int64, C.c_int32, _f32p, _f32p, C.c_float, C.c_float, C.c_int32,
+                  C.POINTER(C.c_uint8), _i64p, _f64p],
+    "adh_tl_rt_norm": [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                       C.c_void_p, _f64p],
+}
+
+
 # ... and of the library staged from its columns and calibrated in HBM (adh_stage_lib.hip, adh_calibration.hip)
 STAGE_LIB_PROTOTYPES = {
     "adh_calibrate_staged_fragments": [C.c_void_p, C.POINTER(LoessModel), C.POINTER(C.c_double)],
@@ -768,9 +787,9 @@ PLAN_PROTOTYPES = {
 
 def declare(lib) -> None:
     """Argument types of the entries listed in RESIDENT_PROTOTYPES, STAGE_PART_PROTOTYPES, APPEND_PROTOTYPES,
-    QUANT_PROTOTYPES, PG_PROTOTYPES, PFDR_PROTOTYPES, STAGE_LIB_PROTOTYPES and PLAN_PROTOTYPES (the others are called with explicit casts)."""
+    QUANT_PROTOTYPES, PG_PROTOTYPES, PFDR_PROTOTYPES, TL_PROTOTYPES, STAGE_LIB_PROTOTYPES and PLAN_PROTOTYPES (the others are called with explicit casts)."""
     for name, argtypes in {**RESIDENT_PROTOTYPES, **STAGE_PART_PROTOTYPES, **APPEND_PROTOTYPES, **QUANT_PROTOTYPES,
-                           **PG_PROTOTYPES, **PFDR_PROTOTYPES, **STAGE_LIB_PROTOTYPES, **PLAN_PROTOTYPES}.items():
+                           **PG_PROTOTYPES, **PFDR_PROTOTYPES, **TL_PROTOTYPES, **STAGE_LIB_PROTOTYPES, **PLAN_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = C.c_int

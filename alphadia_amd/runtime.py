@@ -111,6 +111,15 @@ EXPORTED_SYMBOLS = [
     "adh_pfdr_predict",
     "adh_pfdr_gather",
     "adh_pfdr_time_ms",
+    "adh_tl_create",
+    "adh_tl_destroy",
+    "adh_tl_scatter",
+    "adh_tl_update",
+    "adh_tl_read_kept",
+    "adh_tl_read_matrix",
+    "adh_tl_time_ms",
+    "adh_tl_qc",
+    "adh_tl_rt_norm",
 ]
 
 
@@ -1196,6 +1205,47 @@ class Context:
         """An ``adh_pfdr_t``: group features, the classifier and the gather of the protein-group FDR."""
         return DeviceProteinFdr(self)
 
+    # -- transfer-learning library ----------------------------------------
+    def transfer_library(self, n_columns: int, n_matrices: int) -> DeviceTransferLibrary:
+        """An empty ``adh_tl_t``: the consensus of the transfer-learning accumulator, ``n_matrices`` dense float32
+        matrices of ``n_columns`` columns."""
+        return DeviceTransferLibrary(self, n_columns, n_matrices)
+
+    def tl_qc(self, frag_start, frag_stop, intensity, correlation, cutoff, ratio, empty_passes: bool):
+        """``adh_tl_qc``: ``(use_for_ms2, masked intensity, blocks on the workgroup path, kernel ms)``; ``intensity``
+        is not modified."""
+        fs, fe = _abi.as_c(frag_start, np.int64), _abi.as_c(frag_stop, np.int64)
+        inten = np.array(intensity, dtype=np.float32, order="C", ndmin=2)
+        corr = _abi.as_c(correlation, np.float32)
+        if corr.shape != inten.shape or fs.ndim != 1 or fe.shape != fs.shape:
+            raise ValueError("tl_qc: intensity and correlation of one shape, one start and stop per precursor")
+        use = np.zeros(fs.shape[0], np.uint8)
+        large, ms = C.c_int64(0), C.c_double(0.0)
+        p = lambda a, t: a.ctypes.data_as(C.POINTER(t))  # noqa: E731
+        _check(lib.adh_tl_qc(self._h, fs.shape[0], p(fs, C.c_int64), p(fe, C.c_int64), inten.shape[0], inten.shape[1],
+                             p(inten, C.c_float), p(corr, C.c_float), float(cutoff), float(ratio), int(bool(empty_passes)),
+                             p(use, C.c_uint8), C.byref(large), C.byref(ms)), "adh_tl_qc")
+        return use.astype(bool), inten, int(large.value), float(ms.value)
+
+    def tl_rt_norm(self, rt_observed, rt_calibrated=None, rt_library=None):
+        """``adh_tl_rt_norm``: ``(rt_norm, kernel ms)``; max normalisation when ``rt_calibrated`` is None."""
+        def col(a):
+            a = np.asarray(a)
+            return np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+
+        obs = col(rt_observed)
+        delta = rt_calibrated is not None
+        cal, lb = (col(rt_calibrated), col(rt_library)) if delta else (None, None)
+        if obs.ndim != 1 or (delta and (cal.shape != obs.shape or lb.shape != obs.shape)):
+            raise ValueError("tl_rt_norm: one value of every column per row")
+        out = np.empty(obs.shape[0], np.result_type(obs, cal, lb) if delta else obs.dtype)
+        ms = C.c_double(0.0)
+        f64 = lambda a: int(a is not None and a.dtype == np.float64)  # noqa: E731
+        ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None  # noqa: E731
+        _check(lib.adh_tl_rt_norm(self._h, obs.shape[0], int(delta), ptr(obs), f64(obs), ptr(cal), f64(cal), ptr(lb),
+                                  f64(lb), ptr(out), C.byref(ms)), "adh_tl_rt_norm")
+        return out, float(ms.value)
+
 
 class DeviceMlp:
     """An ``adh_mlp_t``: the classifier network with its parameters, optimiser moments and the
@@ -1598,6 +1648,87 @@ class DeviceProteinFdr:
         """HIP-event times (ms) of the features, all epochs of the last fit, the last predict and the last gather."""
         t = [C.c_double(0.0) for _ in range(4)]
         _check(lib.adh_pfdr_time_ms(self._g, *(C.byref(x) for x in t)), "adh_pfdr_time_ms")
+        return tuple(float(x.value) for x in t)
+
+
+class DeviceTransferLibrary:
+    """An ``adh_tl_t``: the consensus of the transfer-learning library in HBM - sort keys, dense-row blocks and dense
+    matrices - updated run by run (include/alphadia_hip.h: adh_tl_*)."""
+
+    def __init__(self, ctx: Context, n_columns: int, n_matrices: int):
+        self._ctx = ctx  # keeps the handle alive
+        self._g = C.c_void_p()
+        self.n_columns, self.n_matrices = int(n_columns), int(n_matrices)
+        _check(lib.adh_tl_create(ctx._h, self.n_columns, self.n_matrices, C.byref(self._g)), "adh_tl_create")
+        self.n_kept = self.n_rows = 0
+
+    def close(self):
+        if self._g:
+            if self._ctx._h:  # (at interpreter exit the context may be finalised first: its handle and stream are gone)
+                lib.adh_tl_destroy(self._g)
+            self._g = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _p(a, t):
+        return a.ctypes.data_as(C.POINTER(t))
+
+    def scatter(self, n_rows: int, row, col, mz, intensity, correlation) -> bool:
+        """``adh_tl_scatter``: stages a run from its flat rows; True when a cell was written twice (nothing staged)."""
+        r, c = _abi.as_c(row, np.int64), _abi.as_c(col, np.int32)
+        v = [_abi.as_c(x, np.float32) for x in (mz, intensity, correlation)]
+        if r.ndim != 1 or any(a.shape != r.shape for a in (c, *v)):
+            raise ValueError("scatter: one value of every column per flat row")
+        dup = C.c_int32(0)
+        _check(lib.adh_tl_scatter(self._g, int(n_rows), r.shape[0], self._p(r, C.c_int64), self._p(c, C.c_int32),
+                                  *(self._p(a, C.c_float) for a in v), C.byref(dup)), "adh_tl_scatter")
+        return bool(dup.value)
+
+    def update(self, keep_top: int, mod_seq_hash, proba, precursor_idx, frag_start, frag_stop, n_new_rows: int,
+               matrices=None):
+        """``adh_tl_update`` + ``adh_tl_read_kept``: ``(kept, frag_start, frag_stop)`` of the new consensus; ``kept``
+        indexes "consensus before the call, then the new run".  ``matrices`` None: the staged run."""
+        h = np.ascontiguousarray(mod_seq_hash)
+        if h.dtype not in (np.dtype(np.uint64), np.dtype(np.int64)):
+            raise TypeError(f"update: mod_seq_hash must be uint64 or int64, not {h.dtype}")
+        pr = np.asarray(proba)
+        pr = np.ascontiguousarray(pr, dtype=np.float32 if pr.dtype == np.float32 else np.float64)
+        pi, fs, fe = (_abi.as_c(x, np.int64) for x in (precursor_idx, frag_start, frag_stop))
+        n = h.shape[0]
+        if h.ndim != 1 or any(a.shape != (n,) for a in (pr, pi, fs, fe)):
+            raise ValueError("update: one value of every column per precursor")
+        mats = None
+        if matrices is not None:
+            held = [_abi.as_c(m, np.float32) for m in matrices]
+            if len(held) != self.n_matrices or any(m.shape != (n_new_rows, self.n_columns) for m in held):
+                raise ValueError("update: every dense matrix is [n_new_rows, n_columns]")
+            mats = (C.POINTER(C.c_float) * len(held))(*(self._p(m, C.c_float) for m in held))
+        kept_n, rows_n = C.c_int64(0), C.c_int64(0)
+        _check(lib.adh_tl_update(self._g, int(keep_top), n, C.c_void_p(h.ctypes.data), int(h.dtype == np.int64),
+                                 C.c_void_p(pr.ctypes.data), int(pr.dtype == np.float64), self._p(pi, C.c_int64),
+                                 self._p(fs, C.c_int64), self._p(fe, C.c_int64), int(n_new_rows), mats, C.byref(kept_n),
+                                 C.byref(rows_n)), "adh_tl_update")
+        self.n_kept, self.n_rows = int(kept_n.value), int(rows_n.value)
+        kept, start, stop = (np.empty(self.n_kept, np.int64) for _ in range(3))
+        _check(lib.adh_tl_read_kept(self._g, self._p(kept, C.c_int64), self._p(start, C.c_int64), self._p(stop, C.c_int64)),
+               "adh_tl_read_kept")
+        return kept, start, stop
+
+    def matrix(self, m: int) -> np.ndarray:
+        """``adh_tl_read_matrix``: dense matrix ``m`` of the consensus."""
+        out = np.empty((self.n_rows, self.n_columns), np.float32)
+        _check(lib.adh_tl_read_matrix(self._g, int(m), self._p(out, C.c_float)), "adh_tl_read_matrix")
+        return out
+
+    def time_ms(self) -> tuple[float, float, float]:
+        """HIP-event times (ms) of the last update's top-k and row gather and of the last scatter."""
+        t = [C.c_double(0.0) for _ in range(3)]
+        _check(lib.adh_tl_time_ms(self._g, *(C.byref(x) for x in t)), "adh_tl_time_ms")
         return tuple(float(x.value) for x in t)
 
 

@@ -934,6 +934,57 @@ int adh_pfdr_gather(adh_pfdr_t *pfdr, int64_t n_groups, const double *group_valu
 /* HIP-event times (ms): the last adh_pfdr_features, all epochs since adh_pfdr_fit_begin, the last predict and gather */
 int adh_pfdr_time_ms(adh_pfdr_t *pfdr, double *features_ms, double *epochs_ms, double *predict_ms, double *gather_ms);
 
+/* ------------------------------------------------------------------------------------------
+ * Transfer-learning library: TransferLearningAccumulator, normalize_rt_max / _delta_max and
+ * ms2_quality_control (outputtransform/outputaccumulator.py:272-540).  An adh_tl_t keeps the
+ * consensus in HBM: the sort keys and dense-row blocks of its precursors and n_matrices dense
+ * float32 matrices of n_columns columns.  Strings and all other precursor columns stay with the
+ * host, which truncates them with the kept-row index the device returns.
+ * ------------------------------------------------------------------------------------------ */
+
+#define ADH_TL_MAX_MATRICES 4
+/* float32 values of LDS per wavefront in adh_tl_qc: a block with more cells of positive intensity takes the
+ * workgroup path */
+#define ADH_TL_QC_SLICE 512
+
+typedef struct adh_tl adh_tl_t;
+
+int adh_tl_create(adh_handle_t *handle, int32_t n_columns, int32_t n_matrices, adh_tl_t **tl);
+int adh_tl_destroy(adh_tl_t *tl);
+/* Stages one run from its flat fragment rows (needs n_matrices == 3: m/z, intensity, correlation): zero-filled
+ * matrices of n_rows rows, flat row i written at (row[i], col[i]).  A cell written twice sets *duplicate and nothing
+ * is staged.  A row or column outside the matrices fails before anything is launched. */
+int adh_tl_scatter(adh_tl_t *tl, int64_t n_rows, int64_t n_flat, const int64_t *row, const int32_t *col, const float *mz,
+                   const float *intensity, const float *correlation, int32_t *duplicate);
+/* Appends a run of n_new precursors and n_new_rows dense rows (matrices[n_matrices], row-major host arrays; NULL: the
+ * run adh_tl_scatter staged), orders all rows by (mod_seq_hash, proba, precursor_idx) ascending - stable, NaN proba
+ * last; the hash is uint64 or, with hash_is_signed, int64 - keeps the first keep_top rows of every hash, drops the
+ * dense rows of the others and renumbers the kept blocks in the order of their old start. */
+int adh_tl_update(adh_tl_t *tl, int32_t keep_top, int64_t n_new, const void *mod_seq_hash, int32_t hash_is_signed,
+                  const void *proba, int32_t proba_is_f64, const int64_t *precursor_idx, const int64_t *frag_start,
+                  const int64_t *frag_stop, int64_t n_new_rows, const float *const *matrices, int64_t *n_kept,
+                  int64_t *n_kept_rows);
+/* kept[n_kept]: the rows of the last update as indices into "consensus before it, then the new run", in their new
+ * order; frag_start / frag_stop[n_kept]: their renumbered blocks */
+int adh_tl_read_kept(adh_tl_t *tl, int64_t *kept, int64_t *frag_start, int64_t *frag_stop);
+/* matrix m of the consensus, [n_kept_rows * n_columns] row-major */
+int adh_tl_read_matrix(adh_tl_t *tl, int32_t m, float *out);
+/* HIP-event times (ms) of the last update's sort / keep mask and of its renumbering / row gathers, and of the last scatter */
+int adh_tl_time_ms(adh_tl_t *tl, double *topk_ms, double *gather_ms, double *scatter_ms);
+/* ms2_quality_control on host matrices [n_rows * n_columns]: per block the float32 median of the correlations at
+ * cells with intensity > 0 (none: 0.0, and use_for_ms2 = empty_passes), use_for_ms2 = median > cutoff, every
+ * intensity of the block multiplied by (correlation > median * ratio), in place.  *n_large: the blocks that took the
+ * workgroup path. */
+int adh_tl_qc(adh_handle_t *handle, int64_t n_precursors, const int64_t *frag_start, const int64_t *frag_stop,
+              int64_t n_rows, int32_t n_columns, float *intensity, const float *correlation, float cutoff, float ratio,
+              int32_t empty_passes, uint8_t *use_for_ms2, int64_t *n_large, double *kernel_ms);
+/* rt_norm[n]: delta_max == 0: rt_observed / max(rt_observed), the maximum skipping NaN, in rt_observed's type;
+ * else normalize_rt_delta_max with np.max (NaN propagates), every operation in the type NumPy's promotion of its
+ * operands gives; the result is float32 only when all three columns are. */
+int adh_tl_rt_norm(adh_handle_t *handle, int64_t n, int32_t delta_max, const void *rt_observed, int32_t observed_is_f64,
+                   const void *rt_calibrated, int32_t calibrated_is_f64, const void *rt_library, int32_t library_is_f64,
+                   void *rt_norm, double *kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif
