@@ -769,6 +769,24 @@ TL_PROTOTYPES = {
                        C.c_void_p, _f64p],
 }
 
+# ... and of the match-between-runs library (adh_mbr_*, adh_mbr_library.hip)
+_u64p = C.POINTER(C.c_uint64)
+MBR_PROTOTYPES = {
+    "adh_mbr_create": [C.c_void_p, C.POINTER(C.c_void_p)],
+    "adh_mbr_destroy": [C.c_void_p],
+    "adh_mbr_aggregate": [C.c_void_p, C.c_int64, _f64p, _u8p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                          C.c_int32, _u8p, C.c_double, C.c_int32, _i64p, _i64p, _i64p, _i64p],
+    "adh_mbr_read_table": [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, _i64p],
+    "adh_mbr_filter": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, _i64p, _i64p, C.c_int64, C.c_int32, C.c_int32,
+                       C.POINTER(_f32p), _i64p, _i64p],
+    "adh_mbr_read_filter": [C.c_void_p, _i64p, _i64p, _i64p, _i64p],
+    "adh_mbr_read_matrix": [C.c_void_p, C.c_int32, _f32p],
+    "adh_mbr_assign": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, _i64p, _i64p],
+    "adh_mbr_index": [C.c_void_p, C.c_int64, _u64p, C.c_int64, _u64p, _i64p, C.POINTER(C.c_int32)],
+    "adh_mbr_notnull_objects": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint8), _i64p],
+    "adh_mbr_stats": [C.c_void_p, _f64p, _f64p, _f64p, _f64p, _u64p, _u64p],
+}
+
 
 # ... and of the library staged from its columns and calibrated in HBM (adh_stage_lib.hip, adh_calibration.hip)
 STAGE_LIB_PROTOTYPES = {
@@ -787,9 +805,9 @@ PLAN_PROTOTYPES = {
 
 def declare(lib) -> None:
     """Argument types of the entries listed in RESIDENT_PROTOTYPES, STAGE_PART_PROTOTYPES, APPEND_PROTOTYPES,
-    QUANT_PROTOTYPES, PG_PROTOTYPES, PFDR_PROTOTYPES, TL_PROTOTYPES, STAGE_LIB_PROTOTYPES and PLAN_PROTOTYPES (the others are called with explicit casts)."""
+    QUANT_PROTOTYPES, PG_PROTOTYPES, PFDR_PROTOTYPES, TL_PROTOTYPES, MBR_PROTOTYPES, STAGE_LIB_PROTOTYPES and PLAN_PROTOTYPES (the others are called with explicit casts)."""
     for name, argtypes in {**RESIDENT_PROTOTYPES, **STAGE_PART_PROTOTYPES, **APPEND_PROTOTYPES, **QUANT_PROTOTYPES,
-                           **PG_PROTOTYPES, **PFDR_PROTOTYPES, **TL_PROTOTYPES, **STAGE_LIB_PROTOTYPES, **PLAN_PROTOTYPES}.items():
+                           **PG_PROTOTYPES, **PFDR_PROTOTYPES, **TL_PROTOTYPES, **MBR_PROTOTYPES, **STAGE_LIB_PROTOTYPES, **PLAN_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = C.c_int

@@ -120,6 +120,17 @@ EXPORTED_SYMBOLS = [
     "adh_tl_time_ms",
     "adh_tl_qc",
     "adh_tl_rt_norm",
+    "adh_mbr_create",
+    "adh_mbr_destroy",
+    "adh_mbr_aggregate",
+    "adh_mbr_read_table",
+    "adh_mbr_filter",
+    "adh_mbr_read_filter",
+    "adh_mbr_read_matrix",
+    "adh_mbr_assign",
+    "adh_mbr_index",
+    "adh_mbr_notnull_objects",
+    "adh_mbr_stats",
 ]
 
 
@@ -262,6 +273,29 @@ def take_objects(src: np.ndarray, idx: np.ndarray, threads: int = 8) -> np.ndarr
     if rc != 0:  # (an index NumPy would wrap or reject: let NumPy decide; entries written so far are dropped with dst)
         return src[idx]
     return dst
+
+
+def notnull_objects(a) -> np.ndarray:
+    """``pd.notna`` of a 1-d object column of strings and ``None`` (a ``pg`` column) without a Python call per element:
+    ``adh_mbr_notnull_objects`` tells ``None`` and ``str`` apart by pointer, pandas is asked about every other entry.
+    Where the object layout is not the probed one (see ``_probe_take_objects``), pandas does all of it."""
+    global _OBJ_TAKE
+    import pandas as pd
+
+    a = np.asarray(a)
+    if a.dtype != object or a.ndim != 1 or not a.flags.c_contiguous:
+        return np.asarray(pd.notna(a))
+    if _OBJ_TAKE is None:
+        _OBJ_TAKE = _probe_take_objects()
+    if not _OBJ_TAKE:
+        return np.asarray(pd.notna(a))
+    out, other = np.empty(len(a), np.uint8), C.c_int64(0)
+    _check(lib.adh_mbr_notnull_objects(a.ctypes.data, len(a), id(None), id(str), out.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                       C.byref(other)), "adh_mbr_notnull_objects")
+    if other.value:
+        rest = np.flatnonzero(out == 2)
+        out[rest] = pd.notna(a[rest])
+    return out.view(np.bool_)
 
 
 def _check(rc: int, what: str):
@@ -1246,6 +1280,11 @@ class Context:
                                   f64(lb), ptr(out), C.byref(ms)), "adh_tl_rt_norm")
         return out, float(ms.value)
 
+    # -- match-between-runs library ---------------------------------------
+    def mbr_library(self) -> DeviceMbr:
+        """An ``adh_mbr_t``: the aggregate tables, the passed elution groups and the filtered library in HBM."""
+        return DeviceMbr(self)
+
 
 class DeviceMlp:
     """An ``adh_mlp_t``: the classifier network with its parameters, optimiser moments and the
@@ -1730,6 +1769,162 @@ class DeviceTransferLibrary:
         t = [C.c_double(0.0) for _ in range(3)]
         _check(lib.adh_tl_time_ms(self._g, *(C.byref(x) for x in t)), "adh_tl_time_ms")
         return tuple(float(x.value) for x in t)
+
+
+class DeviceMbr:
+    """An ``adh_mbr_t``: the PSM aggregates, the elution groups that passed and the filtered library of the
+    match-between-runs library in HBM (include/alphadia_hip.h: adh_mbr_*)."""
+
+    def __init__(self, ctx: Context):
+        self._ctx = ctx  # keeps the handle alive
+        self._g = C.c_void_p()
+        _check(lib.adh_mbr_create(ctx._h, C.byref(self._g)), "adh_mbr_create")
+        self.n_passed = self.n_by_group = self.n_by_hash = self.n_groups = 0
+        self.n_kept = self.n_rows = self.n_columns = 0
+        self._rt_dtype = self._hash_dtype = self._group_dtype = None
+
+    def close(self):
+        if self._g:
+            if self._ctx._h:  # (at interpreter exit the context may be finalised first: its handle and stream are gone)
+                lib.adh_mbr_destroy(self._g)
+            self._g = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _p(a, t):
+        return a.ctypes.data_as(C.POINTER(t))
+
+    @staticmethod
+    def _group(a, what):
+        """The elution-group column as the entry takes it: uint32 as it is, every other integer type as int64."""
+        a = np.asarray(a)
+        if a.dtype.kind not in "iu" or (a.dtype == np.uint64 and a.size and int(a.max()) >= 2**63):
+            raise TypeError(f"{what}: elution_group_idx must be an integer column below 2^63, not {a.dtype}")
+        return np.ascontiguousarray(a, dtype=np.uint32 if a.dtype == np.uint32 else np.int64)
+
+    @staticmethod
+    def _hash(a, what):
+        a = np.ascontiguousarray(a)
+        if a.dtype not in (np.dtype(np.uint64), np.dtype(np.int64)):
+            raise TypeError(f"{what}: mod_seq_charge_hash must be uint64 or int64, not {a.dtype}")
+        return a
+
+    def aggregate(self, qval, decoy, elution_group_idx, mod_seq_charge_hash, rt_observed, pg_notnull, fdr: float,
+                  keep_decoys: bool):
+        """``adh_mbr_aggregate``: ``(rows that passed, rows of the table by group, by hash, groups that passed)``."""
+        q = np.asarray(qval)
+        if q.dtype == np.float32:  # the comparison NumPy makes in float32, restated exactly in float64
+            fdr = float(np.float32(fdr))
+        q = np.ascontiguousarray(q, dtype=np.float64)
+        d = np.asarray(decoy)
+        d = np.ascontiguousarray(d).view(np.uint8) if d.dtype.itemsize == 1 else (d != 0).astype(np.uint8)
+        eg, h = self._group(elution_group_idx, "aggregate"), self._hash(mod_seq_charge_hash, "aggregate")
+        rt = np.asarray(rt_observed)
+        rt = np.ascontiguousarray(rt, dtype=np.float32 if rt.dtype == np.float32 else np.float64)
+        pg = np.ascontiguousarray(pg_notnull, dtype=np.uint8)
+        n = q.shape[0]
+        if q.ndim != 1 or any(a.shape != (n,) for a in (d, eg, h, rt, pg)):
+            raise ValueError("aggregate: one value of every column per PSM row")
+        out = [C.c_int64(0) for _ in range(4)]
+        _check(lib.adh_mbr_aggregate(self._g, n, self._p(q, C.c_double), self._p(d, C.c_uint8), C.c_void_p(eg.ctypes.data),
+                                     int(eg.dtype == np.uint32), C.c_void_p(h.ctypes.data), int(h.dtype == np.int64),
+                                     C.c_void_p(rt.ctypes.data), int(rt.dtype == np.float64), self._p(pg, C.c_uint8),
+                                     float(fdr), int(bool(keep_decoys)), *(C.byref(x) for x in out)), "adh_mbr_aggregate")
+        self.n_passed, self.n_by_group, self.n_by_hash, self.n_groups = (int(x.value) for x in out)
+        self._rt_dtype, self._hash_dtype = rt.dtype, h.dtype
+        self._group_dtype = np.asarray(elution_group_idx).dtype
+        self.n_kept = self.n_rows = 0
+        return self.n_passed, self.n_by_group, self.n_by_hash, self.n_groups
+
+    def table(self, which: int):
+        """``adh_mbr_read_table``: ``(keys, median, first pg row)`` of the table by group (0) or by hash (1); the keys
+        in the dtype the PSM column had."""
+        n = (self.n_by_group, self.n_by_hash)[which]
+        keys = np.empty(n, np.int64 if which == 0 else self._hash_dtype)
+        med, first = np.empty(n, self._rt_dtype), np.empty(n, np.int64)
+        _check(lib.adh_mbr_read_table(self._g, int(which), C.c_void_p(keys.ctypes.data), C.c_void_p(med.ctypes.data),
+                                      self._p(first, C.c_int64)), "adh_mbr_read_table")
+        return (keys.astype(self._group_dtype) if which == 0 else keys), med, first
+
+    def groups(self) -> np.ndarray:
+        """The elution groups that passed, ascending."""
+        keys = np.empty(self.n_groups, np.int64)
+        _check(lib.adh_mbr_read_table(self._g, 2, C.c_void_p(keys.ctypes.data), None, None), "adh_mbr_read_table")
+        return keys.astype(self._group_dtype)
+
+    def filter(self, elution_group_idx, frag_start, frag_stop, n_rows: int, matrices=None, source_rows: bool = False):
+        """``adh_mbr_filter`` + ``adh_mbr_read_filter``: ``(kept, frag_start, frag_stop, source_row)`` - the kept library
+        rows, their renumbered blocks and, with ``source_rows``, the old dense row of every kept dense row.
+        ``matrices`` None: nothing is gathered on the device."""
+        eg = self._group(elution_group_idx, "filter")
+        fs, fe = _abi.as_c(frag_start, np.int64), _abi.as_c(frag_stop, np.int64)
+        n = eg.shape[0]
+        if eg.ndim != 1 or fs.shape != (n,) or fe.shape != (n,):
+            raise ValueError("filter: one value of every column per precursor")
+        mats, n_cols, held = None, 0, []
+        if matrices is not None:
+            held = [_abi.as_c(m, np.float32) for m in matrices]
+            if not 1 <= len(held) <= _abi.TL_MAX_MATRICES:
+                raise ValueError(f"filter: 1 to {_abi.TL_MAX_MATRICES} dense matrices, not {len(held)}")
+            if any(m.ndim != 2 or m.shape != held[0].shape or m.shape[0] != n_rows for m in held):
+                raise ValueError("filter: every dense matrix is [n_rows, n_columns]")
+            n_cols = held[0].shape[1]
+            mats = (C.POINTER(C.c_float) * len(held))(*(self._p(m, C.c_float) for m in held))
+        kept_n, rows_n = C.c_int64(0), C.c_int64(0)
+        _check(lib.adh_mbr_filter(self._g, n, C.c_void_p(eg.ctypes.data), int(eg.dtype == np.uint32), self._p(fs, C.c_int64),
+                                  self._p(fe, C.c_int64), int(n_rows), int(n_cols), len(held), mats, C.byref(kept_n),
+                                  C.byref(rows_n)), "adh_mbr_filter")
+        self.n_kept, self.n_rows, self.n_columns = int(kept_n.value), int(rows_n.value), int(n_cols)
+        kept, start, stop = (np.empty(self.n_kept, np.int64) for _ in range(3))
+        src = np.empty(self.n_rows, np.int64) if source_rows else None
+        if self.n_kept:
+            _check(lib.adh_mbr_read_filter(self._g, self._p(kept, C.c_int64), self._p(start, C.c_int64),
+                                           self._p(stop, C.c_int64), self._p(src, C.c_int64) if source_rows else None),
+                   "adh_mbr_read_filter")
+        return kept, start, stop, src
+
+    def matrix(self, m: int) -> np.ndarray:
+        """``adh_mbr_read_matrix``: gathered dense matrix ``m`` of the last filter."""
+        out = np.empty((self.n_rows, self.n_columns), np.float32)
+        if self.n_kept:
+            _check(lib.adh_mbr_read_matrix(self._g, int(m), self._p(out, C.c_float)), "adh_mbr_read_matrix")
+        return out
+
+    def assign(self, elution_group_idx, mod_seq_charge_hash):
+        """``adh_mbr_assign``: ``(rt, pg row in the PSM table or -1, precursors whose elution group is missing)``."""
+        eg, h = self._group(elution_group_idx, "assign"), self._hash(mod_seq_charge_hash, "assign")
+        if h.dtype != self._hash_dtype:
+            raise TypeError(f"assign: mod_seq_charge_hash is {h.dtype} in the library and {self._hash_dtype} in the PSM table")
+        n = eg.shape[0]
+        if eg.ndim != 1 or h.shape != (n,):
+            raise ValueError("assign: one value of every column per precursor")
+        rt, row, missing = np.empty(n, self._rt_dtype), np.empty(n, np.int64), C.c_int64(0)
+        _check(lib.adh_mbr_assign(self._g, n, C.c_void_p(eg.ctypes.data), int(eg.dtype == np.uint32), C.c_void_p(h.ctypes.data),
+                                  int(h.dtype == np.int64), C.c_void_p(rt.ctypes.data), self._p(row, C.c_int64),
+                                  C.byref(missing)), "adh_mbr_assign")
+        return rt, row, int(missing.value)
+
+    def index(self, target_keys, lookup_keys):
+        """``adh_mbr_index``: ``(position of every target in lookup_keys or -1, a lookup key occurs twice)``; both
+        columns in an order-preserving uint64 form."""
+        t, k = _abi.as_c(target_keys, np.uint64), _abi.as_c(lookup_keys, np.uint64)
+        out, dup = np.empty(t.shape[0], np.int64), C.c_int32(0)
+        _check(lib.adh_mbr_index(self._g, t.shape[0], self._p(t, C.c_uint64), k.shape[0], self._p(k, C.c_uint64),
+                                 self._p(out, C.c_int64), C.byref(dup)), "adh_mbr_index")
+        return out, bool(dup.value)
+
+    def stats(self) -> dict:
+        """HIP-event times (ms) of the last aggregate, filter, gather and assign; bytes over PCIe since creation."""
+        t = [C.c_double(0.0) for _ in range(4)]
+        b = [C.c_uint64(0), C.c_uint64(0)]
+        _check(lib.adh_mbr_stats(self._g, *(C.byref(x) for x in t), *(C.byref(x) for x in b)), "adh_mbr_stats")
+        return dict(aggregate_ms=t[0].value, filter_ms=t[1].value, gather_ms=t[2].value, assign_ms=t[3].value,
+                    h2d_bytes=int(b[0].value), d2h_bytes=int(b[1].value))
 
 
 _contexts: dict[int, Context] = {}

@@ -985,6 +985,62 @@ int adh_tl_rt_norm(adh_handle_t *handle, int64_t n, int32_t delta_max, const voi
                    const void *rt_calibrated, int32_t calibrated_is_f64, const void *rt_library, int32_t library_is_f64,
                    void *rt_norm, double *kernel_ms);
 
+/* ------------------------------------------------------------------------------------------
+ * Match-between-runs library: MbrLibraryBuilder and IndexBuilder (libtransform/mbr.py).  An
+ * adh_mbr_t keeps what one step leaves for the next in HBM: the two aggregate tables and the
+ * elution groups that passed (adh_mbr_aggregate), the kept library rows and their dense rows
+ * (adh_mbr_filter).  The host may change the library between adh_mbr_filter and adh_mbr_assign
+ * (decoys).  Strings stay with the host: pg comes back as a row of the PSM table.
+ * ------------------------------------------------------------------------------------------ */
+
+typedef struct adh_mbr adh_mbr_t;
+
+int adh_mbr_create(adh_handle_t *handle, adh_mbr_t **mbr);
+int adh_mbr_destroy(adh_mbr_t *mbr);
+/* The PSM table of n rows: rows with qval <= fdr (NaN fails) are aggregated by elution_group_idx (uint32 with
+ * group_is_u32, else int64) and by mod_seq_charge_hash (uint64, or int64 with hash_is_signed): the distinct keys
+ * ascending, the median of the non-NaN rt_observed (float32, or float64 with rt_is_f64; the mean of the two middle
+ * values in float64, rounded to the column's type; NaN when all are NaN; -0.0 counts as +0.0) and the first row with
+ * pg_notnull (-1: none).  The groups that passed are the distinct elution groups of the surviving rows, of those with
+ * decoy == 0 unless keep_decoys.  *n_passed: surviving rows; *n_by_group / *n_by_hash: rows of the two tables. */
+int adh_mbr_aggregate(adh_mbr_t *mbr, int64_t n, const double *qval, const uint8_t *decoy, const void *elution_group_idx,
+                      int32_t group_is_u32, const void *mod_seq_charge_hash, int32_t hash_is_signed, const void *rt_observed,
+                      int32_t rt_is_f64, const uint8_t *pg_notnull, double fdr, int32_t keep_decoys, int64_t *n_passed,
+                      int64_t *n_by_group, int64_t *n_by_hash, int64_t *n_groups);
+/* which 0: the table by elution group (keys as int64 values), 1: by hash (keys in the bits they came in), 2: the
+ * groups that passed (keys only, as int64 values).  median in rt_observed's type. */
+int adh_mbr_read_table(adh_mbr_t *mbr, int32_t which, void *keys, void *median, int64_t *first_row);
+/* The library of n_lib precursors and n_rows dense rows: keeps the precursors whose elution group passed (library row
+ * order), orders their blocks [frag_start, frag_stop) by ascending old start (stable), renumbers them by an exclusive
+ * scan of their lengths and gathers the rows of matrices[n_matrices] (float32 [n_rows * n_columns] host arrays).
+ * matrices NULL: only the source row of every kept dense row is computed (adh_mbr_read_filter). */
+int adh_mbr_filter(adh_mbr_t *mbr, int64_t n_lib, const void *elution_group_idx, int32_t group_is_u32, const int64_t *frag_start,
+                   const int64_t *frag_stop, int64_t n_rows, int32_t n_columns, int32_t n_matrices, const float *const *matrices,
+                   int64_t *n_kept, int64_t *n_kept_rows);
+/* kept[n_kept]: the kept library rows; frag_start / frag_stop[n_kept]: their renumbered blocks; source_row[n_kept_rows]
+ * (may be NULL): the old dense row of every kept dense row */
+int adh_mbr_read_filter(adh_mbr_t *mbr, int64_t *kept, int64_t *frag_start, int64_t *frag_stop, int64_t *source_row);
+/* gathered matrix m, [n_kept_rows * n_columns] row-major */
+int adh_mbr_read_matrix(adh_mbr_t *mbr, int32_t m, float *out);
+/* Per precursor: rt[n] (the aggregate's rt type) and pg_row[n] (a PSM row, -1: null) from the hash table where the
+ * hash was identified, from the elution-group table otherwise.  *n_missing: precursors whose elution group is in
+ * neither (their rt is NaN, pg_row -1).  The hash has the aggregate's signedness. */
+int adh_mbr_assign(adh_mbr_t *mbr, int64_t n, const void *elution_group_idx, int32_t group_is_u32, const void *mod_seq_charge_hash,
+                   int32_t hash_is_signed, void *rt, int64_t *pg_row, int64_t *n_missing);
+/* index[n_targets]: the position of every target key in lookup_keys, -1 when absent; keys in an order-preserving
+ * uint64 form.  *duplicate: a lookup key occurs twice (index is then undefined). */
+int adh_mbr_index(adh_mbr_t *mbr, int64_t n_targets, const uint64_t *target_keys, int64_t n_lookup, const uint64_t *lookup_keys,
+                  int64_t *index, int32_t *duplicate);
+/* The pg_notnull mask of a 1-d array of Python objects without a call per element (host only): out[i] = 0 where
+ * items[i] is `none`, 1 where its type is `str_type`, 2 elsewhere; *n_other counts the 2s.  Only for interpreters whose
+ * objects begin with the reference count and the type pointer (runtime.py probes that). */
+int adh_mbr_notnull_objects(void *const *items, int64_t n, const void *none, const void *str_type, uint8_t *out,
+                            int64_t *n_other);
+/* HIP-event times (ms) of the last aggregate, filter (membership, renumbering), row gather and assign; bytes moved
+ * host to device and device to host since adh_mbr_create */
+int adh_mbr_stats(adh_mbr_t *mbr, double *aggregate_ms, double *filter_ms, double *gather_ms, double *assign_ms,
+                  uint64_t *h2d_bytes, uint64_t *d2h_bytes);
+
 #ifdef __cplusplus
 }
 #endif
