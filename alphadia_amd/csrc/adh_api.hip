@@ -322,7 +322,12 @@ struct Plan {
     // candidates per kernel class (adh_plan.hip): fused kernel / register kernels by cycle count (a
     // kernel per four cycles: every cycle loop is unrolled to the class size) / the LDS kernel
     int64_t n_class[ADH_N_CLASSES] = {0};
-    Caps caps_generic;
+    // the generic class in launch groups by the candidates' own LDS layout (adh_feature_layout.h): candidates and
+    // dynamic LDS of every group; `generic_over` != 0: a candidate beyond the spill path's bound (PlanMeta::gen_over)
+    int64_t n_generic[ADH_GENERIC_GROUPS] = {0};
+    int64_t lds_generic[ADH_GENERIC_GROUPS] = {0};
+    uint64_t generic_over = 0;
+    bool spill_all = false;        // ADH_DEBUG_GENERIC_SPILL
     Caps caps_all;
 };
 
@@ -418,6 +423,8 @@ struct adh_handle {
     int64_t n_timed = 0;
     uint64_t d2h_bytes = 0;  // bytes this library copied device -> host (adh_transfer_counters)
     int64_t class_counts[ADH_N_CLASSES] = {0};  // candidates per kernel class of every launched plan (adh_plan_class_counts)
+    // generic launch groups of every launched plan: candidates per group, largest dynamic LDS per group (adh_generic_launch_stats)
+    int64_t generic_stats[2 * ADH_GENERIC_GROUPS] = {0};
     // page-locked staging of upload_staged (H2D of a caller's pageable arrays): per lane two buffers, their events, a stream
     struct UpLane {
         void *buf[2] = {nullptr, nullptr};
@@ -605,8 +612,11 @@ int adh_create(adh_handle_t **handle, int device) {
         return fail(e == hipErrorOutOfMemory ? ADH_ERR_OUT_OF_MEMORY : ADH_ERR_HIP, msg);
     }
     // the kernels may need more than the default 64 KiB of dynamic LDS
-    (void)hipFuncSetAttribute((const void *)adh_feature_kernel,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    // (these two also have ADH_FEATURE_STATIC_LDS bytes of static LDS)
+    (void)hipFuncSetAttribute((const void *)adh_feature_kernel<false>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, ADH_GENERIC_LDS_LIMIT);
+    (void)hipFuncSetAttribute((const void *)adh_feature_kernel<true>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, ADH_GENERIC_LDS_LIMIT);
     (void)hipFuncSetAttribute((const void *)adh_gather_kernel,
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     // (this kernel also has ADH_IM_STATIC_LDS bytes of static LDS)

@@ -23,6 +23,7 @@
 //   * compile with -ffp-contract=off
 #include "adh_device.h"
 #include "adh_feature_common.h"
+#include "adh_feature_layout.h"
 
 namespace feat {
 
@@ -40,73 +41,40 @@ __device__ __forceinline__ double logistic(double x, double mu, double sigma) {
     return 1.0 / (1.0 + exp(-a));
 }
 
-// LDS regions.  Element counts depend only on the launch capacities.
-struct Layout {
-    int Kc, Oc, Fc, Ic;
-    __host__ __device__ Layout(const Caps &c) : Kc(c.k), Oc(c.o), Fc(c.f), Ic(c.i) {}
-    // doubles
-    __host__ __device__ int d_wt() const { return 0; }
-    __host__ __device__ int d_wtp() const { return d_wt() + Oc * 2 * Fc; }
-    __host__ __device__ int d_qtf() const { return d_wtp() + 2 * Fc; }
-    __host__ __device__ int d_omz() const { return d_qtf() + Ic * Oc; }
-    __host__ __device__ int d_ohe() const { return d_omz() + Kc * Oc; }
-    __host__ __device__ int d_pk() const { return d_ohe() + Kc * Oc; }   // [4][Kc]: mzmean,height,area,merr
-    __host__ __device__ int d_po() const { return d_pk() + 4 * Kc; }     // [2][Oc]: esc, efc
-    __host__ __device__ int d_pi() const { return d_po() + 2 * Oc; }     // [2][Ic]: hp, omzp
-    __host__ __device__ int n_double() const { return d_pi() + 2 * Ic; }
-    // floats (after the doubles)
-    __host__ __device__ int f_tile() const { return 0; }                 // [3][Kc*Oc*Fc]: fi, fm, ffp
-    __host__ __device__ int f_prec() const { return f_tile() + 3 * Kc * Oc * Fc; }  // [2][Ic*Fc]
-    __host__ __device__ int f_tpl() const { return f_prec() + 2 * Ic * Fc; }        // [2][Oc*Fc]
-    __host__ __device__ int f_bp() const { return f_tpl() + 2 * Oc * Fc; }          // [Kc*Fc]
-    __host__ __device__ int f_pk() const { return f_bp() + Kc * Fc; }    // [6][Kc]
-    __host__ __device__ int f_pko() const { return f_pk() + 6 * Kc; }    // [3][Kc*Oc]
-    __host__ __device__ int f_po() const { return f_pko() + 3 * Kc * Oc; }  // [4][Oc]
-    __host__ __device__ int f_pi() const { return f_po() + 4 * Oc; }     // [3][Ic]
-    __host__ __device__ int f_pf() const { return f_pi() + 3 * Ic; }     // [3][Fc]
-    __host__ __device__ int f_feat() const { return f_pf() + 3 * Fc; }
-    __host__ __device__ int n_float() const { return f_feat() + ADH_NUM_FEATURES; }
-    // ints (after the floats)
-    __host__ __device__ int i_pk() const { return 0; }                   // [3][Kc]: present, kmap, ord
-    __host__ __device__ int i_pko() const { return i_pk() + 3 * Kc; }    // [Kc*Oc]: fpeak
-    __host__ __device__ int i_obs() const { return i_pko() + Kc * Oc; }  // [Oc]
-    __host__ __device__ int n_int() const { return i_obs() + Oc; }
-    // bytes (after the ints): [5][Kc]
-    __host__ __device__ int n_byte() const { return ((5 * Kc + 7) / 8) * 8; }
-    __host__ __device__ size_t bytes() const {
-        size_t b = (size_t)n_double() * 8;
-        b += ((size_t)n_float() * 4 + 7) / 8 * 8;
-        b += ((size_t)n_int() * 4 + 7) / 8 * 8;
-        b += n_byte();
-        return b;
+// Where the candidate's tile lives: the three [K][O][F] planes fi, fm, ffp and bp[K][F].  In LDS behind the layout's
+// other regions, or (Spill) in the candidate's spill block of the scratch slab, which only this wavefront touches:
+// the workgroup barriers of the body order its writes and reads there as they do in LDS.
+template <bool Spill>
+struct Tile {
+    float *fi, *fm, *ffp, *bp;
+    __device__ __forceinline__ Tile(const Layout &lay, float *Fl, unsigned char *spill_block) {
+        const int plane = lay.Kc * lay.Oc * lay.Fc;
+        if (Spill) {
+            fi = reinterpret_cast<float *>(spill_block);
+            bp = fi + 3 * plane;
+        } else {
+            fi = Fl + lay.f_tile();
+            bp = Fl + lay.f_bp();
+        }
+        fm = fi + plane;
+        ffp = fm + plane;
     }
 };
 
 }  // namespace feat
 
-size_t adh_feature_lds_bytes(const Caps &c) { return feat::Layout(c).bytes(); }
-
+// Spill = false: the whole layout in LDS (launch groups 0 and 1 of the generic class); Spill = true: the tile planes
+// in `spill` (the scratch slab again, writable and not restrict: `scratch` stays the read-only view of the gather's
+// cells).  Every block lays its LDS out by its candidate's own capacities; `stop_phase` is the developer stop.
+template <bool Spill>
 __global__ __launch_bounds__(ADH_WAVE) void adh_feature_kernel(
     DevRun run, const CandRec *__restrict__ plan, const float *__restrict__ iso_table,
     int32_t n_iso_cols, adh_scoring_config_t cfg, const unsigned char *__restrict__ scratch,
-    DevOut out, Caps caps) {
+    unsigned char *spill, DevOut out, int32_t stop_phase) {
     using namespace feat;
     extern __shared__ __align__(16) unsigned char smem[];
-    const Layout lay(caps);
-    const int Kc = lay.Kc, Oc = lay.Oc, Fc = lay.Fc, Ic = lay.Ic;
-    double *const D = reinterpret_cast<double *>(smem);
-    float *const Fl = reinterpret_cast<float *>(smem + (size_t)lay.n_double() * 8);
-    int *const In = reinterpret_cast<int *>(reinterpret_cast<unsigned char *>(Fl) +
-                                           ((size_t)lay.n_float() * 4 + 7) / 8 * 8);
-    uint8_t *const By = reinterpret_cast<uint8_t *>(In) + ((size_t)lay.n_int() * 4 + 7) / 8 * 8;
-
     const int lane = threadIdx.x;
     const CandRec &r = plan[blockIdx.x];
-    if (r.flags & ADH_FLAG_SKIP) return;
-    const unsigned char *block = scratch + r.scratch_off;
-    const uint32_t *header = reinterpret_cast<const uint32_t *>(block);
-    const int K0 = (int)header[0];
-    if (K0 == 0) return;  // failed before / in the gather kernel
     const uint32_t row = r.row;
     const int L = run.cycle_len;
     const int c0 = r.frame_start / L;
@@ -114,18 +82,36 @@ __global__ __launch_bounds__(ADH_WAVE) void adh_feature_kernel(
     const int O = r.n_obs;
     const int I = min(n_iso_cols, (int)cfg.top_k_isotopes);
     const int OF = O * F;
+
+    // the candidate's own layout (what the plan sized its launch group by: adh_plan_rec_kernel).  The capacities are
+    // read above the early exits and the section bases taken below them on purpose: this order keeps the LDS
+    // instantiation's spilled SGPRs at the count the kernel had with launch-wide capacities (resource table)
+    const Layout lay(own_caps(r.k_cap, O, F, I), Spill);
+    const int Kc = lay.Kc, Oc = lay.Oc, Fc = lay.Fc, Ic = lay.Ic;
+    if (r.flags & ADH_FLAG_SKIP) return;
+    const unsigned char *block = scratch + r.scratch_off;
+    const uint32_t *header = reinterpret_cast<const uint32_t *>(block);
+    const int K0 = (int)header[0];
+    if (K0 == 0) return;  // failed before / in the gather kernel
     const int top_k = out.top_k;
     if (lane == 0 && out.stat_matched_peaks) out.stat_matched_peaks[row] = header[1];
 
+    double *const D = reinterpret_cast<double *>(smem);
+    float *const Fl = reinterpret_cast<float *>(smem + (size_t)lay.n_double() * 8);
+    int *const In = reinterpret_cast<int *>(reinterpret_cast<unsigned char *>(Fl) +
+                                           ((size_t)lay.n_float() * 4 + 7) / 8 * 8);
+    uint8_t *const By = reinterpret_cast<uint8_t *>(In) + ((size_t)lay.n_int() * 4 + 7) / 8 * 8;
+
     // tiles
-    float *const fi = Fl + lay.f_tile();
-    float *const fm = fi + Kc * Oc * Fc;
-    float *const ffp = fm + Kc * Oc * Fc;
+    const Tile<Spill> tile(lay, Fl, Spill ? spill + r.scratch_off + adh_scratch_bytes(r.k_cap, O, max(F, 0), I) : nullptr);
+    float *const fi = tile.fi;
+    float *const fm = tile.fm;
+    float *const ffp = tile.ffp;
     float *const pi = Fl + lay.f_prec();
     float *const pm = pi + Ic * Fc;
     float *const tpl = Fl + lay.f_tpl();
     float *const tfp = tpl + Oc * Fc;
-    float *const bp = Fl + lay.f_bp();
+    float *const bp = tile.bp;
     // per-o / per-i / per-f floats
     float *const oi = Fl + lay.f_po();
     float *const tsum = oi + Oc;
@@ -302,7 +288,7 @@ __global__ __launch_bounds__(ADH_WAVE) void adh_feature_kernel(
     }
     const int n_frame_rt = F;  // frame_stop - frame_start is a multiple of the cycle length
     for (int f = lane; f < F; f += ADH_WAVE) frame_rt[f] = run.rt[r.frame_start + f * L];
-    if (caps.stop_phase == 3) return;
+    if (stop_phase == 3) return;
 
     // =========================== features ===========================
     double *const wt = D + lay.d_wt();
@@ -372,7 +358,7 @@ __global__ __launch_bounds__(ADH_WAVE) void adh_feature_kernel(
             hp[i] = res;
     }
     __syncthreads();
-    if (caps.stop_phase == 4) return;
+    if (stop_phase == 4) return;
 
     // ---- best profile + centre envelope (fragment_features.py:240-250)
     double *const omz = D + lay.d_omz();
@@ -512,7 +498,7 @@ __global__ __launch_bounds__(ADH_WAVE) void adh_feature_kernel(
         ord[rk] = k;
     }
     __syncthreads();
-    if (caps.stop_phase == 5) return;
+    if (stop_phase == 5) return;
 
     // ---- scalar feature assembly by lane 0 (short sequential float sums)
     Assemble asmv;
@@ -526,7 +512,7 @@ __global__ __launch_bounds__(ADH_WAVE) void adh_feature_kernel(
     asmv.merr = merr; asmv.kmap = kmap; asmv.ord = ord; asmv.g_type = g_type; asmv.g_pos = g_pos;
     asmv.n_present = n_present; asmv.K0 = K0; asmv.top3 = 0.0f;
     if (lane == 0) assemble_part1(asmv, I, O, K);
-    if (caps.stop_phase == 6) return;
+    if (stop_phase == 6) return;
 
     // =========================== profile features (profile_features.py:18-206)
     // fi / fm are dead from here on: reuse them as isl[K][F] and nrm[K][F]

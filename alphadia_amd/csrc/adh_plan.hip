@@ -15,11 +15,12 @@
 //     generic LDS kernel) and the size of the candidate's scratch block,
 //   * emits a sort key (class, first cycle).
 // A stable radix sort of (key, row) pairs, an exclusive scan of the scratch sizes in sorted order
-// and one scatter produce the CandRec table in processing order; class boundaries, LDS capacities
-// and the scratch size come back to the host in one 128-byte record.  Nothing of this depends on
-// the order of candidates in the input, and the output rows are the input rows.
+// and one scatter produce the CandRec table in processing order; class boundaries, LDS capacities,
+// the launch groups of the generic class and the scratch size come back to the host in one record
+// (PlanMeta).  Nothing of this depends on the order of candidates in the input, and the output rows are the input rows.
 #pragma once
 #include "adh_device.h"
+#include "adh_feature_layout.h"
 
 // kernel classes, in processing order:
 //   0 ..  6  fused gather + feature kernel (adh_fused.hip), one observation, FM = 8, 12, ..., 32 registers
@@ -32,7 +33,9 @@
 //            requantification, top_k_fragments = 9999)
 //  27 .. 29  the same for one observation
 //  30 .. 35  the same pair with two candidates per wavefront, 32 lanes each: 17 ... 32 fragments kept
-//  36        the generic LDS kernel behind the gather kernel
+//  36        the generic LDS kernel behind the gather kernel; inside the plan its candidates sort into
+//            ADH_GENERIC_GROUPS launch groups by their own LDS layout (sort classes 36, 37, 38: adh_feature_layout.h),
+//            the last of them the spill instantiation
 // ion-mobility plans use classes 0 (one observation), 1 (two), ADH_CLASS_IM_SMALL (one observation, a tile
 // within the limits below: a feature-kernel instantiation with 12.8 KB of LDS instead of 16.3) and the generic one
 #define ADH_CLASS_IM_SMALL 2
@@ -50,6 +53,7 @@
 #define ADH_CLASS_MID1 33
 #define ADH_CLASS_GENERIC 36
 #define ADH_N_CLASSES 37
+#define ADH_N_SORT_CLASSES (ADH_N_CLASSES - 1 + ADH_GENERIC_GROUPS)  // the generic class counts once per launch group
 #define ADH_PLAN_WIDE_KMAX 64
 
 // mirrors of the register-kernel limits (adh_features_fast.hip)
@@ -81,8 +85,13 @@ struct PlanMeta {
     int32_t err, pad;
     int32_t all_k, all_o, all_f, all_n_lib, all_s, all_op;  // maxima over the batch
     int32_t gen_k, gen_o, gen_f, gen_n_lib;                 // maxima over the generic class
-    uint32_t class_first[ADH_N_CLASSES + 1];                // first processing position of every class
+    uint32_t class_first[ADH_N_SORT_CLASSES + 1];           // first processing position of every sort class
     uint64_t scratch_bytes;
+    // generic launch groups: largest own layout (dynamic LDS of the launch; the spill layout in the spill group)
+    int32_t gen_lds[ADH_GENERIC_GROUPS];
+    int32_t pad2;
+    // largest spill layout BEYOND the LDS limit (refused by the host): bytes << 32 | min(K, 2^24 - 1) << 8 | O
+    unsigned long long gen_over;
 };
 
 struct PlanArgs {
@@ -98,6 +107,7 @@ struct PlanArgs {
     int32_t fast_cfg, quant_all;  // fast_cfg: bit 0 the register kernels, bit 1 their wide form
     int32_t fused_cfg;      // the fused kernel may be used (one MS1 row per cycle, <= 3 isotopes): bit 0 for one, bit 1 for two observations
     int32_t n_cyc_bins;     // first-cycle bins per class in the sort key
+    int32_t spill_all;      // developer switch ADH_DEBUG_GENERIC_SPILL: every generic candidate takes the spill path
 };
 
 namespace plan {
@@ -110,6 +120,15 @@ __device__ __forceinline__ void raise_max(int32_t *slot, int32_t v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off));
     if ((threadIdx.x & 63) == 0 && v > *reinterpret_cast<volatile int32_t *>(slot)) atomicMax(slot, v);
+}
+
+__device__ __forceinline__ void raise_max64(unsigned long long *slot, unsigned long long v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long w = __shfl_xor(v, off);
+        v = w > v ? w : v;
+    }
+    if ((threadIdx.x & 63) == 0 && v > *reinterpret_cast<volatile unsigned long long *>(slot)) atomicMax(slot, v);
 }
 
 // isotope m/z range -> quadrupole query range exactly as the kernels compute it
@@ -157,6 +176,9 @@ __global__ __launch_bounds__(256) void adh_plan_rec_kernel(DevCands c, const dou
     uint32_t bin = 0;
     uint64_t nbytes = 0;
     int32_t mx_k = 0, mx_o = 0, mx_f = 0, mx_l = 0, gx_k = 0, gx_o = 0, gx_f = 0, gx_l = 0;
+    int32_t gl[ADH_GENERIC_GROUPS] = {0, 0, 0};
+    unsigned long long over = 0;
+    int group = 0;  // rows flagged to be skipped and rows with an error: the first group, no LDS of their own
     if (!(r.flags & ADH_FLAG_SKIP)) {
         int err = 0;
         if (r.frag_stop < r.frag_start || (int64_t)r.frag_stop > p.n_lib) err = ADH_PLAN_ERR_FRAG_SLICE;
@@ -203,6 +225,24 @@ __global__ __launch_bounds__(256) void adh_plan_rec_kernel(DevCands c, const dou
                                               : ADH_CLASS_FAST2 + (F <= 16 ? 0 : (F <= 24 ? 1 : 2)))));
             bin = (uint32_t)(r.frame_start / p.L);
             nbytes = fused ? 0 : adh_scratch_bytes(r.k_cap, O, max(F, 0), p.I);  // nothing leaves the CU there
+            if (cls == ADH_CLASS_GENERIC) {
+                // the launch group by the candidate's OWN layout; beyond the LDS of a CU the tile planes go to a spill
+                // block behind the gather cells of the same scratch block (one exclusive scan places both)
+                const Caps own = feat::own_caps(r.k_cap, O, F, p.I);
+                uint32_t lds = feat::own_layout_bytes(own, false);
+                group = lds <= (uint32_t)ADH_GENERIC_SMALL_LDS ? 0 : 1;
+                if (lds > (uint32_t)ADH_GENERIC_LDS_LIMIT || p.spill_all) {
+                    group = ADH_GENERIC_GROUP_SPILL;
+                    lds = feat::own_layout_bytes(own, true);
+                    if (lds > (uint32_t)ADH_GENERIC_LDS_LIMIT) {
+                        if (live) over = ((unsigned long long)lds << 32) | ((unsigned long long)min(r.k_cap, 0xFFFFFFu) << 8) | (unsigned)O;
+                        lds = 0;  // (never launched)
+                    } else {
+                        nbytes += feat::spill_bytes(own);
+                    }
+                }
+                if (live) gl[group] = (int32_t)lds;
+            }
             if (live) {
                 mx_k = (int32_t)r.k_cap, mx_o = O, mx_f = F, mx_l = (int32_t)nl;
                 if (cls == ADH_CLASS_GENERIC) gx_k = mx_k, gx_o = mx_o, gx_f = mx_f, gx_l = mx_l;
@@ -217,8 +257,10 @@ __global__ __launch_bounds__(256) void adh_plan_rec_kernel(DevCands c, const dou
     plan::raise_max(&meta->gen_o, gx_o);
     plan::raise_max(&meta->gen_f, gx_f);
     plan::raise_max(&meta->gen_n_lib, gx_l);
+    for (int g = 0; g < ADH_GENERIC_GROUPS; ++g) plan::raise_max(&meta->gen_lds[g], gl[g]);
+    plan::raise_max64(&meta->gen_over, over);
     if (!live) return;
-    const uint32_t key = (uint32_t)cls * (uint32_t)p.n_cyc_bins + min(bin, (uint32_t)p.n_cyc_bins - 1u);
+    const uint32_t key = (uint32_t)(cls + (cls == ADH_CLASS_GENERIC ? group : 0)) * (uint32_t)p.n_cyc_bins + min(bin, (uint32_t)p.n_cyc_bins - 1u);
     recs[j] = r;
     keys[j] = key;
     idx[j] = (uint32_t)j;
@@ -373,7 +415,7 @@ __global__ void adh_plan_order_kernel(const Rec *__restrict__ recs, const uint32
     const int cp = j > 0 ? (int)(sorted_keys[j - 1] / n_cyc_bins) : -1;
     for (int c = cp + 1; c <= cj; ++c) meta->class_first[c] = (uint32_t)j;
     if (j == n - 1) {
-        for (int c = cj + 1; c <= ADH_N_CLASSES; ++c) meta->class_first[c] = (uint32_t)n;
+        for (int c = cj + 1; c <= ADH_N_SORT_CLASSES; ++c) meta->class_first[c] = (uint32_t)n;
         meta->scratch_bytes = offs[j] + sorted_bytes[j];
     }
 }

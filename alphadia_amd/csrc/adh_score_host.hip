@@ -296,14 +296,15 @@ int plan_reserve(adh_handle *h, PlanSlot &s, int64_t n, bool im) {
 
 struct PlanKey {
     uint32_t top_k_fragments, top_k_isotopes;
-    bool fast_cfg, quant_all, fused_cfg, wide_cfg;
+    bool fast_cfg, quant_all, fused_cfg, wide_cfg, spill_all;
 };
 
 PlanKey plan_key(const adh_scoring_config_t *cfg) {
     const bool fast = cfg->experimental_xic != 0 && !getenv("ADH_DEBUG_NO_FAST");
     return PlanKey{cfg->top_k_fragments, cfg->top_k_isotopes, fast, cfg->quant_all != 0,
                    fast && !getenv("ADH_DEBUG_NO_FUSED"),   // developer switches: two-kernel path only
-                   fast && !getenv("ADH_DEBUG_NO_WIDE")};   // ... more than 16 kept fragments through the generic kernel
+                   fast && !getenv("ADH_DEBUG_NO_WIDE"),    // ... more than 16 kept fragments through the generic kernel
+                   getenv("ADH_DEBUG_GENERIC_SPILL") != nullptr};  // ... every generic candidate through the spill instantiation
 }
 
 // enqueue the plan of rows [row0, row0 + n) on `st`; plan_finish() waits for it
@@ -320,6 +321,7 @@ int plan_enqueue(adh_handle *h, PlanSlot &s, const adh_scoring_config_t *cfg, in
     p.top_k = cfg->top_k_fragments;
     p.fast_cfg = (key.fast_cfg ? 1 : 0) | (key.wide_cfg ? 2 : 0);
     p.quant_all = key.quant_all ? 1 : 0;
+    p.spill_all = key.spill_all ? 1 : 0;
     p.fused_cfg = (key.fused_cfg && !im && h->run.n_ms1_obs == 1 && p.I <= 4) ? (getenv("ADH_DEBUG_NO_FUSED2") ? 1 : 3) : 0;
     const unsigned blocks = (unsigned)((n + 255) / 256);
     hipLaunchKernelGGL(adh_plan_init_kernel, dim3(1), dim3(1), 0, st, s.d_meta, p.I);
@@ -328,9 +330,9 @@ int plan_enqueue(adh_handle *h, PlanSlot &s, const adh_scoring_config_t *cfg, in
     p.L = L;
     p.n_frames = n_frames;
     p.n_cyc_bins = (int32_t)std::min<int64_t>(n_frames / L + 2, 1 << 26);
-    // counting sort when the key space is small next to the batch (the usual case: 18 classes x
+    // counting sort when the key space is small next to the batch (the usual case: the sort classes x
     // cycles of the run); a stable radix sort otherwise
-    const int64_t n_keys = (int64_t)ADH_N_CLASSES * p.n_cyc_bins;
+    const int64_t n_keys = (int64_t)ADH_N_SORT_CLASSES * p.n_cyc_bins;
     const bool counting = n_keys <= (1 << 22) && !getenv("ADH_DEBUG_PLAN_RADIX");
     if (counting) {
         if (s.hist_cap < n_keys + 1) {
@@ -418,8 +420,15 @@ int plan_finish(adh_handle *h, PlanSlot &s, const adh_scoring_config_t *cfg, int
     p.d_recs = h->tims_staged ? nullptr : static_cast<CandRec *>(s.ordered);
     p.d_recs_im = h->tims_staged ? static_cast<CandRecIM *>(s.ordered) : nullptr;
     for (int c = 0; c < ADH_N_CLASSES; ++c) p.n_class[c] = (int64_t)m.class_first[c + 1] - (int64_t)m.class_first[c];
+    // the launch groups of the generic class are consecutive sort classes: one class to everything outside the plan
+    p.n_class[ADH_CLASS_GENERIC] = (int64_t)m.class_first[ADH_N_SORT_CLASSES] - (int64_t)m.class_first[ADH_CLASS_GENERIC];
+    for (int g = 0; g < ADH_GENERIC_GROUPS; ++g) {
+        p.n_generic[g] = (int64_t)m.class_first[ADH_CLASS_GENERIC + g + 1] - (int64_t)m.class_first[ADH_CLASS_GENERIC + g];
+        p.lds_generic[g] = m.gen_lds[g];
+    }
+    p.generic_over = m.gen_over;
+    p.spill_all = key.spill_all;
     p.caps_all = Caps{m.all_k, m.all_o, m.all_f, std::max(I, 1), m.all_n_lib, 0, m.all_s, m.all_op};
-    p.caps_generic = h->tims_staged ? p.caps_all : Caps{m.gen_k, m.gen_o, m.gen_f, std::max(I, 1), m.gen_n_lib, 0, 1, 1};
     p.scratch_bytes = std::max<uint64_t>(m.scratch_bytes, 32);
     p.top_k_fragments = key.top_k_fragments;
     p.top_k_isotopes = key.top_k_isotopes;
@@ -699,6 +708,16 @@ int launch_scoring_im(adh_handle *h, Plan &p, const adh_scoring_config_t *cfg, a
 int launch_scoring(adh_handle *h, Plan &p, const adh_scoring_config_t *cfg, adh_output_t *out, hipStream_t st) {
     if (h->timed.size() > 48) fold_timed(h, false);
     if (p.n == 0) return ADH_OK;
+    if (!h->tims_staged && p.generic_over != 0) {
+        // even the spill path keeps everything indexed by K * O and K in LDS (feat::Layout with spill = true): refused
+        // before anything is launched or counted
+        char buf[256];
+        snprintf(buf, sizeof(buf),
+                 "candidate needs %llu bytes of LDS on the spill path of the generic kernel (K=%llu O=%llu): exceeds the bound of %d bytes",
+                 (unsigned long long)(p.generic_over >> 32), (unsigned long long)((p.generic_over >> 8) & 0xFFFFFFu),
+                 (unsigned long long)(p.generic_over & 0xFFu), (int)ADH_GENERIC_LDS_LIMIT);
+        return fail(ADH_ERR_UNSUPPORTED, buf);
+    }
     for (int c = 0; c < ADH_N_CLASSES; ++c) h->class_counts[c] += p.n_class[c];
     if (h->tims_staged) return launch_scoring_im(h, p, cfg, out, st);
     if (cfg->collect_fragments && p.caps_all.k > out->top_k)
@@ -709,14 +728,6 @@ int launch_scoring(adh_handle *h, Plan &p, const adh_scoring_config_t *cfg, adh_
     Caps gcaps = p.caps_all;
     if (const char *dbg = getenv("ADH_DEBUG_GATHER")) gcaps.stop_phase = atoi(dbg);
     const size_t g_lds = adh_gather_lds_bytes(gcaps, h->run.n_ms1_obs);
-    p.caps_generic.stop_phase = stop_phase;
-    const size_t f_lds = adh_feature_lds_bytes(p.caps_generic);
-    if (p.n_class[ADH_CLASS_GENERIC] > 0 && f_lds > 160 * 1024) {
-        char buf[256];
-        snprintf(buf, sizeof(buf), "candidate tile needs %zu bytes of LDS (K=%d O=%d F=%d): exceeds 160 KiB", f_lds,
-                 p.caps_generic.k, p.caps_generic.o, p.caps_generic.f);
-        return fail(ADH_ERR_UNSUPPORTED, buf);
-    }
     if (g_lds > 160 * 1024) return fail(ADH_ERR_UNSUPPORTED, "library slice / MS1 tile too large for the gather kernel");
     int rc = ensure_scratch(h, p.scratch_bytes);
     if (rc != ADH_OK) return rc;
@@ -862,8 +873,25 @@ int launch_scoring(adh_handle *h, Plan &p, const adh_scoring_config_t *cfg, adh_
             if (!wide_class && p.n_class[c] > 0 && (c == ADH_CLASS_GENERIC ? run_generic : run_fast)) {
                 const CandRec *recs = p.d_recs + first;
                 if (c == ADH_CLASS_GENERIC) {
-                    hipLaunchKernelGGL(adh_feature_kernel, dim3((unsigned)p.n_class[c]), dim3(ADH_WAVE), f_lds, st, h->run, recs,
-                                       h->cs.iso, n_iso, *cfg, d_scratch, *out, p.caps_generic);
+                    // one launch per group of own layouts, each with the LDS of its largest candidate; the last group
+                    // keeps its tile planes in the spill blocks of the scratch slab
+                    int64_t at = 0;
+                    for (int g = 0; g < ADH_GENERIC_GROUPS; ++g) {
+                        const int64_t ng = p.n_generic[g];
+                        if (ng == 0) continue;
+                        const size_t lds = (size_t)p.lds_generic[g];
+                        if (g == ADH_GENERIC_GROUP_SPILL)
+                            hipLaunchKernelGGL(adh_feature_kernel<true>, dim3((unsigned)ng), dim3(ADH_WAVE), lds, st, h->run,
+                                               recs + at, h->cs.iso, n_iso, *cfg, d_scratch, d_scratch, *out, (int32_t)stop_phase);
+                        else
+                            hipLaunchKernelGGL(adh_feature_kernel<false>, dim3((unsigned)ng), dim3(ADH_WAVE), lds, st, h->run,
+                                               recs + at, h->cs.iso, n_iso, *cfg, d_scratch, (unsigned char *)nullptr, *out,
+                                               (int32_t)stop_phase);
+                        HIP_TRY(hipGetLastError());
+                        h->generic_stats[g] += ng;
+                        h->generic_stats[ADH_GENERIC_GROUPS + g] = std::max<int64_t>(h->generic_stats[ADH_GENERIC_GROUPS + g], (int64_t)lds);
+                        at += ng;
+                    }
                 } else {
                     const unsigned blocks = (unsigned)((p.n_class[c] + per_block - 1) / per_block);
                     const int32_t nc = (int32_t)p.n_class[c];
@@ -1076,7 +1104,8 @@ int adh_score_uploaded(adh_handle_t *h, const adh_scoring_config_t *cfg, adh_out
     Plan &p = h->plan;
     const PlanKey key = plan_key(cfg);
     if (!(p.ready && p.top_k_fragments == key.top_k_fragments && p.top_k_isotopes == key.top_k_isotopes &&
-          p.fast_ok == key.fast_cfg && p.fused_ok == key.fused_cfg && p.wide_ok == key.wide_cfg && p.quant_all == key.quant_all)) {
+          p.fast_ok == key.fast_cfg && p.fused_ok == key.fused_cfg && p.wide_ok == key.wide_cfg && p.quant_all == key.quant_all &&
+          p.spill_all == key.spill_all)) {
         p = Plan();
         rc = plan_enqueue(h, h->slots[0], cfg, 0, h->cs.n, st);
         if (rc == ADH_OK) rc = plan_finish(h, h->slots[0], cfg, 0, h->cs.n, p);
@@ -1118,6 +1147,15 @@ int adh_plan_class_counts(adh_handle_t *h, int64_t *counts, int32_t reset) {
     for (int c = 0; c < ADH_N_CLASSES; ++c) {
         counts[c] = h->class_counts[c];
         if (reset) h->class_counts[c] = 0;
+    }
+    return ADH_OK;
+}
+
+int adh_generic_launch_stats(adh_handle_t *h, int64_t *stats, int32_t reset) {
+    if (!h || !stats) return fail(ADH_ERR_INVALID_ARGUMENT, "NULL argument");
+    for (int i = 0; i < 2 * ADH_GENERIC_GROUPS; ++i) {
+        stats[i] = h->generic_stats[i];
+        if (reset) h->generic_stats[i] = 0;
     }
     return ADH_OK;
 }

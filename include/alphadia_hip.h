@@ -465,6 +465,20 @@ int adh_kernel_time_ms(adh_handle_t *handle, double *gather_ms, double *feature_
  */
 int adh_plan_class_counts(adh_handle_t *handle, int64_t *counts, int32_t reset);
 
+/*
+ * Launch groups of the generic class (36) of an AlphaRaw plan.  Its candidates are launched in three groups
+ * by the LDS layout each one needs on its own (fragments kept x observations x cycles):
+ *   group 0  layouts up to 38 784 bytes (several blocks share a CU)
+ *   group 1  layouts up to 161 664 bytes (160 KiB less the kernel's 2 176 bytes of static LDS)
+ *   group 2  larger ones: the spill instantiation, with the [K][O][F] tile planes in the scratch slab
+ * `stats[0..2]`: candidates per group of every plan whose generic kernels were launched on the handle since
+ * the last reset, summed over chunks and entry points; `stats[3..5]`: the largest dynamic LDS (bytes) any such
+ * launch of the group asked for.  Read-only host counters: tests prove with them which path ran.
+ * ADH_DEBUG_GENERIC_SPILL (set to any value) sends every generic candidate to group 2.
+ */
+#define ADH_GENERIC_LAUNCH_STATS 6
+int adh_generic_launch_stats(adh_handle_t *handle, int64_t *stats, int32_t reset);
+
 /* ------------------------------------------------------------------------
  * Multi-GPU: one process per GPU, candidates sharded by contiguous score-group ranges
  * (score groups are independent, search/scoring/containers/score_group.py:66-75), ONE RCCL
