@@ -1345,6 +1345,143 @@ def golden_selection_cycles():
           f"{os.path.getsize(path)/2**20:.2f} MiB")
 
 
+SELECTION_CFG_KEYS = ("rt_tolerance precursor_mz_tolerance fragment_mz_tolerance candidate_count "
+                      "top_k_precursors exclude_shared_ions kernel_size f_mobility f_rt center_fraction "
+                      "min_size_mobility min_size_rt max_size_mobility max_size_rt use_weighted_score "
+                      "join_close_candidates join_close_candidates_scan_threshold "
+                      "join_close_candidates_cycle_threshold").split()
+SELECTION_CFG_KEYS_IM = SELECTION_CFG_KEYS + ("mobility_tolerance sigma_scale_rt sigma_scale_mobility peak_len_rt "
+                                              "peak_len_mobility").split()
+SELECTION_OUT_COLS = ("precursor_idx rank score scan_center scan_start scan_stop frame_center frame_start "
+                      "frame_stop elution_group_idx decoy").split()
+
+
+def _run_reference_selection(d, name, dia, library, updates, cfg_keys):
+    """CandidateSelection.__call__ of the reference with `updates` on its default config; kernel, config fields and
+    output columns go to d under `name`_kernel / `name`_cfg_* / `name`_out_*.  -> the candidate table."""
+    from alphadia.search.selection import selection as ref_sel
+    from alphadia.search.selection.config_df import CandidateSelectionConfig
+
+    cfg = CandidateSelectionConfig()
+    cfg.update(updates)
+    cs = ref_sel.CandidateSelection(
+        dia, library.precursor_df.copy(), library.fragment_df.copy(), cfg,
+        rt_column="rt_library", mobility_column="mobility_library",
+        precursor_mz_column="mz_library", fragment_mz_column="mz_library",
+        fwhm_rt=cfg.peak_len_rt, fwhm_mobility=cfg.peak_len_mobility,
+    )
+    df = cs(thread_count=1)
+    d[f"{name}_kernel"] = np.asarray(cs.kernel, dtype=np.float32)
+    cj = cs.config_jit
+    for k in cfg_keys:
+        d[f"{name}_cfg_{k}"] = np.asarray(getattr(cj, k))
+    for k in ("feature_mean", "feature_std", "feature_weight"):
+        d[f"{name}_cfg_{k}"] = np.asarray(getattr(cj, k), dtype=np.float64)
+    for c in SELECTION_OUT_COLS:
+        d[f"{name}_out_{c}"] = df[c].values
+    return df
+
+
+def share_fragments(library, fraction: float, seed: int) -> None:
+    """Cardinality 2 for that share of the fragments (exclude_shared_ions drops them), from a stream of its own."""
+    card = library.fragment_df["cardinality"].values.copy()
+    card[np.random.default_rng([seed, 23]).random(card.size) < fraction] = 2
+    library.fragment_df["cardinality"] = card
+
+
+# candidate selection at the limits of the selection kernels (tests/test_selection_limits_gpu.py): libraries of 4 ... 60
+# fragments per precursor (the reference takes every fragment of the slice, selection.py:120-137), a fifth of them
+# shared, up to 16 candidates per precursor, a smoothing kernel of 16 cycles
+# (tolerances of 50 ppm on a narrow m/z range: no tile has a stretch of cycles without any signal, in which only the
+# noise of the reference's float32 FFT would make peaks - equal scores, ordered by an unstable sort)
+SELECTION_LIMITS = {
+    # every precursor's tile is the whole run: far more than 16 peaks compete for the 16 ranks
+    "many": dict(rt_tolerance=500.0, candidate_count=16, top_k_precursors=4, exclude_shared_ions=True, min_size_rt=2,
+                 join_close_candidates=False, precursor_mz_tolerance=50.0, fragment_mz_tolerance=50.0),
+    "k16": dict(rt_tolerance=40.0, kernel_size=16, candidate_count=8, top_k_precursors=1, min_size_rt=2,
+                join_close_candidates=True, precursor_mz_tolerance=50.0, fragment_mz_tolerance=50.0),
+}
+
+
+def selection_limits_case() -> syn.SyntheticCase:
+    case = small_case(129, n_precursors=120, n_cycles=260, per_precursor=1, n_ms2=4, ms1_peaks=110, ms2_peaks=55,
+                      frag_mz_hi=260, ms2_mz_range=(195, 265), planted_fraction=0.7, amplitude=0.3,
+                      few_fragment_fraction=0.0, k_fragments=(4, 60))
+    share_fragments(case.library, 0.2, 129)
+    return case
+
+
+def golden_selection_limits():
+    """CandidateSelection.__call__ (as golden_selection, same FFT stand-in) on a run of 260 cycles with 4 ... 60
+    fragments per precursor, the settings of SELECTION_LIMITS."""
+    import ref_shim
+
+    ref_shim.install_selection_glue()
+    case = selection_limits_case()
+    d = case_to_dict(case)
+    d["caveat"] = np.asarray(CAVEAT)
+    for name, upd in SELECTION_LIMITS.items():
+        df = _run_reference_selection(d, name, DuckDia(case.dia), case.library, upd, SELECTION_CFG_KEYS)
+        per = df.groupby("precursor_idx").size()
+        print(name, len(df), "candidates for", len(per), "precursors;", int((per == upd["candidate_count"]).sum()),
+              "with every rank filled")
+        assert len(df) > 300
+    n_frag = (case.library.precursor_df.flat_frag_stop_idx - case.library.precursor_df.flat_frag_start_idx).values
+    assert n_frag.min() == 4 and n_frag.max() == 60 and (n_frag > 16).sum() > 60
+    path = os.path.join(OUT_DIR, "selection_limits.npz")
+    np.savez_compressed(path, **d)
+    print(path, f"{os.path.getsize(path)/2**20:.2f} MiB")
+
+
+# ion mobility: 4 ... 60 fragments and 4 isotopes give 8 ... 64 m/z windows per precursor.  A coarse TOF axis (1 200
+# bins) and windows of +-300 ppm: every tile (the whole scan range, 32 cycles) is full enough that no stretch of it is
+# without signal (see SELECTION_LIMITS).  "wide": fragment windows of +-800 ppm, with which about half the precursors
+# queue more events in one window than its sort list takes (512), and the other half do not
+_TIMSTOF_LIMITS = dict(rt_tolerance=3.0, mobility_tolerance=0.6, candidate_count=16, top_k_precursors=4, min_size_rt=2,
+                       peak_len_rt=1.2, sigma_scale_rt=0.5, peak_len_mobility=0.05, sigma_scale_mobility=1.0,
+                       max_size_mobility=20, precursor_mz_tolerance=300.0, fragment_mz_tolerance=300.0)
+SELECTION_TIMSTOF_LIMITS = {
+    "many": dict(_TIMSTOF_LIMITS, join_close_candidates=False),
+    "wide": dict(_TIMSTOF_LIMITS, fragment_mz_tolerance=800.0),
+}
+
+
+def selection_timstof_limits_case() -> syn.TimsTOFCase:
+    return syn.make_timstof_case(n_precursors=60, n_cycles=34, config_id=132, per_precursor=1, n_ms2_frames=3,
+                                 windows_per_frame=2, scan_max_index=64, planted_fraction=0.4, n_tof=1200,
+                                 events_per_push=17.0, k_fragments=(4, 60))
+
+
+def golden_selection_timstof_limits():
+    """CandidateSelection.__call__ on a small ion-mobility run (as golden_selection_timstof) with 4 ... 60 fragments
+    per precursor, the settings of SELECTION_TIMSTOF_LIMITS."""
+    import ref_shim
+
+    ref_shim.install_selection_glue()
+    case = selection_timstof_limits_case()
+    d = {"tims_" + c: getattr(case.dia, c) for c in TIMS_COLS}
+    d["tims_scan_max_index"] = np.asarray(case.dia.scan_max_index)
+    d["tims_zeroth_frame"] = np.asarray(case.dia.zeroth_frame)
+    for c in FRAG_COLS:
+        d["frag_" + c] = case.library.fragment_df[c].values
+    for c in PREC_NUM_COLS:
+        d["prec_" + c] = case.library.precursor_df[c].values
+    d["caveat"] = np.asarray(CAVEAT)
+    for name, upd in SELECTION_TIMSTOF_LIMITS.items():
+        dia = DuckTims(case.dia)
+        dia.has_mobility = True
+        df = _run_reference_selection(d, name, dia, case.library, upd, SELECTION_CFG_KEYS_IM)
+        per = df.groupby("precursor_idx").size()
+        print(name, len(df), "candidates for", len(per), "precursors; per precursor", np.bincount(per.values),
+              "kernel", d[f"{name}_kernel"].shape)
+        assert len(df) > 150
+    n_frag = (case.library.precursor_df.flat_frag_stop_idx - case.library.precursor_df.flat_frag_start_idx).values
+    assert n_frag.min() == 4 and n_frag.max() == 60 and (n_frag > 28).sum() >= 20  # (W = 8 ... 64 with four isotopes)
+    path = os.path.join(OUT_DIR, "selection_timstof_limits.npz")
+    np.savez_compressed(path, **d)
+    print(path, f"{os.path.getsize(path)/2**20:.2f} MiB")
+
+
 def golden_timstof_cycles():
     """Full scoring (handler defaults) on an ion-mobility run with two MS1 frames per cycle and every MS2 frame
     three times per cycle: two unfragmented observations, three and more fragment observations per candidate."""
@@ -1455,6 +1592,12 @@ if __name__ == "__main__":
     if "--selection-only" in sys.argv:
         golden_selection()
         sys.exit(0)
+    if "--selection-limits-only" in sys.argv:
+        golden_selection_limits()
+        sys.exit(0)
+    if "--selection-timstof-limits-only" in sys.argv:
+        golden_selection_timstof_limits()
+        sys.exit(0)
     if "--small-only" in sys.argv:
         golden_get_dense()
         golden_fragcomp()
@@ -1508,3 +1651,5 @@ if __name__ == "__main__":
     golden_selection_cycles()
     golden_timstof_cycles()
     golden_boxes_timstof()
+    golden_selection_limits()
+    golden_selection_timstof_limits()

@@ -819,13 +819,15 @@ def make_timstof_case(
     sorted_noise: bool = False,
     threads: int = 16,
     cycle: np.ndarray | None = None,
+    k_fragments: int | tuple = 12,
 ) -> TimsTOFCase:
     """Run "B" of SURVEY.md section 8(d) at a configurable (test) scale.
 
     ``sorted_noise``: draw the noise events already in (TOF, push) order - order statistics of uniform keys
     as cumulative sums of exponential gaps, TOF range by TOF range on ``threads`` threads - instead of
     drawing and lexsorting them: the full-size run (5e8 events) in seconds instead of minutes.  Another
-    random stream, hence another run: the committed fixtures use the default."""
+    random stream, hence another run: the committed fixtures use the default.
+    ``k_fragments``: as in ``make_library`` (a count, or (lo, hi) drawn per precursor from a stream of its own)."""
     seed = BASE_SEED + config_id if seed is None else seed
     rng = np.random.default_rng([seed, 7])
     if cycle is None:
@@ -841,7 +843,7 @@ def make_timstof_case(
     mz_table = (np.sqrt(tof_mz_lo) + t * (np.sqrt(tof_mz_hi) - np.sqrt(tof_mz_lo)) / (n_tof - 1)) ** 2
 
     lib = make_library(n_precursors, seed, mz_lo=mz_lo, mz_hi=mz_hi, rt_max=float(rt[-1]),
-                       frag_mz_lo=frag_mz_lo, frag_mz_hi=frag_mz_hi)
+                       frag_mz_lo=frag_mz_lo, frag_mz_hi=frag_mz_hi, k_fragments=k_fragments)
     pdf, fdf = lib.precursor_df, lib.fragment_df
     pdf["mobility_library"] = rng.uniform(0.7, 1.5, n_precursors).astype(np.float32)
 
