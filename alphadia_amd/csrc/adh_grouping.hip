@@ -20,18 +20,19 @@
 //                are sorted once by (pattern, rank) and come back as a CSR of id codes per pattern.
 //
 // No kernel here waits for another workgroup: kernel boundaries are the only global synchronisation, and the round
-// loop of the labelling is bounded (kMaxRounds).  Included by adh_api.hip (shares its error helpers and the handle).
+// loop of the labelling is bounded (kMaxRounds).  Included by adh_api.hip behind adh_session.h (shares its error
+// helpers, the handle and the session helpers).
 
 struct adh_pg {
     adh_handle_t *h = nullptr;
-    std::vector<void *> bufs;  // the device buffers of the last solve
+    sess::DevBufs bufs;  // the device buffers of the last solve and of the filters since
     bool solved = false;
     int32_t P = 0, I = 0;
     int64_t E = 0;
     uint64_t *pkey = nullptr;       // the edges as pattern << 32 | id, ascending
     uint32_t *is_master = nullptr;  // [I]
     int32_t n_comp = 0, n_large = 0, rounds = 0;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    sess::EventPair ev;
     double label_ms = 0.0, cover_ms = 0.0, filter_ms = 0.0;
 };
 
@@ -44,50 +45,7 @@ constexpr int kCoverBlock = 1024;
 constexpr int kLdsIds = 8192;   // set sizes of a larger component live in global memory
 constexpr int kJump = 32;       // pointer-jumping steps of one launch
 constexpr int kMaxRounds = 256;
-
-inline unsigned grid_for(int64_t n) {
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + kBlock - 1) / kBlock, 16384));
-}
-
-void release(adh_pg *g) {
-    for (void *p : g->bufs)
-        if (p) (void)hipFree(p);
-    g->bufs.clear();
-    g->pkey = nullptr;
-    g->is_master = nullptr;
-    g->solved = false;
-}
-
-template <typename T>
-hipError_t alloc(adh_pg *g, T **p, size_t n) {
-    void *v = nullptr;
-    hipError_t e = hipMalloc(&v, std::max<size_t>(n, 4) * sizeof(T));
-    if (e != hipSuccess) return e;
-    g->bufs.push_back(v);
-    *p = static_cast<T *>(v);
-    return hipSuccess;
-}
-
-template <typename F>
-int timed(adh_pg *g, double &ms, F &&body) {
-    hipStream_t st = g->h->stream;
-    if (!g->e0) HIP_TRY(hipEventCreate(&g->e0));
-    if (!g->e1) HIP_TRY(hipEventCreate(&g->e1));
-    HIP_TRY(hipEventRecord(g->e0, st));
-    const int rc = body();
-    if (rc != ADH_OK) return rc;
-    HIP_TRY(hipEventRecord(g->e1, st));
-    HIP_TRY(hipEventSynchronize(g->e1));
-    float f = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&f, g->e0, g->e1));
-    ms = f;
-    return ADH_OK;
-}
-
-__global__ void __launch_bounds__(kBlock) iota_kernel(uint32_t *__restrict__ v, int64_t n) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) v[i] = (uint32_t)i;
-}
+using sess::grid_for;
 
 // both sort keys of every edge and the degree of its two ends
 __global__ void __launch_bounds__(kBlock) keys_kernel(const int32_t *__restrict__ ep, const int32_t *__restrict__ ei,
@@ -323,37 +281,6 @@ __global__ void __launch_bounds__(kBlock) filter_key_kernel(const uint64_t *__re
     }
 }
 
-template <typename T>
-int exclusive_scan(adh_pg *g, T *v, int64_t n, void **tmp, size_t *tmp_bytes) {
-    hipStream_t st = g->h->stream;
-    size_t need = 0;
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, v, v, (int)n, st));
-    if (need > *tmp_bytes) {
-        unsigned char *t = nullptr;
-        HIP_TRY(alloc(g, &t, need));
-        *tmp = t;
-        *tmp_bytes = need;
-    }
-    need = *tmp_bytes;
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(*tmp, need, v, v, (int)n, st));
-    return ADH_OK;
-}
-
-int sort_keys(adh_pg *g, const uint64_t *in, uint64_t *out, int64_t n, void **tmp, size_t *tmp_bytes) {
-    hipStream_t st = g->h->stream;
-    size_t need = 0;
-    HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, need, in, out, (int)n, 0, 64, st));
-    if (need > *tmp_bytes) {
-        unsigned char *t = nullptr;
-        HIP_TRY(alloc(g, &t, need));
-        *tmp = t;
-        *tmp_bytes = need;
-    }
-    need = *tmp_bytes;
-    HIP_TRY(hipcub::DeviceRadixSort::SortKeys(*tmp, need, in, out, (int)n, 0, 64, st));
-    return ADH_OK;
-}
-
 }  // namespace pg
 
 extern "C" {
@@ -370,10 +297,7 @@ int adh_pg_destroy(adh_pg_t *g) {
     if (!g) return ADH_OK;
     (void)hipSetDevice(g->h->device);
     (void)hipStreamSynchronize(g->h->stream);
-    pg::release(g);
-    if (g->e0) (void)hipEventDestroy(g->e0);
-    if (g->e1) (void)hipEventDestroy(g->e1);
-    delete g;
+    delete g;  // (the members free their device memory and events)
     return ADH_OK;
 }
 
@@ -398,7 +322,8 @@ int adh_pg_solve(adh_pg_t *g, int32_t n_patterns, int32_t n_ids, int64_t n_edges
     HIP_TRY(hipSetDevice(g->h->device));
     hipStream_t st = g->h->stream;
     HIP_TRY(hipStreamSynchronize(st));
-    pg::release(g);
+    g->bufs.release();
+    g->pkey = nullptr, g->is_master = nullptr, g->solved = false;
     g->P = n_patterns, g->I = n_ids, g->E = E;
     g->label_ms = g->cover_ms = g->filter_ms = 0.0;
     g->n_comp = g->n_large = g->rounds = 0;
@@ -408,50 +333,45 @@ int adh_pg_solve(adh_pg_t *g, int32_t n_patterns, int32_t n_ids, int64_t n_edges
     uint64_t *ikey_in = nullptr, *pkey_in = nullptr, *ikey = nullptr, *pkey = nullptr, *ckey_in = nullptr, *ckey = nullptr;
     uint32_t *ioff = nullptr, *poff = nullptr, *parent = nullptr, *flag = nullptr, *head = nullptr, *sorted_id = nullptr,
              *pos = nullptr, *comp_off = nullptr, *list = nullptr, *is_master = nullptr;
-    HIP_TRY(pg::alloc(g, &d_ep, (size_t)E));
-    HIP_TRY(pg::alloc(g, &d_ei, (size_t)E));
-    HIP_TRY(pg::alloc(g, &d_w, (size_t)P));
-    HIP_TRY(pg::alloc(g, &d_master, (size_t)P));
-    HIP_TRY(pg::alloc(g, &d_emptied, (size_t)I));
-    HIP_TRY(pg::alloc(g, &d_size, (size_t)I));
-    HIP_TRY(pg::alloc(g, &ikey_in, (size_t)E));
-    HIP_TRY(pg::alloc(g, &pkey_in, (size_t)E));
-    HIP_TRY(pg::alloc(g, &ikey, (size_t)E));
-    HIP_TRY(pg::alloc(g, &pkey, (size_t)E));
-    HIP_TRY(pg::alloc(g, &ckey_in, (size_t)I));
-    HIP_TRY(pg::alloc(g, &ckey, (size_t)I));
-    HIP_TRY(pg::alloc(g, &ioff, (size_t)I + 1));
-    HIP_TRY(pg::alloc(g, &poff, (size_t)P + 1));
-    HIP_TRY(pg::alloc(g, &parent, (size_t)N));
-    HIP_TRY(pg::alloc(g, &flag, 4));  // [0] a round changed something, [1] number of large components
-    HIP_TRY(pg::alloc(g, &head, (size_t)I));
-    HIP_TRY(pg::alloc(g, &sorted_id, (size_t)I));
-    HIP_TRY(pg::alloc(g, &pos, (size_t)I));
-    HIP_TRY(pg::alloc(g, &comp_off, (size_t)I + 1));
-    HIP_TRY(pg::alloc(g, &list, (size_t)I));
-    HIP_TRY(pg::alloc(g, &is_master, (size_t)I));
-    void *tmp = nullptr;
-    size_t tmp_bytes = 0;
-
-    HIP_TRY(hipMemcpyAsync(d_ep, edge_pattern, (size_t)E * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_ei, edge_id, (size_t)E * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_w, weight, (size_t)P * 4, hipMemcpyHostToDevice, st));
+    auto &B = g->bufs;
+    HIP_TRY(B.upload(&d_ep, edge_pattern, (size_t)E, st));
+    HIP_TRY(B.upload(&d_ei, edge_id, (size_t)E, st));
+    HIP_TRY(B.upload(&d_w, weight, (size_t)P, st));
+    HIP_TRY(B.alloc(&d_master, (size_t)P));
+    HIP_TRY(B.alloc(&d_emptied, (size_t)I));
+    HIP_TRY(B.alloc(&d_size, (size_t)I));
+    HIP_TRY(B.alloc(&ikey_in, (size_t)E));
+    HIP_TRY(B.alloc(&pkey_in, (size_t)E));
+    HIP_TRY(B.alloc(&ikey, (size_t)E));
+    HIP_TRY(B.alloc(&pkey, (size_t)E));
+    HIP_TRY(B.alloc(&ckey_in, (size_t)I));
+    HIP_TRY(B.alloc(&ckey, (size_t)I));
+    HIP_TRY(B.alloc(&ioff, (size_t)I + 1));
+    HIP_TRY(B.alloc(&poff, (size_t)P + 1));
+    HIP_TRY(B.alloc(&parent, (size_t)N));
+    HIP_TRY(B.alloc(&flag, 4));  // [0] a round changed something, [1] number of large components
+    HIP_TRY(B.alloc(&head, (size_t)I));
+    HIP_TRY(B.alloc(&sorted_id, (size_t)I));
+    HIP_TRY(B.alloc(&pos, (size_t)I));
+    HIP_TRY(B.alloc(&comp_off, (size_t)I + 1));
+    HIP_TRY(B.alloc(&list, (size_t)I));
+    HIP_TRY(B.alloc(&is_master, (size_t)I));
+    sess::BufsTmp tmp{B};  // hipCUB temporary storage: a superseded block stays in bufs, no free inside the call
 
     uint32_t n_comp = 0;
     int rounds = 0;
     bool converged = false;
-    int rc = pg::timed(g, g->label_ms, [&]() -> int {
+    int rc = sess::timed(g->ev, st, g->label_ms, [&]() -> int {
         HIP_TRY(hipMemsetAsync(ioff, 0, ((size_t)I + 1) * 4, st));
         HIP_TRY(hipMemsetAsync(poff, 0, ((size_t)P + 1) * 4, st));
         hipLaunchKernelGGL(pg::keys_kernel, dim3(pg::grid_for(E)), dim3(pg::kBlock), 0, st, d_ep, d_ei, E, ikey_in, pkey_in,
                            ioff, poff);
         HIP_TRY(hipGetLastError());
-        int r = pg::exclusive_scan(g, ioff, I + 1, &tmp, &tmp_bytes);
-        if (r == ADH_OK) r = pg::exclusive_scan(g, poff, P + 1, &tmp, &tmp_bytes);
-        if (r == ADH_OK) r = pg::sort_keys(g, ikey_in, ikey, E, &tmp, &tmp_bytes);
-        if (r == ADH_OK) r = pg::sort_keys(g, pkey_in, pkey, E, &tmp, &tmp_bytes);
-        if (r != ADH_OK) return r;
-        hipLaunchKernelGGL(pg::iota_kernel, dim3(pg::grid_for(N)), dim3(pg::kBlock), 0, st, parent, N);
+        ADH_TRY(sess::exclusive_sum(tmp, ioff, ioff, I + 1, st));
+        ADH_TRY(sess::exclusive_sum(tmp, poff, poff, P + 1, st));
+        ADH_TRY(sess::sort_keys(tmp, ikey_in, ikey, E, 64, st));
+        ADH_TRY(sess::sort_keys(tmp, pkey_in, pkey, E, 64, st));
+        hipLaunchKernelGGL(sess::iota_kernel, dim3(pg::grid_for(N)), dim3(pg::kBlock), 0, st, parent, N);
         HIP_TRY(hipGetLastError());
         while (rounds < pg::kMaxRounds) {
             ++rounds;
@@ -473,20 +393,10 @@ int adh_pg_solve(adh_pg_t *g, int32_t n_patterns, int32_t n_ids, int64_t n_edges
         // the ids by (component, id code); a component's label is its smallest node, an id
         hipLaunchKernelGGL(pg::comp_key_kernel, dim3(pg::grid_for(I)), dim3(pg::kBlock), 0, st, parent, I, ckey_in);
         HIP_TRY(hipGetLastError());
-        r = pg::sort_keys(g, ckey_in, ckey, I, &tmp, &tmp_bytes);
-        if (r != ADH_OK) return r;
+        ADH_TRY(sess::sort_keys(tmp, ckey_in, ckey, I, 64, st));
         hipLaunchKernelGGL(pg::comp_head_kernel, dim3(pg::grid_for(I)), dim3(pg::kBlock), 0, st, ckey, I, head);
         HIP_TRY(hipGetLastError());
-        size_t need = 0;
-        HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, need, head, head, (int)I, st));
-        if (need > tmp_bytes) {
-            unsigned char *t = nullptr;
-            HIP_TRY(pg::alloc(g, &t, need));
-            tmp = t;
-            tmp_bytes = need;
-        }
-        need = tmp_bytes;
-        HIP_TRY(hipcub::DeviceScan::InclusiveSum(tmp, need, head, head, (int)I, st));
+        ADH_TRY(sess::inclusive_sum(tmp, head, head, I, st));
         HIP_TRY(hipMemcpyAsync(&n_comp, head + (I - 1), 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         return ADH_OK;
@@ -500,7 +410,7 @@ int adh_pg_solve(adh_pg_t *g, int32_t n_patterns, int32_t n_ids, int64_t n_edges
 
     uint32_t n_large = 0;
     pg::Graph gr{ioff, ikey, poff, pkey, d_w, pos, d_master, d_emptied, is_master};
-    rc = pg::timed(g, g->cover_ms, [&]() -> int {
+    rc = sess::timed(g->ev, st, g->cover_ms, [&]() -> int {
         HIP_TRY(hipMemsetAsync(d_master, 0xFF, (size_t)P * 4, st));
         HIP_TRY(hipMemsetAsync(d_emptied, 0xFF, (size_t)I * 4, st));
         HIP_TRY(hipMemsetAsync(is_master, 0, (size_t)I * 4, st));
@@ -553,24 +463,23 @@ int adh_pg_filter(adh_pg_t *g, int32_t n_strings, const int32_t *id_string, cons
     int32_t *d_str = nullptr, *d_rank = nullptr;
     uint32_t *allowed = nullptr, *count = nullptr, *val_in = nullptr, *val = nullptr;
     uint64_t *key_in = nullptr, *key = nullptr;
-    HIP_TRY(pg::alloc(g, &d_str, (size_t)I));
-    HIP_TRY(pg::alloc(g, &d_rank, (size_t)I));
-    HIP_TRY(pg::alloc(g, &allowed, (size_t)S));
-    HIP_TRY(pg::alloc(g, &count, (size_t)P + 1));
-    HIP_TRY(pg::alloc(g, &val_in, (size_t)E));
-    HIP_TRY(pg::alloc(g, &val, (size_t)E));
-    HIP_TRY(pg::alloc(g, &key_in, (size_t)E));
-    HIP_TRY(pg::alloc(g, &key, (size_t)E));
-    size_t sort_bytes = 0;
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, key_in, key, val_in, val, (int)E, 0, 64, st));
-    unsigned char *sort_tmp = nullptr;
-    HIP_TRY(pg::alloc(g, &sort_tmp, sort_bytes));
-    void *tmp = nullptr;
-    size_t tmp_bytes = 0;
-    HIP_TRY(hipMemcpyAsync(d_str, id_string, (size_t)I * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_rank, id_rank, (size_t)I * 4, hipMemcpyHostToDevice, st));
+    auto &B = g->bufs;
+    HIP_TRY(B.upload(&d_str, id_string, (size_t)I, st));
+    HIP_TRY(B.upload(&d_rank, id_rank, (size_t)I, st));
+    HIP_TRY(B.alloc(&allowed, (size_t)S));
+    HIP_TRY(B.alloc(&count, (size_t)P + 1));
+    HIP_TRY(B.alloc(&val_in, (size_t)E));
+    HIP_TRY(B.alloc(&val, (size_t)E));
+    HIP_TRY(B.alloc(&key_in, (size_t)E));
+    HIP_TRY(B.alloc(&key, (size_t)E));
+    // (the sort's temporary storage is in place before the timed part)
+    sess::TmpSize sort;
+    ADH_TRY(sess::sort_pairs(sort, key_in, key, val_in, val, E, 64, st));
+    sess::BufsTmp sort_tmp{B}, scan_tmp{B};
+    HIP_TRY(sort_tmp.reserve(sort.bytes));
     uint32_t kept = 0;
-    int rc = pg::timed(g, g->filter_ms, [&]() -> int {
+    g->filter_ms = 0.0;
+    int rc = sess::timed(g->ev, st, g->filter_ms, [&]() -> int {
         HIP_TRY(hipMemsetAsync(allowed, 0, (size_t)S * 4, st));
         HIP_TRY(hipMemsetAsync(count, 0, ((size_t)P + 1) * 4, st));
         hipLaunchKernelGGL(pg::allow_kernel, dim3(pg::grid_for(I)), dim3(pg::kBlock), 0, st, g->is_master, d_str, I, allowed);
@@ -578,10 +487,8 @@ int adh_pg_filter(adh_pg_t *g, int32_t n_strings, const int32_t *id_string, cons
         hipLaunchKernelGGL(pg::filter_key_kernel, dim3(pg::grid_for(E)), dim3(pg::kBlock), 0, st, g->pkey, E, d_str, d_rank,
                            allowed, key_in, val_in, count);
         HIP_TRY(hipGetLastError());
-        const int r = pg::exclusive_scan(g, count, P + 1, &tmp, &tmp_bytes);
-        if (r != ADH_OK) return r;
-        size_t sb = sort_bytes;
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(sort_tmp, sb, key_in, key, val_in, val, (int)E, 0, 64, st));
+        ADH_TRY(sess::exclusive_sum(scan_tmp, count, count, P + 1, st));
+        ADH_TRY(sess::sort_pairs(sort_tmp, key_in, key, val_in, val, E, 64, st));
         HIP_TRY(hipMemcpyAsync(&kept, count + P, 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         return ADH_OK;

@@ -25,58 +25,41 @@
 //                    keys flagged (pandas refuses a duplicate index), a binary search per target.
 // adh_mbr_notnull_objects: the null mask of the pg column on the host (no kernel): None and str told apart by pointer.
 //
-// All global writes are plain vector stores or vector integer atomics.  Included by adh_api.hip after
-// adh_transfer_library.hip (shares its helpers and kernels, the error helpers and the handle).
+// All global writes are plain vector stores or vector integer atomics.  Included by adh_api.hip behind adh_session.h
+// (shares its error helpers, the handle and the session helpers); the block-bookkeeping kernels of namespace tl come
+// with the include below.
+#include "adh_transfer_library.hip"
 
 struct adh_mbr {
     adh_handle_t *h = nullptr;
     // the aggregate: [0] by elution group, [1] by hash - distinct keys ascending (order-preserving form), median,
     // original row of the first non-null pg (0xFFFFFFFF: none); the groups that passed.  Grow-only.
-    uint64_t *key[2] = {nullptr, nullptr};
-    double *med[2] = {nullptr, nullptr};
-    uint32_t *first[2] = {nullptr, nullptr};
-    size_t key_cap[2] = {0, 0}, med_cap[2] = {0, 0}, first_cap[2] = {0, 0};
+    sess::DevArray<uint64_t> key[2];
+    sess::DevArray<double> med[2];
+    sess::DevArray<uint32_t> first[2];
     int64_t n_seg[2] = {-1, -1};
-    uint64_t *groups = nullptr;
-    size_t groups_cap = 0;
+    sess::DevArray<uint64_t> groups;
     int64_t n_groups = -1;
     int rt_is_f64 = 0, hash_signed = 0, eg_is_u32 = 0;
     // the filter: kept library rows, their renumbered blocks, the source row of every kept dense row, the matrices
-    uint32_t *kept = nullptr, *src_row = nullptr;
-    int64_t *start = nullptr, *stop = nullptr;
-    size_t kept_cap = 0, src_cap = 0, start_cap = 0, stop_cap = 0;
-    float *mat[ADH_TL_MAX_MATRICES] = {nullptr, nullptr, nullptr, nullptr};
-    size_t mat_cap[ADH_TL_MAX_MATRICES] = {0, 0, 0, 0};
+    sess::DevArray<uint32_t> kept, src_row;
+    sess::DevArray<int64_t> start, stop;
+    sess::DevArray<float> mat[ADH_TL_MAX_MATRICES];
     int64_t n_kept = -1, n_rows = 0;
     int32_t C = 0, M = 0;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    sess::EventPair ev;
     double aggregate_ms = 0.0, filter_ms = 0.0, gather_ms = 0.0, assign_ms = 0.0;
     uint64_t h2d_bytes = 0, d2h_bytes = 0;
 };
 
 namespace mbr {
 
-using tl::kBlock;
-using tl::grid_for;
+using sess::grid_for;
+using sess::kBlock;
 
 constexpr uint64_t kSign = 0x8000000000000000ull;
 constexpr uint64_t kNanKey = 0xFFFFFFFFFFFFFFFFull;
 constexpr int kKeyU32 = 0, kKeyI64 = 1, kKeyU64 = 2;
-
-template <typename T>
-hipError_t grow(T *&p, size_t &cap, size_t n) {
-    n = std::max<size_t>(n, 4);
-    if (n <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    void *v = nullptr;
-    hipError_t e = hipMalloc(&v, n * sizeof(T));
-    if (e != hipSuccess) return e;
-    p = static_cast<T *>(v);
-    cap = n;
-    return hipSuccess;
-}
 
 __device__ __forceinline__ uint64_t load_key(const void *__restrict__ col, int32_t kind, int64_t i) {
     if (kind == kKeyU32) return (uint64_t)((const uint32_t *)col)[i] ^ kSign;  // (as the int64 of the same value)
@@ -235,21 +218,11 @@ __global__ void __launch_bounds__(kBlock) index_kernel(const uint64_t *__restric
     }
 }
 
-template <typename In, typename Flag, typename Out>
-int select_flagged(tl::Bufs &B, const In *in, const Flag *flag, Out *out, uint32_t *n_sel, int64_t n, hipStream_t st) {
-    size_t need = 0;
-    HIP_TRY(hipcub::DeviceSelect::Flagged(nullptr, need, in, flag, out, n_sel, (int)n, st));
-    unsigned char *tmp = nullptr;
-    HIP_TRY(B.alloc(&tmp, need));
-    HIP_TRY(hipcub::DeviceSelect::Flagged(tmp, need, in, flag, out, n_sel, (int)n, st));
-    return ADH_OK;
-}
-
 inline int key_kind(int32_t is_u32) { return is_u32 ? kKeyU32 : kKeyI64; }
 inline int hash_kind(int32_t is_signed) { return is_signed ? kKeyI64 : kKeyU64; }
 
 // one key of the aggregate: fills g->key / med / first [w]; w == 0 also the groups that passed
-int aggregate_key(adh_mbr *g, tl::Bufs &B, int w, const uint32_t *sel, int64_t K, const void *col, int32_t kind, const void *rt,
+int aggregate_key(adh_mbr *g, sess::DevBufs &B, int w, const uint32_t *sel, int64_t K, const void *col, int32_t kind, const void *rt,
                   int32_t rt_is_f64, const uint8_t *pg_notnull, const uint8_t *decoy, int32_t keep_decoys, const uint32_t *iota,
                   hipStream_t st) {
     uint64_t *key = nullptr, *rtk = nullptr, *k_in = nullptr, *k_s = nullptr, *rtk_s = nullptr;
@@ -271,46 +244,40 @@ int aggregate_key(adh_mbr *g, tl::Bufs &B, int w, const uint32_t *sel, int64_t K
     hipLaunchKernelGGL(keys_kernel, grid, block, 0, st, sel, K, col, kind, rt, rt_is_f64, key, rtk);
     HIP_TRY(hipGetLastError());
     // least significant key first: the RT, then the group key
-    TL_TRY(tl::sort_pairs(B, rtk, rtk_s, iota, p1, K, st));
+    ADH_TRY(sess::sort_pairs(B, rtk, rtk_s, iota, p1, K, 64, st));
     hipLaunchKernelGGL(tl::take_kernel, grid, block, 0, st, (const uint64_t *)key, (const uint32_t *)p1, K, k_in);
     HIP_TRY(hipGetLastError());
-    TL_TRY(tl::sort_pairs(B, k_in, k_s, p1, p2, K, st));
+    ADH_TRY(sess::sort_pairs(B, k_in, k_s, p1, p2, K, 64, st));
     hipLaunchKernelGGL(tl::take_kernel, grid, block, 0, st, (const uint64_t *)rtk, (const uint32_t *)p2, K, rtk_s);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(head_flag_kernel, grid, block, 0, st, (const uint64_t *)k_s, K, head);
     HIP_TRY(hipGetLastError());
-    {
-        size_t need = 0;
-        HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, need, head, seg, (int)K, st));
-        unsigned char *tmp = nullptr;
-        HIP_TRY(B.alloc(&tmp, need));
-        HIP_TRY(hipcub::DeviceScan::InclusiveSum(tmp, need, head, seg, (int)K, st));
-    }
-    TL_TRY(select_flagged(B, iota, head, seg_start, n_sel, K, st));
+    ADH_TRY(sess::inclusive_sum(B, head, seg, K, st));
+    ADH_TRY(sess::select_flagged(B, iota, (const uint32_t *)head, seg_start, n_sel, K, st));
     uint32_t S32 = 0;
     HIP_TRY(hipMemcpyAsync(&S32, n_sel, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     const int64_t S = S32;
     if (S < 1 || S > K) return fail(ADH_ERR_HIP, "adh_mbr_aggregate: inconsistent number of segments");
-    HIP_TRY(grow(g->key[w], g->key_cap[w], (size_t)S));
-    HIP_TRY(grow(g->med[w], g->med_cap[w], (size_t)S));
-    HIP_TRY(grow(g->first[w], g->first_cap[w], (size_t)S));
+    HIP_TRY(g->key[w].reserve((size_t)S));
+    HIP_TRY(g->med[w].reserve((size_t)S));
+    HIP_TRY(g->first[w].reserve((size_t)S));
     HIP_TRY(hipMemsetAsync(g->first[w], 0xFF, (size_t)S * 4, st));
     if (has_target) HIP_TRY(hipMemsetAsync(has_target, 0, (size_t)S, st));
     hipLaunchKernelGGL(segment_rows_kernel, grid, block, 0, st, (const uint32_t *)seg, (const uint32_t *)p2, sel, pg_notnull, decoy, K,
-                       g->first[w], has_target);
+                       g->first[w].p, has_target);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(median_kernel, dim3(grid_for(S)), block, 0, st, (const uint64_t *)k_s, (const uint64_t *)rtk_s,
-                       (const uint32_t *)seg_start, S, K, g->key[w], g->med[w]);
+                       (const uint32_t *)seg_start, S, K, g->key[w].p, g->med[w].p);
     HIP_TRY(hipGetLastError());
     g->n_seg[w] = S;
     if (w != 0) return ADH_OK;
-    HIP_TRY(grow(g->groups, g->groups_cap, (size_t)S));
+    HIP_TRY(g->groups.reserve((size_t)S));
     if (keep_decoys) {
         HIP_TRY(hipMemcpyAsync(g->groups, g->key[0], (size_t)S * 8, hipMemcpyDeviceToDevice, st));
         g->n_groups = S;
     } else {
-        TL_TRY(select_flagged(B, (const uint64_t *)g->key[0], (const uint8_t *)has_target, g->groups, n_sel, S, st));
+        ADH_TRY(sess::select_flagged(B, (const uint64_t *)g->key[0].p, (const uint8_t *)has_target, g->groups.p, n_sel, S, st));
         uint32_t G32 = 0;
         HIP_TRY(hipMemcpyAsync(&G32, n_sel, 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -336,12 +303,7 @@ int adh_mbr_destroy(adh_mbr_t *g) {
     if (!g) return ADH_OK;
     (void)hipSetDevice(g->h->device);
     (void)hipStreamSynchronize(g->h->stream);
-    for (int w = 0; w < 2; ++w) tl::drop(g->key[w]), tl::drop(g->med[w]), tl::drop(g->first[w]);
-    for (int m = 0; m < ADH_TL_MAX_MATRICES; ++m) tl::drop(g->mat[m]);
-    tl::drop(g->groups), tl::drop(g->kept), tl::drop(g->src_row), tl::drop(g->start), tl::drop(g->stop);
-    if (g->e0) (void)hipEventDestroy(g->e0);
-    if (g->e1) (void)hipEventDestroy(g->e1);
-    delete g;
+    delete g;  // (the members free their device memory and events)
     return ADH_OK;
 }
 
@@ -366,47 +328,41 @@ int adh_mbr_aggregate(adh_mbr_t *g, int64_t n, const double *qval, const uint8_t
     *n_passed = *n_by_group = *n_by_hash = *n_groups = 0;
     if (n == 0) return ADH_OK;
     const size_t gb = group_is_u32 ? 4 : 8, rb = rt_is_f64 ? 8 : 4;
-    tl::Bufs B;
+    sess::DevBufs B;
     double *d_q = nullptr;
     uint8_t *d_decoy = nullptr, *d_pg = nullptr, *flag = nullptr;
     unsigned char *d_eg = nullptr, *d_hash = nullptr, *d_rt = nullptr;
     uint32_t *iota = nullptr, *sel = nullptr, *n_sel = nullptr;
-    HIP_TRY(B.alloc(&d_q, (size_t)n));
-    HIP_TRY(B.alloc(&d_decoy, (size_t)n));
-    HIP_TRY(B.alloc(&d_pg, (size_t)n));
+    HIP_TRY(B.upload(&d_q, qval, (size_t)n, st));
+    HIP_TRY(B.upload(&d_decoy, decoy, (size_t)n, st));
+    HIP_TRY(B.upload(&d_pg, pg_notnull, (size_t)n, st));
     HIP_TRY(B.alloc(&flag, (size_t)n));
-    HIP_TRY(B.alloc(&d_eg, (size_t)n * gb));
-    HIP_TRY(B.alloc(&d_hash, (size_t)n * 8));
-    HIP_TRY(B.alloc(&d_rt, (size_t)n * rb));
+    HIP_TRY(B.upload(&d_eg, elution_group_idx, (size_t)n * gb, st));
+    HIP_TRY(B.upload(&d_hash, mod_seq_charge_hash, (size_t)n * 8, st));
+    HIP_TRY(B.upload(&d_rt, rt_observed, (size_t)n * rb, st));
     HIP_TRY(B.alloc(&iota, (size_t)n));
     HIP_TRY(B.alloc(&sel, (size_t)n));
     HIP_TRY(B.alloc(&n_sel, 4));
-    HIP_TRY(hipMemcpyAsync(d_q, qval, (size_t)n * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_decoy, decoy, (size_t)n, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_pg, pg_notnull, (size_t)n, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_eg, elution_group_idx, (size_t)n * gb, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_hash, mod_seq_charge_hash, (size_t)n * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_rt, rt_observed, (size_t)n * rb, hipMemcpyHostToDevice, st));
     g->h2d_bytes += (uint64_t)n * (8 + 1 + 1 + gb + 8 + rb);
-    tl::Timer t{g->e0, g->e1, st};
-    TL_TRY(t.begin());
-    hipLaunchKernelGGL(mbr::pass_kernel, dim3(tl::grid_for(n)), dim3(tl::kBlock), 0, st, (const double *)d_q, fdr, n, flag);
+    sess::EventPair &t = g->ev;
+    ADH_TRY(t.begin(st));
+    hipLaunchKernelGGL(mbr::pass_kernel, dim3(mbr::grid_for(n)), dim3(mbr::kBlock), 0, st, (const double *)d_q, fdr, n, flag);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(tl::iota_kernel, dim3(tl::grid_for(n)), dim3(tl::kBlock), 0, st, iota, n);
+    hipLaunchKernelGGL(sess::iota_kernel, dim3(mbr::grid_for(n)), dim3(mbr::kBlock), 0, st, iota, n);
     HIP_TRY(hipGetLastError());
-    TL_TRY(mbr::select_flagged(B, (const uint32_t *)iota, (const uint8_t *)flag, sel, n_sel, n, st));
+    ADH_TRY(sess::select_flagged(B, (const uint32_t *)iota, (const uint8_t *)flag, sel, n_sel, n, st));
     uint32_t K32 = 0;
     HIP_TRY(hipMemcpyAsync(&K32, n_sel, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     const int64_t K = K32;
     if (K > n) return fail(ADH_ERR_HIP, "adh_mbr_aggregate: inconsistent number of passing rows");
     if (K > 0) {
-        TL_TRY(mbr::aggregate_key(g, B, 0, sel, K, d_eg, mbr::key_kind(group_is_u32), d_rt, rt_is_f64, d_pg, d_decoy, keep_decoys,
+        ADH_TRY(mbr::aggregate_key(g, B, 0, sel, K, d_eg, mbr::key_kind(group_is_u32), d_rt, rt_is_f64, d_pg, d_decoy, keep_decoys,
                                   iota, st));
-        TL_TRY(mbr::aggregate_key(g, B, 1, sel, K, d_hash, mbr::hash_kind(hash_is_signed), d_rt, rt_is_f64, d_pg, d_decoy, 1, iota,
+        ADH_TRY(mbr::aggregate_key(g, B, 1, sel, K, d_hash, mbr::hash_kind(hash_is_signed), d_rt, rt_is_f64, d_pg, d_decoy, 1, iota,
                                   st));
     }
-    TL_TRY(t.end(g->aggregate_ms));
+    ADH_TRY(t.end(st, g->aggregate_ms));
     g->d2h_bytes += 16;
     *n_passed = K;
     *n_by_group = g->n_seg[0];
@@ -424,7 +380,7 @@ int adh_mbr_read_table(adh_mbr_t *g, int32_t which, void *keys, void *median, in
     const size_t S = (size_t)(which == 2 ? g->n_groups : g->n_seg[which]);
     if (S == 0) return ADH_OK;
     uint64_t *k = (uint64_t *)keys;
-    HIP_TRY(hipMemcpyAsync(k, which == 2 ? g->groups : g->key[which], S * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(k, which == 2 ? g->groups.p : g->key[which].p, S * 8, hipMemcpyDeviceToHost, st));
     std::vector<double> med;
     std::vector<uint32_t> first;
     if (which != 2) {
@@ -478,22 +434,19 @@ int adh_mbr_filter(adh_mbr_t *g, int64_t n_lib, const void *elution_group_idx, i
     }
     const int32_t C = n_columns;
     const size_t gb = group_is_u32 ? 4 : 8;
-    tl::Bufs B;
+    sess::DevBufs B;
     unsigned char *d_eg = nullptr;
     int64_t *start = nullptr, *stop = nullptr;
     uint8_t *flag = nullptr;
     uint32_t *iota = nullptr, *n_sel = nullptr;
     const float *src[ADH_TL_MAX_MATRICES] = {nullptr, nullptr, nullptr, nullptr};
-    HIP_TRY(B.alloc(&d_eg, (size_t)n_lib * gb));
-    HIP_TRY(B.alloc(&start, (size_t)n_lib));
-    HIP_TRY(B.alloc(&stop, (size_t)n_lib));
+    HIP_TRY(B.upload(&d_eg, elution_group_idx, (size_t)n_lib * gb, st));
+    HIP_TRY(B.upload(&start, frag_start, (size_t)n_lib, st));
+    HIP_TRY(B.upload(&stop, frag_stop, (size_t)n_lib, st));
     HIP_TRY(B.alloc(&flag, (size_t)n_lib));
     HIP_TRY(B.alloc(&iota, (size_t)n_lib));
     HIP_TRY(B.alloc(&n_sel, 4));
-    HIP_TRY(mbr::grow(g->kept, g->kept_cap, (size_t)n_lib));
-    HIP_TRY(hipMemcpyAsync(d_eg, elution_group_idx, (size_t)n_lib * gb, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(start, frag_start, (size_t)n_lib * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(stop, frag_stop, (size_t)n_lib * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(g->kept.reserve((size_t)n_lib));
     g->h2d_bytes += (uint64_t)n_lib * (gb + 16);
     {
         // the matrices are the bytes of this step: from the caller's pageable arrays through the handle's page-locked lanes
@@ -505,19 +458,19 @@ int adh_mbr_filter(adh_mbr_t *g, int64_t n_lib, const void *elution_group_idx, i
             g->h2d_bytes += (uint64_t)n_rows * C * 4;
             src[m] = d;
         }
-        if (M > 0 && n_rows > 0) TL_TRY(upload_staged(g->h, jobs));
+        if (M > 0 && n_rows > 0) ADH_TRY(upload_staged(g->h, jobs));
     }
-    tl::Timer t{g->e0, g->e1, st};
-    TL_TRY(t.begin());
-    hipLaunchKernelGGL(mbr::member_kernel, dim3(tl::grid_for(n_lib)), dim3(tl::kBlock), 0, st, (const void *)d_eg,
-                       mbr::key_kind(group_is_u32), n_lib, (const uint64_t *)g->groups, g->n_groups, flag);
+    sess::EventPair &t = g->ev;
+    ADH_TRY(t.begin(st));
+    hipLaunchKernelGGL(mbr::member_kernel, dim3(mbr::grid_for(n_lib)), dim3(mbr::kBlock), 0, st, (const void *)d_eg,
+                       mbr::key_kind(group_is_u32), n_lib, (const uint64_t *)g->groups.p, g->n_groups, flag);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(tl::iota_kernel, dim3(tl::grid_for(n_lib)), dim3(tl::kBlock), 0, st, iota, n_lib);
+    hipLaunchKernelGGL(sess::iota_kernel, dim3(mbr::grid_for(n_lib)), dim3(mbr::kBlock), 0, st, iota, n_lib);
     HIP_TRY(hipGetLastError());
-    TL_TRY(mbr::select_flagged(B, (const uint32_t *)iota, (const uint8_t *)flag, g->kept, n_sel, n_lib, st));
+    ADH_TRY(sess::select_flagged(B, (const uint32_t *)iota, (const uint8_t *)flag, g->kept.p, n_sel, n_lib, st));
     uint32_t K32 = 0;
     HIP_TRY(hipMemcpyAsync(&K32, n_sel, 4, hipMemcpyDeviceToHost, st));
-    TL_TRY(t.end(g->filter_ms));
+    ADH_TRY(t.end(st, g->filter_ms));
     const int64_t K = K32;
     if (K > n_lib) return fail(ADH_ERR_HIP, "adh_mbr_filter: inconsistent number of kept precursors");
     if (K == 0) {
@@ -534,56 +487,50 @@ int adh_mbr_filter(adh_mbr_t *g, int64_t n_lib, const void *elution_group_idx, i
     HIP_TRY(B.alloc(&ord, (size_t)K));
     HIP_TRY(B.alloc(&len, (size_t)K));
     HIP_TRY(B.alloc(&new_start, (size_t)K));
-    HIP_TRY(mbr::grow(g->start, g->start_cap, (size_t)K));
-    HIP_TRY(mbr::grow(g->stop, g->stop_cap, (size_t)K));
-    TL_TRY(t.begin());
-    hipLaunchKernelGGL(tl::kept_start_kernel, dim3(tl::grid_for(K)), dim3(tl::kBlock), 0, st, (const uint32_t *)g->kept,
+    HIP_TRY(g->start.reserve((size_t)K));
+    HIP_TRY(g->stop.reserve((size_t)K));
+    ADH_TRY(t.begin(st));
+    hipLaunchKernelGGL(tl::kept_start_kernel, dim3(mbr::grid_for(K)), dim3(mbr::kBlock), 0, st, (const uint32_t *)g->kept.p,
                        (const int64_t *)start, K, ks_in, pos_in);
     HIP_TRY(hipGetLastError());
-    TL_TRY(tl::sort_pairs(B, ks_in, ks, pos_in, ord, K, st));
-    hipLaunchKernelGGL(tl::block_len_kernel, dim3(tl::grid_for(K)), dim3(tl::kBlock), 0, st, (const uint32_t *)g->kept,
+    ADH_TRY(sess::sort_pairs(B, ks_in, ks, pos_in, ord, K, 32, st));
+    hipLaunchKernelGGL(tl::block_len_kernel, dim3(mbr::grid_for(K)), dim3(mbr::kBlock), 0, st, (const uint32_t *)g->kept.p,
                        (const uint32_t *)ord, (const int64_t *)start, (const int64_t *)stop, K, len);
     HIP_TRY(hipGetLastError());
-    {
-        size_t need = 0;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, len, new_start, (int)K, st));
-        unsigned char *tmp = nullptr;
-        HIP_TRY(B.alloc(&tmp, need));
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, need, len, new_start, (int)K, st));
-    }
+    ADH_TRY(sess::exclusive_sum(B, len, new_start, K, st));
     int64_t last[2] = {0, 0};
     HIP_TRY(hipMemcpyAsync(&last[0], new_start + (K - 1), 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(&last[1], len + (K - 1), 8, hipMemcpyDeviceToHost, st));
-    hipLaunchKernelGGL(mbr::renumber_kernel, dim3(tl::grid_for(K)), dim3(tl::kBlock), 0, st, (const uint32_t *)ord,
-                       (const int64_t *)new_start, (const int64_t *)len, K, g->start, g->stop);
+    hipLaunchKernelGGL(mbr::renumber_kernel, dim3(mbr::grid_for(K)), dim3(mbr::kBlock), 0, st, (const uint32_t *)ord,
+                       (const int64_t *)new_start, (const int64_t *)len, K, g->start.p, g->stop.p);
     HIP_TRY(hipGetLastError());
-    TL_TRY(t.end(g->filter_ms));
+    ADH_TRY(t.end(st, g->filter_ms));
     g->d2h_bytes += 20;
     const int64_t Rn = last[0] + last[1];
     if (Rn < 0 || Rn >= (int64_t)0x7FFFFFF0ll)
         return fail(ADH_ERR_UNSUPPORTED, "adh_mbr_filter: the kept fragment rows number 2^31 or more");
-    HIP_TRY(mbr::grow(g->src_row, g->src_cap, (size_t)Rn));
-    for (int m = 0; m < M; ++m) HIP_TRY(mbr::grow(g->mat[m], g->mat_cap[m], (size_t)Rn * C));
+    HIP_TRY(g->src_row.reserve((size_t)Rn));
+    for (int m = 0; m < M; ++m) HIP_TRY(g->mat[m].reserve((size_t)Rn * C));
     if (Rn > 0) {
-        TL_TRY(t.begin());
-        hipLaunchKernelGGL(tl::row_map_kernel, dim3(tl::grid_for(Rn)), dim3(tl::kBlock), 0, st, (const int64_t *)new_start,
-                           (const uint32_t *)ks, K, Rn, g->src_row);
+        ADH_TRY(t.begin(st));
+        hipLaunchKernelGGL(tl::row_map_kernel, dim3(mbr::grid_for(Rn)), dim3(mbr::kBlock), 0, st, (const int64_t *)new_start,
+                           (const uint32_t *)ks, K, Rn, g->src_row.p);
         HIP_TRY(hipGetLastError());
         for (int m = 0; m < M; ++m) {
             if (C % 4 == 0) {
                 const int32_t Q = C / 4;
                 int32_t shift = 0;
                 while ((1 << shift) < Q && shift < 6) ++shift;
-                hipLaunchKernelGGL(mbr::row_gather4_kernel, dim3(tl::grid_for(Rn << shift)), dim3(tl::kBlock), 0, st,
-                                   (const float4 *)src[m], (const uint32_t *)g->src_row, Rn, Q, shift, (float4 *)g->mat[m]);
+                hipLaunchKernelGGL(mbr::row_gather4_kernel, dim3(mbr::grid_for(Rn << shift)), dim3(mbr::kBlock), 0, st,
+                                   (const float4 *)src[m], (const uint32_t *)g->src_row.p, Rn, Q, shift, (float4 *)g->mat[m].p);
             } else {  // rows that are no multiple of 16 bytes: adh_tl_update's gather, all rows from one source
-                hipLaunchKernelGGL(tl::row_gather_kernel, dim3(tl::grid_for(Rn * C)), dim3(tl::kBlock), 0, st, src[m],
-                                   (const float *)nullptr, (const uint32_t *)g->src_row, (int64_t)0x7FFFFFFFFFFFFFFFll, Rn * C, C,
-                                   g->mat[m]);
+                hipLaunchKernelGGL(tl::row_gather_kernel, dim3(mbr::grid_for(Rn * C)), dim3(mbr::kBlock), 0, st, src[m],
+                                   (const float *)nullptr, (const uint32_t *)g->src_row.p, (int64_t)0x7FFFFFFFFFFFFFFFll, Rn * C, C,
+                                   g->mat[m].p);
             }
             HIP_TRY(hipGetLastError());
         }
-        TL_TRY(t.end(g->gather_ms));
+        ADH_TRY(t.end(st, g->gather_ms));
     }
     HIP_TRY(hipStreamSynchronize(st));
     g->n_kept = K, g->n_rows = Rn;
@@ -639,28 +586,26 @@ int adh_mbr_assign(adh_mbr_t *g, int64_t n, const void *elution_group_idx, int32
     hipStream_t st = g->h->stream;
     HIP_TRY(hipStreamSynchronize(st));
     const size_t gb = group_is_u32 ? 4 : 8, rb = g->rt_is_f64 ? 8 : 4;
-    tl::Bufs B;
+    sess::DevBufs B;
     unsigned char *d_eg = nullptr, *d_hash = nullptr, *d_rt = nullptr;
     int64_t *d_row = nullptr;
     uint32_t *d_missing = nullptr;
-    HIP_TRY(B.alloc(&d_eg, (size_t)n * gb));
-    HIP_TRY(B.alloc(&d_hash, (size_t)n * 8));
+    HIP_TRY(B.upload(&d_eg, elution_group_idx, (size_t)n * gb, st));
+    HIP_TRY(B.upload(&d_hash, mod_seq_charge_hash, (size_t)n * 8, st));
     HIP_TRY(B.alloc(&d_rt, (size_t)n * rb));
     HIP_TRY(B.alloc(&d_row, (size_t)n));
     HIP_TRY(B.alloc(&d_missing, 4));
-    HIP_TRY(hipMemcpyAsync(d_eg, elution_group_idx, (size_t)n * gb, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_hash, mod_seq_charge_hash, (size_t)n * 8, hipMemcpyHostToDevice, st));
     g->h2d_bytes += (uint64_t)n * (gb + 8);
-    tl::Timer t{g->e0, g->e1, st};
-    TL_TRY(t.begin());
+    sess::EventPair &t = g->ev;
+    ADH_TRY(t.begin(st));
     HIP_TRY(hipMemsetAsync(d_missing, 0, 4, st));
-    hipLaunchKernelGGL(mbr::assign_kernel, dim3(tl::grid_for(n)), dim3(tl::kBlock), 0, st, (const void *)d_eg,
+    hipLaunchKernelGGL(mbr::assign_kernel, dim3(mbr::grid_for(n)), dim3(mbr::kBlock), 0, st, (const void *)d_eg,
                        mbr::key_kind(group_is_u32), (const void *)d_hash, mbr::hash_kind(hash_is_signed), n,
-                       (const uint64_t *)g->key[0], (const double *)g->med[0], (const uint32_t *)g->first[0], g->n_seg[0],
-                       (const uint64_t *)g->key[1], (const double *)g->med[1], (const uint32_t *)g->first[1], g->n_seg[1],
+                       (const uint64_t *)g->key[0].p, (const double *)g->med[0].p, (const uint32_t *)g->first[0].p, g->n_seg[0],
+                       (const uint64_t *)g->key[1].p, (const double *)g->med[1].p, (const uint32_t *)g->first[1].p, g->n_seg[1],
                        g->rt_is_f64, (void *)d_rt, d_row, d_missing);
     HIP_TRY(hipGetLastError());
-    TL_TRY(t.end(g->assign_ms));
+    ADH_TRY(t.end(st, g->assign_ms));
     uint32_t missing = 0;
     HIP_TRY(hipMemcpyAsync(rt, d_rt, (size_t)n * rb, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(pg_row, d_row, (size_t)n * 8, hipMemcpyDeviceToHost, st));
@@ -686,30 +631,28 @@ int adh_mbr_index(adh_mbr_t *g, int64_t n_targets, const uint64_t *target_keys, 
     HIP_TRY(hipSetDevice(g->h->device));
     hipStream_t st = g->h->stream;
     HIP_TRY(hipStreamSynchronize(st));
-    tl::Bufs B;
+    sess::DevBufs B;
     uint64_t *d_t = nullptr, *d_l = nullptr, *sorted = nullptr;
     uint32_t *iota = nullptr, *pos = nullptr;
     int64_t *d_out = nullptr;
     int32_t *d_dup = nullptr;
-    HIP_TRY(B.alloc(&d_t, (size_t)n_targets));
-    HIP_TRY(B.alloc(&d_l, (size_t)n_lookup));
+    HIP_TRY(B.upload(&d_t, target_keys, (size_t)n_targets, st));
+    HIP_TRY(B.upload(&d_l, lookup_keys, (size_t)n_lookup, st));
     HIP_TRY(B.alloc(&sorted, (size_t)n_lookup));
     HIP_TRY(B.alloc(&iota, (size_t)n_lookup));
     HIP_TRY(B.alloc(&pos, (size_t)n_lookup));
     HIP_TRY(B.alloc(&d_out, (size_t)n_targets));
     HIP_TRY(B.alloc(&d_dup, 4));
-    if (n_targets > 0) HIP_TRY(hipMemcpyAsync(d_t, target_keys, (size_t)n_targets * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_l, lookup_keys, (size_t)n_lookup * 8, hipMemcpyHostToDevice, st));
     g->h2d_bytes += (uint64_t)(n_targets + n_lookup) * 8;
     HIP_TRY(hipMemsetAsync(d_dup, 0, 4, st));
-    hipLaunchKernelGGL(tl::iota_kernel, dim3(tl::grid_for(n_lookup)), dim3(tl::kBlock), 0, st, iota, n_lookup);
+    hipLaunchKernelGGL(sess::iota_kernel, dim3(mbr::grid_for(n_lookup)), dim3(mbr::kBlock), 0, st, iota, n_lookup);
     HIP_TRY(hipGetLastError());
-    TL_TRY(tl::sort_pairs(B, (const uint64_t *)d_l, sorted, (const uint32_t *)iota, pos, n_lookup, st));
-    hipLaunchKernelGGL(mbr::adjacent_equal_kernel, dim3(tl::grid_for(n_lookup)), dim3(tl::kBlock), 0, st, (const uint64_t *)sorted,
+    ADH_TRY(sess::sort_pairs(B, (const uint64_t *)d_l, sorted, (const uint32_t *)iota, pos, n_lookup, 64, st));
+    hipLaunchKernelGGL(mbr::adjacent_equal_kernel, dim3(mbr::grid_for(n_lookup)), dim3(mbr::kBlock), 0, st, (const uint64_t *)sorted,
                        n_lookup, d_dup);
     HIP_TRY(hipGetLastError());
     if (n_targets > 0) {
-        hipLaunchKernelGGL(mbr::index_kernel, dim3(tl::grid_for(n_targets)), dim3(tl::kBlock), 0, st, (const uint64_t *)d_t, n_targets,
+        hipLaunchKernelGGL(mbr::index_kernel, dim3(mbr::grid_for(n_targets)), dim3(mbr::kBlock), 0, st, (const uint64_t *)d_t, n_targets,
                            (const uint64_t *)sorted, (const uint32_t *)pos, n_lookup, d_out);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(index, d_out, (size_t)n_targets * 8, hipMemcpyDeviceToHost, st));

@@ -24,23 +24,23 @@
 // adh_pfdr_predict:  a thread per row, the same forward expression: equal rows give equal bits.
 // adh_pfdr_gather:   row -> its group's value, NaN for a row of no group.
 //
-// Included by adh_api.hip (shares its error helpers and the handle).
+// Included by adh_api.hip behind adh_session.h (shares its error helpers, the handle and the session helpers).
 
 struct adh_pfdr {
     adh_handle_t *h = nullptr;
-    std::vector<void *> bufs;  // the device buffers of the last adh_pfdr_features
+    sess::DevBufs bufs;  // the device buffers of the last adh_pfdr_features
     int64_t n_rows = 0, n_groups = -1;
     int32_t *row_group = nullptr, *group_pg = nullptr;
     uint8_t *group_decoy = nullptr;
     double *feat = nullptr;
     // the classifier
-    std::vector<void *> fit_bufs;
+    sess::DevBufs fit_bufs;
     int64_t n_train = 0;
     double *x = nullptr, *y = nullptr, *params = nullptr, *m = nullptr, *v = nullptr, *lr = nullptr, *loss = nullptr;
     int32_t *order = nullptr;
     int32_t max_steps = 0;
     bool fitted = false;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    sess::EventPair ev;
     double features_ms = 0.0, epochs_ms = 0.0, predict_ms = 0.0, gather_ms = 0.0;
 };
 
@@ -59,41 +59,7 @@ constexpr uint32_t kLeaf = 128;      // NumPy's PW_BLOCKSIZE
 constexpr uint32_t kSeqRows = 1024;  // groups up to this many rows are summed by one thread
 constexpr uint32_t kChunk = 8192;    // NumPy's buffer size: a longer vector is summed chunk after chunk
 
-inline unsigned grid_for(int64_t n) {
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + kBlock - 1) / kBlock, 16384));
-}
-
-void release(std::vector<void *> &bufs) {
-    for (void *p : bufs)
-        if (p) (void)hipFree(p);
-    bufs.clear();
-}
-
-template <typename T>
-hipError_t alloc(std::vector<void *> &bufs, T **p, size_t n) {
-    void *v = nullptr;
-    hipError_t e = hipMalloc(&v, std::max<size_t>(n, 4) * sizeof(T));
-    if (e != hipSuccess) return e;
-    bufs.push_back(v);
-    *p = static_cast<T *>(v);
-    return hipSuccess;
-}
-
-template <typename F>
-int timed(adh_pfdr *g, double &ms, bool accumulate, F &&body) {
-    hipStream_t st = g->h->stream;
-    if (!g->e0) HIP_TRY(hipEventCreate(&g->e0));
-    if (!g->e1) HIP_TRY(hipEventCreate(&g->e1));
-    HIP_TRY(hipEventRecord(g->e0, st));
-    const int rc = body();
-    if (rc != ADH_OK) return rc;
-    HIP_TRY(hipEventRecord(g->e1, st));
-    HIP_TRY(hipEventSynchronize(g->e1));
-    float f = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&f, g->e0, g->e1));
-    ms = accumulate ? ms + f : f;
-    return ADH_OK;
-}
+using sess::grid_for;
 
 // ---- group features ---------------------------------------------------------------------------------------------
 
@@ -328,33 +294,12 @@ __global__ void __launch_bounds__(kBlock) gather_kernel(const int32_t *__restric
     }
 }
 
-template <typename K, typename V>
-int sort_pairs(std::vector<void *> &bufs, const K *k_in, K *k_out, const V *v_in, V *v_out, int64_t n, int end_bit,
-               hipStream_t st) {
-    size_t need = 0;
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, need, k_in, k_out, v_in, v_out, (int)n, 0, end_bit, st));
-    unsigned char *tmp = nullptr;
-    HIP_TRY(alloc(bufs, &tmp, need));
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, need, k_in, k_out, v_in, v_out, (int)n, 0, end_bit, st));
-    return ADH_OK;
-}
-
-int sort_keys(std::vector<void *> &bufs, const uint64_t *in, uint64_t *out, int64_t n, hipStream_t st) {
-    size_t need = 0;
-    HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, need, in, out, (int)n, 0, 64, st));
-    unsigned char *tmp = nullptr;
-    HIP_TRY(alloc(bufs, &tmp, need));
-    HIP_TRY(hipcub::DeviceRadixSort::SortKeys(tmp, need, in, out, (int)n, 0, 64, st));
-    return ADH_OK;
-}
-
 template <typename T>
 int score_stats(adh_pfdr *g, const void *proba, const uint32_t *srow, int64_t n, int64_t nv, int64_t G,
                 const uint32_t *seg_start, uint32_t *list, uint32_t *n_large, hipStream_t st) {
     T *d_p = nullptr, *d_s = nullptr;
-    HIP_TRY(alloc(g->bufs, &d_p, (size_t)n));
-    HIP_TRY(alloc(g->bufs, &d_s, (size_t)nv));
-    HIP_TRY(hipMemcpyAsync(d_p, proba, (size_t)n * sizeof(T), hipMemcpyHostToDevice, st));
+    HIP_TRY(g->bufs.upload(&d_p, (const T *)proba, (size_t)n, st));
+    HIP_TRY(g->bufs.alloc(&d_s, (size_t)nv));
     hipLaunchKernelGGL((score_gather_kernel<T>), dim3(grid_for(nv)), dim3(kBlock), 0, st, d_p, srow, nv, d_s);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemsetAsync(n_large, 0, 4, st));
@@ -529,11 +474,7 @@ int adh_pfdr_destroy(adh_pfdr_t *g) {
     if (!g) return ADH_OK;
     (void)hipSetDevice(g->h->device);
     (void)hipStreamSynchronize(g->h->stream);
-    pfdr::release(g->bufs);
-    pfdr::release(g->fit_bufs);
-    if (g->e0) (void)hipEventDestroy(g->e0);
-    if (g->e1) (void)hipEventDestroy(g->e1);
-    delete g;
+    delete g;  // (the members free their device memory and events)
     return ADH_OK;
 }
 
@@ -560,7 +501,7 @@ int adh_pfdr_features(adh_pfdr_t *g, int64_t n_rows, const int32_t *pg, const ui
     HIP_TRY(hipSetDevice(g->h->device));
     hipStream_t st = g->h->stream;
     HIP_TRY(hipStreamSynchronize(st));
-    pfdr::release(g->bufs);
+    g->bufs.release();
     g->n_rows = n, g->n_groups = -1;
     g->features_ms = 0.0;
     auto &B = g->bufs;
@@ -572,38 +513,28 @@ int adh_pfdr_features(adh_pfdr_t *g, int64_t n_rows, const int32_t *pg, const ui
              *pos_in = nullptr, *pos = nullptr, *sk_in = nullptr, *sk = nullptr, *counts = nullptr, *list = nullptr,
              *n_large = nullptr;
     uint64_t *akey_in = nullptr, *akey = nullptr;
-    HIP_TRY(pfdr::alloc(B, &d_pg, (size_t)n));
-    HIP_TRY(pfdr::alloc(B, &d_seq, (size_t)n));
-    HIP_TRY(pfdr::alloc(B, &d_run, (size_t)n));
-    HIP_TRY(pfdr::alloc(B, &d_decoy, (size_t)n));
-    HIP_TRY(pfdr::alloc(B, &d_prec, (size_t)n));
-    HIP_TRY(pfdr::alloc(B, &key_in, (size_t)n));
-    HIP_TRY(pfdr::alloc(B, &key, (size_t)n));
-    HIP_TRY(pfdr::alloc(B, &row_in, (size_t)n));
-    HIP_TRY(pfdr::alloc(B, &srow, (size_t)n));
-    HIP_TRY(pfdr::alloc(B, &seg, (size_t)nv));
-    HIP_TRY(pfdr::alloc(B, &g->row_group, (size_t)n));
-    HIP_TRY(pfdr::alloc(B, &n_large, 4));
-    HIP_TRY(hipMemcpyAsync(d_pg, pg, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_seq, sequence, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_run, run, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_decoy, decoy, (size_t)n, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_prec, precursor_idx, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(B.upload(&d_pg, pg, (size_t)n, st));
+    HIP_TRY(B.upload(&d_seq, sequence, (size_t)n, st));
+    HIP_TRY(B.upload(&d_run, run, (size_t)n, st));
+    HIP_TRY(B.upload(&d_decoy, decoy, (size_t)n, st));
+    HIP_TRY(B.upload(&d_prec, precursor_idx, (size_t)n, st));
+    HIP_TRY(B.alloc(&key_in, (size_t)n));
+    HIP_TRY(B.alloc(&key, (size_t)n));
+    HIP_TRY(B.alloc(&row_in, (size_t)n));
+    HIP_TRY(B.alloc(&srow, (size_t)n));
+    HIP_TRY(B.alloc(&seg, (size_t)nv));
+    HIP_TRY(B.alloc(&g->row_group, (size_t)n));
+    HIP_TRY(B.alloc(&n_large, 4));
 
     uint32_t G32 = 0;
-    int rc = pfdr::timed(g, g->features_ms, false, [&]() -> int {
+    int rc = sess::timed(g->ev, st, g->features_ms, [&]() -> int {
         hipLaunchKernelGGL(pfdr::row_key_kernel, dim3(pfdr::grid_for(n)), dim3(pfdr::kBlock), 0, st, d_pg, d_decoy, n, key_in,
                            row_in);
         HIP_TRY(hipGetLastError());
-        int r = pfdr::sort_pairs(B, key_in, key, row_in, srow, n, 32, st);
-        if (r != ADH_OK) return r;
+        ADH_TRY(sess::sort_pairs(B, key_in, key, row_in, srow, n, 32, st));
         hipLaunchKernelGGL(pfdr::head_kernel, dim3(pfdr::grid_for(nv)), dim3(pfdr::kBlock), 0, st, key, nv, seg);
         HIP_TRY(hipGetLastError());
-        size_t need = 0;
-        HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, need, seg, seg, (int)nv, st));
-        unsigned char *tmp = nullptr;
-        HIP_TRY(pfdr::alloc(B, &tmp, need));
-        HIP_TRY(hipcub::DeviceScan::InclusiveSum(tmp, need, seg, seg, (int)nv, st));
+        ADH_TRY(sess::inclusive_sum(B, seg, seg, nv, st));
         HIP_TRY(hipMemcpyAsync(&G32, seg + (nv - 1), 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         return ADH_OK;
@@ -612,23 +543,22 @@ int adh_pfdr_features(adh_pfdr_t *g, int64_t n_rows, const int32_t *pg, const ui
     const int64_t G = G32;
     if (G < 1 || G > nv) return fail(ADH_ERR_HIP, "adh_pfdr_features: inconsistent group count");
 
-    HIP_TRY(pfdr::alloc(B, &seg_start, (size_t)G + 1));
-    HIP_TRY(pfdr::alloc(B, &g->group_pg, (size_t)G));
-    HIP_TRY(pfdr::alloc(B, &g->group_decoy, (size_t)G));
-    HIP_TRY(pfdr::alloc(B, &g->feat, (size_t)G * pfdr::kIn));
-    HIP_TRY(pfdr::alloc(B, &counts, (size_t)G * 3));
-    HIP_TRY(pfdr::alloc(B, &list, (size_t)G));
-    HIP_TRY(pfdr::alloc(B, &akey_in, (size_t)nv));
-    HIP_TRY(pfdr::alloc(B, &akey, (size_t)nv));
-    HIP_TRY(pfdr::alloc(B, &wide_in, (size_t)nv));
-    HIP_TRY(pfdr::alloc(B, &wide, (size_t)nv));
-    HIP_TRY(pfdr::alloc(B, &wide2, (size_t)nv));
-    HIP_TRY(pfdr::alloc(B, &pos_in, (size_t)nv));
-    HIP_TRY(pfdr::alloc(B, &pos, (size_t)nv));
-    HIP_TRY(pfdr::alloc(B, &sk_in, (size_t)nv));
-    HIP_TRY(pfdr::alloc(B, &sk, (size_t)nv));
-    double rest_ms = 0.0;
-    rc = pfdr::timed(g, rest_ms, false, [&]() -> int {
+    HIP_TRY(B.alloc(&seg_start, (size_t)G + 1));
+    HIP_TRY(B.alloc(&g->group_pg, (size_t)G));
+    HIP_TRY(B.alloc(&g->group_decoy, (size_t)G));
+    HIP_TRY(B.alloc(&g->feat, (size_t)G * pfdr::kIn));
+    HIP_TRY(B.alloc(&counts, (size_t)G * 3));
+    HIP_TRY(B.alloc(&list, (size_t)G));
+    HIP_TRY(B.alloc(&akey_in, (size_t)nv));
+    HIP_TRY(B.alloc(&akey, (size_t)nv));
+    HIP_TRY(B.alloc(&wide_in, (size_t)nv));
+    HIP_TRY(B.alloc(&wide, (size_t)nv));
+    HIP_TRY(B.alloc(&wide2, (size_t)nv));
+    HIP_TRY(B.alloc(&pos_in, (size_t)nv));
+    HIP_TRY(B.alloc(&pos, (size_t)nv));
+    HIP_TRY(B.alloc(&sk_in, (size_t)nv));
+    HIP_TRY(B.alloc(&sk, (size_t)nv));
+    rc = sess::timed(g->ev, st, g->features_ms, [&]() -> int {
         HIP_TRY(hipMemsetAsync(g->row_group, 0xFF, (size_t)n * 4, st));
         HIP_TRY(hipMemsetAsync(counts, 0, (size_t)G * 3 * 4, st));
         hipLaunchKernelGGL(pfdr::seg_fill_kernel, dim3(pfdr::grid_for(nv)), dim3(pfdr::kBlock), 0, st, key, seg, srow, nv,
@@ -640,20 +570,17 @@ int adh_pfdr_features(adh_pfdr_t *g, int64_t n_rows, const int32_t *pg, const ui
             hipLaunchKernelGGL(pfdr::attr_key_kernel, dim3(pfdr::grid_for(nv)), dim3(pfdr::kBlock), 0, st, seg, srow, attr[a], nv,
                                akey_in);
             HIP_TRY(hipGetLastError());
-            const int r = pfdr::sort_keys(B, akey_in, akey, nv, st);
-            if (r != ADH_OK) return r;
+            ADH_TRY(sess::sort_keys(B, akey_in, akey, nv, 64, st));
             hipLaunchKernelGGL(pfdr::distinct_kernel, dim3(pfdr::grid_for(nv)), dim3(pfdr::kBlock), 0, st, akey, nv, count[a]);
             HIP_TRY(hipGetLastError());
         }
         hipLaunchKernelGGL(pfdr::wide_gather_kernel, dim3(pfdr::grid_for(nv)), dim3(pfdr::kBlock), 0, st, d_prec, srow, nv,
                            wide_in, pos_in);
         HIP_TRY(hipGetLastError());
-        int r = pfdr::sort_pairs(B, wide_in, wide, pos_in, pos, nv, 64, st);
-        if (r != ADH_OK) return r;
+        ADH_TRY(sess::sort_pairs(B, wide_in, wide, pos_in, pos, nv, 64, st));
         hipLaunchKernelGGL(pfdr::take_seg_kernel, dim3(pfdr::grid_for(nv)), dim3(pfdr::kBlock), 0, st, seg, pos, nv, sk_in);
         HIP_TRY(hipGetLastError());
-        r = pfdr::sort_pairs(B, sk_in, sk, wide, wide2, nv, 32, st);
-        if (r != ADH_OK) return r;
+        ADH_TRY(sess::sort_pairs(B, sk_in, sk, wide, wide2, nv, 32, st));
         hipLaunchKernelGGL(pfdr::wide_distinct_kernel, dim3(pfdr::grid_for(nv)), dim3(pfdr::kBlock), 0, st, sk, wide2, nv,
                            counts + G);
         HIP_TRY(hipGetLastError());
@@ -664,7 +591,6 @@ int adh_pfdr_features(adh_pfdr_t *g, int64_t n_rows, const int32_t *pg, const ui
                             : pfdr::score_stats<float>(g, proba, srow, n, nv, G, seg_start, list, n_large, st);
     });
     if (rc != ADH_OK) return rc;
-    g->features_ms += rest_ms;
     g->n_groups = G;
     *n_groups = G;
     return ADH_OK;
@@ -697,23 +623,20 @@ int adh_pfdr_fit_begin(adh_pfdr_t *g, int64_t n_train, const double *x, const ui
     HIP_TRY(hipSetDevice(g->h->device));
     hipStream_t st = g->h->stream;
     HIP_TRY(hipStreamSynchronize(st));
-    pfdr::release(g->fit_bufs);
+    g->fit_bufs.release();
     g->fitted = false;
     g->epochs_ms = g->predict_ms = 0.0;
     auto &B = g->fit_bufs;
     const int64_t batch = std::min<int64_t>(n_train, pfdr::kBatch);
     g->max_steps = (int32_t)((n_train + batch - 1) / batch);
-    HIP_TRY(pfdr::alloc(B, &g->x, (size_t)n_train * pfdr::kIn));
-    HIP_TRY(pfdr::alloc(B, &g->y, (size_t)n_train));
-    HIP_TRY(pfdr::alloc(B, &g->order, (size_t)n_train));
-    HIP_TRY(pfdr::alloc(B, &g->lr, (size_t)g->max_steps));
-    HIP_TRY(pfdr::alloc(B, &g->params, (size_t)pfdr::kParams));
-    HIP_TRY(pfdr::alloc(B, &g->m, (size_t)pfdr::kParams));
-    HIP_TRY(pfdr::alloc(B, &g->v, (size_t)pfdr::kParams));
-    HIP_TRY(pfdr::alloc(B, &g->loss, 4));
-    HIP_TRY(hipMemcpyAsync(g->x, x, (size_t)n_train * pfdr::kIn * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(g->y, yd.data(), (size_t)n_train * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(g->params, params, (size_t)pfdr::kParams * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(B.upload(&g->x, x, (size_t)n_train * pfdr::kIn, st));
+    HIP_TRY(B.upload(&g->y, (const double *)yd.data(), (size_t)n_train, st));
+    HIP_TRY(B.alloc(&g->order, (size_t)n_train));
+    HIP_TRY(B.alloc(&g->lr, (size_t)g->max_steps));
+    HIP_TRY(B.upload(&g->params, params, (size_t)pfdr::kParams, st));
+    HIP_TRY(B.alloc(&g->m, (size_t)pfdr::kParams));
+    HIP_TRY(B.alloc(&g->v, (size_t)pfdr::kParams));
+    HIP_TRY(B.alloc(&g->loss, 4));
     HIP_TRY(hipMemsetAsync(g->m, 0, (size_t)pfdr::kParams * 8, st));
     HIP_TRY(hipMemsetAsync(g->v, 0, (size_t)pfdr::kParams * 8, st));
     HIP_TRY(hipStreamSynchronize(st));  // (yd leaves scope)
@@ -735,7 +658,7 @@ int adh_pfdr_epoch(adh_pfdr_t *g, const int32_t *order, int32_t n_steps, const d
     hipStream_t st = g->h->stream;
     HIP_TRY(hipMemcpyAsync(g->order, order, (size_t)g->n_train * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(g->lr, step_size, (size_t)n_steps * 8, hipMemcpyHostToDevice, st));
-    const int rc = pfdr::timed(g, g->epochs_ms, true, [&]() -> int {
+    const int rc = sess::timed(g->ev, st, g->epochs_ms, [&]() -> int {  // (adds up over the epochs of one fit)
         hipLaunchKernelGGL(pfdr::epoch_kernel, dim3(1), dim3(pfdr::kEpochBlock), 0, st, g->x, g->y, (int32_t)g->n_train, g->order,
                            g->lr, g->params, g->m, g->v, g->loss);
         HIP_TRY(hipGetLastError());
@@ -760,7 +683,8 @@ int adh_pfdr_predict(adh_pfdr_t *g, int64_t n, const double *x, double *proba) {
     HIP_TRY(s.alloc(&d_x, (size_t)n * pfdr::kIn));
     HIP_TRY(s.alloc(&d_p, (size_t)n));
     HIP_TRY(hipMemcpyAsync(d_x, x, (size_t)n * pfdr::kIn * 8, hipMemcpyHostToDevice, st));
-    const int rc = pfdr::timed(g, g->predict_ms, false, [&]() -> int {
+    g->predict_ms = 0.0;
+    const int rc = sess::timed(g->ev, st, g->predict_ms, [&]() -> int {
         hipLaunchKernelGGL(pfdr::predict_kernel, dim3(pfdr::grid_for(n)), dim3(pfdr::kBlock), 0, st, d_x, n, g->params, d_p);
         HIP_TRY(hipGetLastError());
         return ADH_OK;
@@ -784,7 +708,8 @@ int adh_pfdr_gather(adh_pfdr_t *g, int64_t n_groups, const double *group_value, 
     HIP_TRY(s.alloc(&d_v, (size_t)n_groups));
     HIP_TRY(s.alloc(&d_out, (size_t)g->n_rows));
     HIP_TRY(hipMemcpyAsync(d_v, group_value, (size_t)n_groups * 8, hipMemcpyHostToDevice, st));
-    const int rc = pfdr::timed(g, g->gather_ms, false, [&]() -> int {
+    g->gather_ms = 0.0;
+    const int rc = sess::timed(g->ev, st, g->gather_ms, [&]() -> int {
         hipLaunchKernelGGL(pfdr::gather_kernel, dim3(pfdr::grid_for(g->n_rows)), dim3(pfdr::kBlock), 0, st, g->row_group, d_v,
                            g->n_rows, d_out);
         HIP_TRY(hipGetLastError());

@@ -11,63 +11,42 @@
 // n_keys x n_runs matrices (adh_quant_build).  The matrices stay on the device: the host copies the ones it needs
 // (adh_quant_matrix), and every filter call (adh_quant_filter) reads the quality matrix in place - a row mean in the
 // order NumPy takes it, a radix sort by (group, mean descending, row), a rank per group, the mask.
-// Included by adh_api.hip (shares its error helpers and the handle).
+// Included by adh_api.hip behind adh_session.h (shares its error helpers, the handle and the session helpers).
 
 struct adh_quant {
+    // scratch that grows with the largest run or filter seen: sized in bytes with an eighth of slack
+    using Scratch = sess::DevArray<unsigned char, sess::eighth_slack>;
     adh_handle_t *h = nullptr;
     int32_t n_cols = 0;
-    uint32_t *psm = nullptr;  // sorted distinct precursor_idx of the PSMs
+    sess::DevArray<uint32_t, sess::as_asked> psm;  // sorted distinct precursor_idx of the PSMs
     int64_t n_psm = 0;
     // kept rows of all runs in run order: ion key, precursor_idx, run, then n_cols value columns of cap rows each
     int64_t n_rows = 0, cap = 0;
-    int64_t *ion = nullptr;
-    uint32_t *pidx = nullptr, *run = nullptr;
-    float *val = nullptr;
+    sess::DevArray<int64_t> ion;
+    sess::DevArray<uint32_t> pidx, run;
+    sess::DevArray<float> val;
     int32_t n_runs = 0;
-    // one run's input columns and its row flags / offsets
-    void *in = nullptr;
-    size_t in_bytes = 0;
-    uint32_t *off = nullptr;
-    size_t off_bytes = 0;
+    // one run's input columns and its row flags / offsets (u32)
+    Scratch in, off;
     // the built union: keys, matrices (n_cols x n_runs columns of n_keys), filter scratch
     bool built = false, duplicate = false;
     int64_t n_keys = 0;
-    int64_t *key_ion = nullptr;
-    uint32_t *key_pidx = nullptr;
-    float *mat = nullptr;
-    size_t mat_bytes = 0;
-    void *work = nullptr, *tmp = nullptr;
-    size_t work_bytes = 0, tmp_bytes = 0;
-    uint32_t *flag = nullptr;  // one u32 on the device: a run holds a key twice
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    sess::DevArray<int64_t, sess::as_asked> key_ion;  // (built once, with at least one key: the exact size)
+    sess::DevArray<uint32_t, sess::as_asked> key_pidx;
+    sess::DevArray<float, sess::as_asked> mat;
+    Scratch work, tmp;  // tmp: hipCUB temporary storage
+    sess::DevArray<uint32_t> flag;  // one u32 on the device: a run holds a key twice
+    sess::EventPair ev;
     double build_ms = 0.0, filter_ms = 0.0;
 };
 
 namespace quant {
 
-constexpr int kBlock = 256;
+using sess::grid_for;
+using sess::kBlock;
 constexpr uint32_t kNoGroup = 0xFFFFFFFFu;
 
-inline unsigned grid_for(int64_t n) {
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + kBlock - 1) / kBlock, 16384));
-}
-
 __host__ __device__ inline size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
-
-// grow-only device buffer (contents are not kept)
-inline hipError_t reserve(void **p, size_t &have, size_t need) {
-    if (have >= need && *p) return hipSuccess;
-    if (*p) {
-        hipError_t e = hipDeviceSynchronize();
-        if (e != hipSuccess) return e;
-        (void)hipFree(*p);
-        *p = nullptr;
-        have = 0;
-    }
-    hipError_t e = hipMalloc(p, need + need / 8 + 256);
-    if (e == hipSuccess) have = need + need / 8 + 256;
-    return e;
-}
 
 // the ion key (quant_builder.py:52-81) in int64: precursor_idx + number << 32 + type << 40 + charge << 48 +
 // loss_type << 56, wrapping as Numba's int64 arithmetic does
@@ -116,11 +95,6 @@ __global__ void __launch_bounds__(kBlock) append_kernel(const unsigned char *__r
         run[j] = run_id;
         for (int c = 0; c < n_cols; ++c) val[(size_t)c * (size_t)cap + (size_t)j] = cols[(size_t)c * b4 / 4 + (size_t)i];
     }
-}
-
-__global__ void __launch_bounds__(kBlock) iota_kernel(uint32_t *__restrict__ v, int64_t n) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) v[i] = (uint32_t)i;
 }
 
 // head[i] = the sorted key at i starts a new key; a key repeated inside one run raises the flag (the reference's
@@ -230,59 +204,37 @@ __global__ void __launch_bounds__(kBlock) rank_kernel(const uint64_t *__restrict
     }
 }
 
-template <typename F>
-int timed(adh_quant *q, double &ms, F &&body) {
-    hipStream_t st = q->h->stream;
-    if (!q->e0) HIP_TRY(hipEventCreate(&q->e0));
-    if (!q->e1) HIP_TRY(hipEventCreate(&q->e1));
-    HIP_TRY(hipEventRecord(q->e0, st));
-    const int rc = body();
-    if (rc != ADH_OK) return rc;
-    HIP_TRY(hipEventRecord(q->e1, st));
-    HIP_TRY(hipEventSynchronize(q->e1));
-    float f = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&f, q->e0, q->e1));
-    ms = f;
-    return ADH_OK;
-}
-
 // the appended row buffers grown to hold `need` rows, the rows so far kept
 int grow_rows(adh_quant *q, int64_t need) {
     if (need <= q->cap) return ADH_OK;
     const int64_t cap = std::max<int64_t>(need, q->cap + q->cap / 2 + 4096);
     hipStream_t st = q->h->stream;
-    int64_t *ion = nullptr;
-    uint32_t *pidx = nullptr, *run = nullptr;
-    float *val = nullptr;
-    hipError_t e = hipMalloc(&ion, (size_t)cap * 8);
-    if (e == hipSuccess) e = hipMalloc(&pidx, (size_t)cap * 4);
-    if (e == hipSuccess) e = hipMalloc(&run, (size_t)cap * 4);
-    if (e == hipSuccess) e = hipMalloc(&val, (size_t)cap * 4 * (size_t)std::max(q->n_cols, 1));
+    sess::DevArray<int64_t> ion;
+    sess::DevArray<uint32_t> pidx, run;
+    sess::DevArray<float> val;
+    hipError_t e = ion.reserve((size_t)cap);
+    if (e == hipSuccess) e = pidx.reserve((size_t)cap);
+    if (e == hipSuccess) e = run.reserve((size_t)cap);
+    if (e == hipSuccess) e = val.reserve((size_t)cap * (size_t)std::max(q->n_cols, 1));
     if (e == hipSuccess && q->n_rows > 0) {
         const size_t r = (size_t)q->n_rows;
-        e = hipMemcpyAsync(ion, q->ion, r * 8, hipMemcpyDeviceToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(pidx, q->pidx, r * 4, hipMemcpyDeviceToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(run, q->run, r * 4, hipMemcpyDeviceToDevice, st);
+        e = hipMemcpyAsync(ion.p, q->ion.p, r * 8, hipMemcpyDeviceToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(pidx.p, q->pidx.p, r * 4, hipMemcpyDeviceToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(run.p, q->run.p, r * 4, hipMemcpyDeviceToDevice, st);
         for (int c = 0; c < q->n_cols && e == hipSuccess; ++c)
-            e = hipMemcpyAsync(val + (size_t)c * (size_t)cap, q->val + (size_t)c * (size_t)q->cap, r * 4,
+            e = hipMemcpyAsync(val.p + (size_t)c * (size_t)cap, q->val.p + (size_t)c * (size_t)q->cap, r * 4,
                                hipMemcpyDeviceToDevice, st);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        for (void *p : {(void *)ion, (void *)pidx, (void *)run, (void *)val})
-            if (p) (void)hipFree(p);
         return fail(e == hipErrorOutOfMemory ? ADH_ERR_OUT_OF_MEMORY : ADH_ERR_HIP,
                     std::string("adh_quant_add_run: row buffers: ") + hipGetErrorString(e));
     }
-    for (void *p : {(void *)q->ion, (void *)q->pidx, (void *)q->run, (void *)q->val})
-        if (p) (void)hipFree(p);
-    q->ion = ion, q->pidx = pidx, q->run = run, q->val = val, q->cap = cap;
+    // (the old buffers leave with the locals)
+    q->ion.swap(ion), q->pidx.swap(pidx), q->run.swap(run), q->val.swap(val), q->cap = cap;
     return ADH_OK;
 }
-
-// hipCUB temporary storage of at least `need` bytes in q->tmp
-inline hipError_t reserve_tmp(adh_quant *q, size_t need) { return reserve(&q->tmp, q->tmp_bytes, need); }
 
 }  // namespace quant
 
@@ -301,10 +253,10 @@ int adh_quant_create(adh_handle_t *h, int32_t n_columns, const uint32_t *psm_pre
     q->h = h;
     q->n_cols = n_columns;
     q->n_psm = n_psm;
-    hipError_t e = hipMalloc(&q->psm, (size_t)std::max<int64_t>(n_psm, 1) * 4);
+    hipError_t e = q->psm.reserve((size_t)std::max<int64_t>(n_psm, 1));
     if (e == hipSuccess && n_psm > 0)
-        e = hipMemcpyAsync(q->psm, psm_precursor_idx, (size_t)n_psm * 4, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMalloc(&q->flag, 16);
+        e = hipMemcpyAsync(q->psm.p, psm_precursor_idx, (size_t)n_psm * 4, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = q->flag.reserve(4);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) {
         adh_quant_destroy(q);
@@ -320,13 +272,7 @@ int adh_quant_destroy(adh_quant_t *q) {
     if (!q) return ADH_OK;
     (void)hipSetDevice(q->h->device);
     (void)hipStreamSynchronize(q->h->stream);
-    for (void *p : {(void *)q->psm, (void *)q->ion, (void *)q->pidx, (void *)q->run, (void *)q->val, q->in,
-                    (void *)q->off, (void *)q->key_ion, (void *)q->key_pidx, (void *)q->mat, q->work, q->tmp,
-                    (void *)q->flag})
-        if (p) (void)hipFree(p);
-    if (q->e0) (void)hipEventDestroy(q->e0);
-    if (q->e1) (void)hipEventDestroy(q->e1);
-    delete q;
+    delete q;  // (the members free their device memory and events)
     return ADH_OK;
 }
 
@@ -349,9 +295,10 @@ int adh_quant_add_run(adh_quant_t *q, int64_t n, const uint32_t *precursor_idx, 
     hipStream_t st = q->h->stream;
     using quant::align16;
     const size_t b4 = align16((size_t)n * 4), b1 = align16((size_t)n);
-    HIP_TRY(quant::reserve(&q->in, q->in_bytes, b4 + 4 * b1 + (size_t)q->n_cols * b4));
-    HIP_TRY(quant::reserve((void **)&q->off, q->off_bytes, (size_t)(n + 1) * 4));
-    unsigned char *in = static_cast<unsigned char *>(q->in);
+    HIP_TRY(q->in.reserve(b4 + 4 * b1 + (size_t)q->n_cols * b4));
+    HIP_TRY(q->off.reserve((size_t)(n + 1) * 4));
+    unsigned char *in = q->in.p;
+    uint32_t *off = reinterpret_cast<uint32_t *>(q->off.p);
     HIP_TRY(hipMemcpyAsync(in, precursor_idx, (size_t)n * 4, hipMemcpyHostToDevice, st));
     const uint8_t *bytes[4] = {number, type, charge, loss_type};
     for (int j = 0; j < 4; ++j)
@@ -359,21 +306,17 @@ int adh_quant_add_run(adh_quant_t *q, int64_t n, const uint32_t *precursor_idx, 
     for (int c = 0; c < q->n_cols; ++c)
         HIP_TRY(hipMemcpyAsync(in + b4 + 4 * b1 + (size_t)c * b4, columns[c], (size_t)n * 4, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(quant::member_kernel, dim3(quant::grid_for(n + 1)), dim3(quant::kBlock), 0, st,
-                       reinterpret_cast<const uint32_t *>(in), n, q->psm, q->n_psm, q->off);
+                       reinterpret_cast<const uint32_t *>(in), n, q->psm.p, q->n_psm, off);
     HIP_TRY(hipGetLastError());
-    size_t need = 0;
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, q->off, q->off, (int)(n + 1), st));
-    HIP_TRY(quant::reserve_tmp(q, need));
-    need = q->tmp_bytes;
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(q->tmp, need, q->off, q->off, (int)(n + 1), st));
+    ADH_TRY(sess::exclusive_sum(q->tmp, off, off, n + 1, st));
     uint32_t kept = 0;
-    HIP_TRY(hipMemcpyAsync(&kept, q->off + n, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&kept, off + n, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     const int rc = quant::grow_rows(q, q->n_rows + (int64_t)kept);
     if (rc != ADH_OK) return rc;
     if (kept > 0) {
         hipLaunchKernelGGL(quant::append_kernel, dim3(quant::grid_for(n)), dim3(quant::kBlock), 0, st, in, n, q->n_cols,
-                           q->off, q->n_rows, run_id, q->ion, q->pidx, q->run, q->val, q->cap);
+                           off, q->n_rows, run_id, q->ion.p, q->pidx.p, q->run.p, q->val.p, q->cap);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(st));  // (the next run reuses the input buffer)
     }
@@ -391,35 +334,34 @@ int adh_quant_build(adh_quant_t *q, int64_t *n_keys, int32_t *duplicate) {
     const int R = q->n_runs;
     int64_t keys = 0;
     bool dup = false;
-    const int rc = quant::timed(q, q->build_ms, [&]() -> int {
+    q->build_ms = 0.0;
+    const int rc = sess::timed(q->ev, st, q->build_ms, [&]() -> int {
         if (n == 0) return ADH_OK;
         if (R == 1) {
             keys = n;
         } else {
             // work: sorted keys [n] i64 | perm in [n] u32 | perm [n] u32 | key id [n] u32
             const size_t wb = quant::align16((size_t)n * 8) + 3 * quant::align16((size_t)n * 4);
-            HIP_TRY(quant::reserve(&q->work, q->work_bytes, wb));
-            unsigned char *w = static_cast<unsigned char *>(q->work);
+            HIP_TRY(q->work.reserve(wb));
+            unsigned char *w = q->work.p;
             int64_t *skey = reinterpret_cast<int64_t *>(w);
             uint32_t *perm_in = reinterpret_cast<uint32_t *>(w + quant::align16((size_t)n * 8));
             uint32_t *perm = perm_in + quant::align16((size_t)n * 4) / 4;
             uint32_t *kid = perm + quant::align16((size_t)n * 4) / 4;
-            hipLaunchKernelGGL(quant::iota_kernel, dim3(quant::grid_for(n)), dim3(quant::kBlock), 0, st, perm_in, n);
+            hipLaunchKernelGGL(sess::iota_kernel, dim3(quant::grid_for(n)), dim3(quant::kBlock), 0, st, perm_in, n);
             HIP_TRY(hipGetLastError());
-            size_t need = 0;
-            HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, need, q->ion, skey, perm_in, perm, (int)n, 0, 64, st));
-            size_t need_scan = 0;
-            HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, need_scan, kid, kid, (int)n, st));
-            HIP_TRY(quant::reserve_tmp(q, std::max(need, need_scan)));
-            need = q->tmp_bytes;
+            // one block for the sort and the scan
+            sess::TmpSize both;
+            ADH_TRY(sess::sort_pairs(both, q->ion.p, skey, perm_in, perm, n, 64, st));
+            ADH_TRY(sess::inclusive_sum(both, kid, kid, n, st));
+            HIP_TRY(q->tmp.reserve(both.bytes));
             // stable: rows of one key stay in run order
-            HIP_TRY(hipcub::DeviceRadixSort::SortPairs(q->tmp, need, q->ion, skey, perm_in, perm, (int)n, 0, 64, st));
+            ADH_TRY(sess::sort_pairs(q->tmp, q->ion.p, skey, perm_in, perm, n, 64, st));
             HIP_TRY(hipMemsetAsync(q->flag, 0, 4, st));
-            hipLaunchKernelGGL(quant::head_kernel, dim3(quant::grid_for(n)), dim3(quant::kBlock), 0, st, skey, perm, q->run,
-                               n, kid, q->flag);
+            hipLaunchKernelGGL(quant::head_kernel, dim3(quant::grid_for(n)), dim3(quant::kBlock), 0, st, skey, perm, q->run.p,
+                               n, kid, q->flag.p);
             HIP_TRY(hipGetLastError());
-            need = q->tmp_bytes;
-            HIP_TRY(hipcub::DeviceScan::InclusiveSum(q->tmp, need, kid, kid, (int)n, st));
+            ADH_TRY(sess::inclusive_sum(q->tmp, kid, kid, n, st));
             uint32_t hk[2] = {0, 0};
             HIP_TRY(hipMemcpyAsync(&hk[0], kid + n - 1, 4, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipMemcpyAsync(&hk[1], q->flag, 4, hipMemcpyDeviceToHost, st));
@@ -428,22 +370,23 @@ int adh_quant_build(adh_quant_t *q, int64_t *n_keys, int32_t *duplicate) {
             dup = hk[1] != 0;
             if (dup) return ADH_OK;  // (the host merges these rows itself)
         }
-        HIP_TRY(hipMalloc(&q->key_ion, (size_t)keys * 8));
-        HIP_TRY(hipMalloc(&q->key_pidx, (size_t)keys * 4));
-        q->mat_bytes = (size_t)keys * (size_t)R * (size_t)q->n_cols * 4;
-        HIP_TRY(hipMalloc(&q->mat, q->mat_bytes));
+        const size_t plane = (size_t)keys * (size_t)R * (size_t)q->n_cols;
+        HIP_TRY(q->key_ion.reserve((size_t)keys));
+        HIP_TRY(q->key_pidx.reserve((size_t)keys));
+        HIP_TRY(q->mat.reserve(plane));
         if (R == 1) {
-            hipLaunchKernelGGL(quant::single_kernel, dim3(quant::grid_for(n)), dim3(quant::kBlock), 0, st, q->ion, q->pidx,
-                               q->val, q->cap, n, q->n_cols, q->key_ion, q->key_pidx, q->mat);
+            hipLaunchKernelGGL(quant::single_kernel, dim3(quant::grid_for(n)), dim3(quant::kBlock), 0, st, q->ion.p, q->pidx.p,
+                               q->val.p, q->cap, n, q->n_cols, q->key_ion.p, q->key_pidx.p, q->mat.p);
         } else {
-            HIP_TRY(hipMemsetAsync(q->mat, 0, q->mat_bytes, st));
-            unsigned char *w = static_cast<unsigned char *>(q->work);
+            HIP_TRY(hipMemsetAsync(q->mat, 0, plane * 4, st));
+            unsigned char *w = q->work.p;
             const int64_t *skey = reinterpret_cast<const int64_t *>(w);
             const uint32_t *perm = reinterpret_cast<const uint32_t *>(w + quant::align16((size_t)n * 8)) +
                                    quant::align16((size_t)n * 4) / 4;
             const uint32_t *kid = perm + quant::align16((size_t)n * 4) / 4;
             hipLaunchKernelGGL(quant::scatter_kernel, dim3(quant::grid_for(n)), dim3(quant::kBlock), 0, st, skey, perm, kid,
-                               n, q->pidx, q->run, q->val, q->cap, q->n_cols, keys, R, q->key_ion, q->key_pidx, q->mat);
+                               n, q->pidx.p, q->run.p, q->val.p, q->cap, q->n_cols, keys, R, q->key_ion.p, q->key_pidx.p,
+                               q->mat.p);
         }
         HIP_TRY(hipGetLastError());
         return ADH_OK;
@@ -463,8 +406,8 @@ int adh_quant_keys(adh_quant_t *q, int64_t *ion, uint32_t *precursor_idx) {
     if (q->n_keys == 0) return ADH_OK;
     HIP_TRY(hipSetDevice(q->h->device));
     hipStream_t st = q->h->stream;
-    HIP_TRY(hipMemcpyAsync(ion, q->key_ion, (size_t)q->n_keys * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(precursor_idx, q->key_pidx, (size_t)q->n_keys * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(ion, q->key_ion.p, (size_t)q->n_keys * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(precursor_idx, q->key_pidx.p, (size_t)q->n_keys * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     q->h->d2h_bytes += (uint64_t)q->n_keys * 12;
     return ADH_OK;
@@ -477,7 +420,7 @@ int adh_quant_matrix(adh_quant_t *q, int32_t column, float *out) {
     if (q->n_keys == 0) return ADH_OK;
     HIP_TRY(hipSetDevice(q->h->device));
     const size_t plane = (size_t)q->n_keys * (size_t)q->n_runs;
-    HIP_TRY(hipMemcpyAsync(out, q->mat + (size_t)column * plane, plane * 4, hipMemcpyDeviceToHost, q->h->stream));
+    HIP_TRY(hipMemcpyAsync(out, q->mat.p + (size_t)column * plane, plane * 4, hipMemcpyDeviceToHost, q->h->stream));
     HIP_TRY(hipStreamSynchronize(q->h->stream));
     q->h->d2h_bytes += plane * 4;
     return ADH_OK;
@@ -490,12 +433,12 @@ int adh_quant_rows(adh_quant_t *q, int64_t *ion, uint32_t *precursor_idx, uint32
     HIP_TRY(hipSetDevice(q->h->device));
     hipStream_t st = q->h->stream;
     const size_t r = (size_t)q->n_rows;
-    HIP_TRY(hipMemcpyAsync(ion, q->ion, r * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(precursor_idx, q->pidx, r * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(run, q->run, r * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(ion, q->ion.p, r * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(precursor_idx, q->pidx.p, r * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(run, q->run.p, r * 4, hipMemcpyDeviceToHost, st));
     for (int c = 0; c < q->n_cols; ++c) {
         if (!columns[c]) return fail(ADH_ERR_INVALID_ARGUMENT, "adh_quant_rows: a quantity column is NULL");
-        HIP_TRY(hipMemcpyAsync(columns[c], q->val + (size_t)c * (size_t)q->cap, r * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(columns[c], q->val.p + (size_t)c * (size_t)q->cap, r * 4, hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(hipStreamSynchronize(st));
     q->h->d2h_bytes += r * (16 + 4 * (size_t)q->n_cols);
@@ -512,12 +455,11 @@ int adh_quant_set_matrix(adh_quant_t *q, int64_t n_keys, int32_t n_runs, const f
     hipStream_t st = q->h->stream;
     q->n_runs = n_runs;
     q->n_keys = n_keys;
-    q->mat_bytes = (size_t)n_keys * (size_t)n_runs * 4;
     if (n_keys > 0) {
-        HIP_TRY(hipMalloc(&q->mat, q->mat_bytes));
+        HIP_TRY(q->mat.reserve((size_t)n_keys * (size_t)n_runs));
         for (int r = 0; r < n_runs; ++r) {
             if (!run_columns[r]) return fail(ADH_ERR_INVALID_ARGUMENT, "adh_quant_set_matrix: a run column is NULL");
-            HIP_TRY(hipMemcpyAsync(q->mat + (size_t)r * (size_t)n_keys, run_columns[r], (size_t)n_keys * 4,
+            HIP_TRY(hipMemcpyAsync(q->mat.p + (size_t)r * (size_t)n_keys, run_columns[r], (size_t)n_keys * 4,
                                    hipMemcpyHostToDevice, st));
         }
         HIP_TRY(hipStreamSynchronize(st));
@@ -546,8 +488,8 @@ int adh_quant_filter(adh_quant_t *q, int32_t column, const int32_t *group, int32
                  o_rout = o_rin + align16((size_t)n * 4), o_first = o_rout + align16((size_t)n * 4),
                  o_rank = o_first + align16((size_t)std::max(n_groups, 1) * 4), o_mask = o_rank + align16((size_t)n * 8),
                  wb = o_mask + align16((size_t)n);
-    HIP_TRY(quant::reserve(&q->work, q->work_bytes, wb));
-    unsigned char *w = static_cast<unsigned char *>(q->work);
+    HIP_TRY(q->work.reserve(wb));
+    unsigned char *w = q->work.p;
     int32_t *d_group = reinterpret_cast<int32_t *>(w);
     float *d_total = reinterpret_cast<float *>(w + o_total);
     uint64_t *kin = reinterpret_cast<uint64_t *>(w + o_kin), *kout = reinterpret_cast<uint64_t *>(w + o_kout);
@@ -555,19 +497,20 @@ int adh_quant_filter(adh_quant_t *q, int32_t column, const int32_t *group, int32
     uint32_t *first = reinterpret_cast<uint32_t *>(w + o_first);
     double *d_rank = reinterpret_cast<double *>(w + o_rank);
     uint8_t *d_mask = w + o_mask;
-    size_t need = 0;
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, need, kin, kout, rin, rout, (int)n, 0, 64, st));
-    HIP_TRY(quant::reserve_tmp(q, need));
+    // (the sort's temporary storage is in place before the timed part)
+    sess::TmpSize sort;
+    ADH_TRY(sess::sort_pairs(sort, kin, kout, rin, rout, n, 64, st));
+    HIP_TRY(q->tmp.reserve(sort.bytes));
     HIP_TRY(hipMemcpyAsync(d_group, group, (size_t)n * 4, hipMemcpyHostToDevice, st));
     const int32_t R = q->n_runs;
-    const float *m = q->mat + (size_t)column * (size_t)n * (size_t)R;
-    int rc = quant::timed(q, q->filter_ms, [&]() -> int {
+    const float *m = q->mat.p + (size_t)column * (size_t)n * (size_t)R;
+    q->filter_ms = 0.0;
+    int rc = sess::timed(q->ev, st, q->filter_ms, [&]() -> int {
         hipLaunchKernelGGL(quant::total_kernel, dim3(quant::grid_for(n)), dim3(quant::kBlock), 0, st, m, n, R, d_group,
                            d_total, kin, rin);
         HIP_TRY(hipGetLastError());
-        size_t tb = q->tmp_bytes;
         // stable: ties keep the row order (method="first")
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(q->tmp, tb, kin, kout, rin, rout, (int)n, 0, 64, st));
+        ADH_TRY(sess::sort_pairs(q->tmp, kin, kout, rin, rout, n, 64, st));
         hipLaunchKernelGGL(quant::first_kernel, dim3(quant::grid_for(n)), dim3(quant::kBlock), 0, st, kout, n, first);
         HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(quant::rank_kernel, dim3(quant::grid_for(n)), dim3(quant::kBlock), 0, st, kout, rout, n, first,

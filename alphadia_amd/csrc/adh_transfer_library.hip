@@ -24,90 +24,36 @@
 // adh_tl_rt_norm:  two max reductions (NaN-skipping for pandas' max, NaN-propagating for np.max) and the elementwise
 //                  formula, every operation in the reference's order and in the dtype NumPy's promotion gives it.
 //
-// All global writes are plain vector stores or vector integer atomics.  Included by adh_api.hip (shares its error
-// helpers and the handle).
+// All global writes are plain vector stores or vector integer atomics.  Included by adh_api.hip behind adh_session.h
+// (shares its error helpers, the handle and the session helpers); adh_mbr_library.hip includes this file for the
+// block-bookkeeping kernels of namespace tl.
+#pragma once
 
 struct adh_tl {
     adh_handle_t *h = nullptr;
     int32_t C = 0, M = 0;
     // the consensus: key columns and dense-row blocks of its precursors, the dense matrices
     int64_t n_prec = 0, n_rows = 0;
-    uint64_t *hk = nullptr, *pk = nullptr, *ik = nullptr;
-    int64_t *start = nullptr, *stop = nullptr;
-    float *mat[ADH_TL_MAX_MATRICES] = {nullptr, nullptr, nullptr, nullptr};
+    sess::DevArray<uint64_t> hk, pk, ik;
+    sess::DevArray<int64_t> start, stop;
+    sess::DevArray<float> mat[ADH_TL_MAX_MATRICES];
     int hash_signed = -1;
     // the staged run of adh_tl_scatter
-    float *staged[ADH_TL_MAX_MATRICES] = {nullptr, nullptr, nullptr, nullptr};
+    sess::DevArray<float> staged[ADH_TL_MAX_MATRICES];
     int64_t staged_rows = -1;
     // the kept rows of the last update
-    uint32_t *kept = nullptr;
+    sess::DevArray<uint32_t> kept;
     int64_t n_kept = -1;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    sess::EventPair ev;
     double topk_ms = 0.0, gather_ms = 0.0, scatter_ms = 0.0;
 };
 
 namespace tl {
 
-constexpr int kBlock = 256;
+using sess::grid_for;
+using sess::kBlock;
 constexpr int kWave = 64;
 constexpr int kQcSlice = ADH_TL_QC_SLICE;  // floats of LDS per wavefront
-
-inline unsigned grid_for(int64_t n) {
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + kBlock - 1) / kBlock, 16384));
-}
-
-struct Bufs {
-    std::vector<void *> ptrs;
-    ~Bufs() {
-        for (void *p : ptrs)
-            if (p) (void)hipFree(p);
-    }
-    template <typename T>
-    hipError_t alloc(T **p, size_t n) {
-        void *v = nullptr;
-        hipError_t e = hipMalloc(&v, std::max<size_t>(n, 4) * sizeof(T));
-        if (e != hipSuccess) return e;
-        ptrs.push_back(v);
-        *p = static_cast<T *>(v);
-        return hipSuccess;
-    }
-    // the caller keeps p
-    void keep(void *p) {
-        for (void *&q : ptrs)
-            if (q == p) q = nullptr;
-    }
-};
-
-template <typename T>
-void drop(T *&p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
-
-struct Timer {
-    hipEvent_t &e0, &e1;
-    hipStream_t st;
-    int begin() {
-        if (!e0) HIP_TRY(hipEventCreate(&e0));
-        if (!e1) HIP_TRY(hipEventCreate(&e1));
-        HIP_TRY(hipEventRecord(e0, st));
-        return ADH_OK;
-    }
-    int end(double &ms) {
-        HIP_TRY(hipEventRecord(e1, st));
-        HIP_TRY(hipEventSynchronize(e1));
-        float f = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&f, e0, e1));
-        ms += f;
-        return ADH_OK;
-    }
-};
-
-#define TL_TRY(expr)                 \
-    do {                             \
-        const int _rc = (expr);      \
-        if (_rc != ADH_OK) return _rc; \
-    } while (0)
 
 // ---- the dense scatter ------------------------------------------------------------------------------------------
 
@@ -155,11 +101,6 @@ __global__ void __launch_bounds__(kBlock) key_kernel(const uint64_t *__restrict_
         o_start[i] = start[i] + row0;
         o_stop[i] = stop[i] + row0;
     }
-}
-
-__global__ void __launch_bounds__(kBlock) iota_kernel(uint32_t *__restrict__ out, int64_t n) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = (uint32_t)i;
 }
 
 __global__ void __launch_bounds__(kBlock) take_kernel(const uint64_t *__restrict__ key, const uint32_t *__restrict__ perm,
@@ -244,16 +185,6 @@ __global__ void __launch_bounds__(kBlock) row_gather_kernel(const float *__restr
         const int64_t s = src_row[r];
         out[e] = s < rows0 ? cons[s * C + c] : run[(s - rows0) * C + c];
     }
-}
-
-template <typename K>
-int sort_pairs(Bufs &B, const K *k_in, K *k_out, const uint32_t *v_in, uint32_t *v_out, int64_t n, hipStream_t st) {
-    size_t need = 0;
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, need, k_in, k_out, v_in, v_out, (int)n, 0, (int)sizeof(K) * 8, st));
-    unsigned char *tmp = nullptr;
-    HIP_TRY(B.alloc(&tmp, need));
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, need, k_in, k_out, v_in, v_out, (int)n, 0, (int)sizeof(K) * 8, st));
-    return ADH_OK;
 }
 
 // ---- MS2 quality control ----------------------------------------------------------------------------------------
@@ -467,7 +398,7 @@ __global__ void __launch_bounds__(kBlock) rt_delta_kernel(const TO *__restrict__
 }
 
 template <typename T, bool SKIP>
-int reduce_max(Bufs &B, const T *x, int64_t n, T **out, hipStream_t st) {
+int reduce_max(sess::DevBufs &B, const T *x, int64_t n, T **out, hipStream_t st) {
     const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + kBlock - 1) / kBlock, 1024));
     T *part = nullptr;
     HIP_TRY(B.alloc(&part, (size_t)blocks));
@@ -480,18 +411,18 @@ int reduce_max(Bufs &B, const T *x, int64_t n, T **out, hipStream_t st) {
 }
 
 template <typename TO, typename TC, typename TL>
-int rt_delta_max(Bufs &B, const void *d_obs, const void *d_cal, const void *d_lib, int64_t n, void *d_out, hipStream_t st) {
+int rt_delta_max(sess::DevBufs &B, const void *d_obs, const void *d_cal, const void *d_lib, int64_t n, void *d_out, hipStream_t st) {
     using TN = decltype(TL() * (TO() - TC()));
     const TO *obs = (const TO *)d_obs;
     TN *cn = nullptr;
     TO *obs_max = nullptr;
     TN *cn_max = nullptr;
     HIP_TRY(B.alloc(&cn, (size_t)n));
-    TL_TRY((reduce_max<TO, false>(B, obs, n, &obs_max, st)));
+    ADH_TRY((reduce_max<TO, false>(B, obs, n, &obs_max, st)));
     hipLaunchKernelGGL((rt_calibrated_kernel<TO, TC, TL, TN>), dim3(grid_for(n)), dim3(kBlock), 0, st, obs, (const TC *)d_cal,
                        (const TL *)d_lib, n, cn);
     HIP_TRY(hipGetLastError());
-    TL_TRY((reduce_max<TN, false>(B, cn, n, &cn_max, st)));
+    ADH_TRY((reduce_max<TN, false>(B, cn, n, &cn_max, st)));
     hipLaunchKernelGGL((rt_delta_kernel<TO, TN>), dim3(grid_for(n)), dim3(kBlock), 0, st, obs, (const TO *)obs_max,
                        (const TN *)cn, (const TN *)cn_max, n, (TN *)d_out);
     HIP_TRY(hipGetLastError());
@@ -499,7 +430,7 @@ int rt_delta_max(Bufs &B, const void *d_obs, const void *d_cal, const void *d_li
 }
 
 void release_staged(adh_tl *g) {
-    for (int m = 0; m < ADH_TL_MAX_MATRICES; ++m) drop(g->staged[m]);
+    for (int m = 0; m < ADH_TL_MAX_MATRICES; ++m) g->staged[m].release();
     g->staged_rows = -1;
 }
 
@@ -524,12 +455,7 @@ int adh_tl_destroy(adh_tl_t *g) {
     if (!g) return ADH_OK;
     (void)hipSetDevice(g->h->device);
     (void)hipStreamSynchronize(g->h->stream);
-    tl::release_staged(g);
-    for (int m = 0; m < ADH_TL_MAX_MATRICES; ++m) tl::drop(g->mat[m]);
-    tl::drop(g->hk), tl::drop(g->pk), tl::drop(g->ik), tl::drop(g->start), tl::drop(g->stop), tl::drop(g->kept);
-    if (g->e0) (void)hipEventDestroy(g->e0);
-    if (g->e1) (void)hipEventDestroy(g->e1);
-    delete g;
+    delete g;  // (the members free their device memory and events)
     return ADH_OK;
 }
 
@@ -549,30 +475,23 @@ int adh_tl_scatter(adh_tl_t *g, int64_t n_rows, int64_t n_flat, const int64_t *r
     HIP_TRY(hipStreamSynchronize(st));
     tl::release_staged(g);
     const size_t cells = (size_t)n_rows * (size_t)g->C;
-    tl::Bufs B;
+    sess::DevBufs B;
     int64_t *d_row = nullptr;
     int32_t *d_col = nullptr, *d_dup = nullptr;
     float *d_mz = nullptr, *d_in = nullptr, *d_co = nullptr;
     uint32_t *occ = nullptr;
-    HIP_TRY(B.alloc(&d_row, (size_t)n_flat));
-    HIP_TRY(B.alloc(&d_col, (size_t)n_flat));
-    HIP_TRY(B.alloc(&d_mz, (size_t)n_flat));
-    HIP_TRY(B.alloc(&d_in, (size_t)n_flat));
-    HIP_TRY(B.alloc(&d_co, (size_t)n_flat));
+    HIP_TRY(B.upload(&d_row, row, (size_t)n_flat, st));
+    HIP_TRY(B.upload(&d_col, col, (size_t)n_flat, st));
+    HIP_TRY(B.upload(&d_mz, mz, (size_t)n_flat, st));
+    HIP_TRY(B.upload(&d_in, intensity, (size_t)n_flat, st));
+    HIP_TRY(B.upload(&d_co, correlation, (size_t)n_flat, st));
     HIP_TRY(B.alloc(&d_dup, 4));
     HIP_TRY(B.alloc(&occ, cells / 32 + 1));
     float *m[3] = {nullptr, nullptr, nullptr};
     for (int k = 0; k < 3; ++k) HIP_TRY(B.alloc(&m[k], cells));
-    if (n_flat > 0) {
-        HIP_TRY(hipMemcpyAsync(d_row, row, (size_t)n_flat * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_col, col, (size_t)n_flat * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_mz, mz, (size_t)n_flat * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_in, intensity, (size_t)n_flat * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_co, correlation, (size_t)n_flat * 4, hipMemcpyHostToDevice, st));
-    }
-    tl::Timer t{g->e0, g->e1, st};
+    sess::EventPair &t = g->ev;
     g->scatter_ms = 0.0;
-    TL_TRY(t.begin());
+    ADH_TRY(t.begin(st));
     HIP_TRY(hipMemsetAsync(d_dup, 0, 4, st));
     HIP_TRY(hipMemsetAsync(occ, 0, (cells / 32 + 1) * 4, st));
     for (int k = 0; k < 3; ++k) HIP_TRY(hipMemsetAsync(m[k], 0, std::max<size_t>(cells, 4) * 4, st));
@@ -581,15 +500,12 @@ int adh_tl_scatter(adh_tl_t *g, int64_t n_rows, int64_t n_flat, const int64_t *r
                            n_flat, g->C, m[0], m[1], m[2], occ, d_dup);
         HIP_TRY(hipGetLastError());
     }
-    TL_TRY(t.end(g->scatter_ms));
+    ADH_TRY(t.end(st, g->scatter_ms));
     HIP_TRY(hipMemcpyAsync(duplicate, d_dup, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     g->h->d2h_bytes += 4;
     if (*duplicate) return ADH_OK;  // nothing is staged
-    for (int k = 0; k < 3; ++k) {
-        B.keep(m[k]);
-        g->staged[k] = m[k];
-    }
+    for (int k = 0; k < 3; ++k) g->staged[k].adopt(B, m[k], cells);
     g->staged_rows = n_rows;
     return ADH_OK;
 }
@@ -620,19 +536,18 @@ int adh_tl_update(adh_tl_t *g, int32_t keep_top, int64_t n_new, const void *hash
     hipStream_t st = g->h->stream;
     HIP_TRY(hipStreamSynchronize(st));
     const int32_t C = g->C;
-    tl::Bufs B;
+    sess::DevBufs B;
 
     // the run's matrices
     const float *run[ADH_TL_MAX_MATRICES] = {nullptr, nullptr, nullptr, nullptr};
     if (matrices) {
         for (int m = 0; m < g->M; ++m) {
             float *d = nullptr;
-            HIP_TRY(B.alloc(&d, (size_t)n_new_rows * C));
-            if (n_new_rows > 0) HIP_TRY(hipMemcpyAsync(d, matrices[m], (size_t)n_new_rows * C * 4, hipMemcpyHostToDevice, st));
+            HIP_TRY(B.upload(&d, matrices[m], (size_t)n_new_rows * C, st));
             run[m] = d;
         }
     } else {
-        for (int m = 0; m < g->M; ++m) run[m] = g->staged[m];
+        for (int m = 0; m < g->M; ++m) run[m] = g->staged[m].p;
     }
 
     // consensus, then the new run
@@ -664,21 +579,16 @@ int adh_tl_update(adh_tl_t *g, int32_t keep_top, int64_t n_new, const void *hash
     }
     if (n_new > 0) {
         const size_t pb = proba_is_f64 ? 8 : 4;
-        HIP_TRY(B.alloc(&raw_hash, (size_t)n_new));
-        HIP_TRY(B.alloc(&raw_idx, (size_t)n_new));
-        HIP_TRY(B.alloc(&raw_start, (size_t)n_new));
-        HIP_TRY(B.alloc(&raw_stop, (size_t)n_new));
-        HIP_TRY(B.alloc(&raw_proba, (size_t)n_new * pb));
-        HIP_TRY(hipMemcpyAsync(raw_hash, hash, (size_t)n_new * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(raw_idx, precursor_idx, (size_t)n_new * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(raw_start, frag_start, (size_t)n_new * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(raw_stop, frag_stop, (size_t)n_new * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(raw_proba, proba, (size_t)n_new * pb, hipMemcpyHostToDevice, st));
+        HIP_TRY(B.upload(&raw_hash, (const uint64_t *)hash, (size_t)n_new, st));
+        HIP_TRY(B.upload(&raw_idx, precursor_idx, (size_t)n_new, st));
+        HIP_TRY(B.upload(&raw_start, frag_start, (size_t)n_new, st));
+        HIP_TRY(B.upload(&raw_stop, frag_stop, (size_t)n_new, st));
+        HIP_TRY(B.upload(&raw_proba, proba, (size_t)n_new * pb, st));
     }
 
-    tl::Timer t{g->e0, g->e1, st};
+    sess::EventPair &t = g->ev;
     g->topk_ms = g->gather_ms = 0.0;
-    TL_TRY(t.begin());
+    ADH_TRY(t.begin(st));
     if (n_new > 0) {
         hipLaunchKernelGGL(tl::key_kernel, dim3(tl::grid_for(n_new)), dim3(tl::kBlock), 0, st, raw_hash, hash_is_signed ? 1 : 0,
                            (const void *)raw_proba, proba_is_f64, raw_idx, raw_start, raw_stop, n_new, R0, hk + n0, pk + n0,
@@ -686,37 +596,27 @@ int adh_tl_update(adh_tl_t *g, int32_t keep_top, int64_t n_new, const void *hash
         HIP_TRY(hipGetLastError());
     }
     // least significant key first: precursor_idx, proba, mod_seq_hash
-    hipLaunchKernelGGL(tl::iota_kernel, dim3(tl::grid_for(n)), dim3(tl::kBlock), 0, st, perm_a, n);
+    hipLaunchKernelGGL(sess::iota_kernel, dim3(tl::grid_for(n)), dim3(tl::kBlock), 0, st, perm_a, n);
     HIP_TRY(hipGetLastError());
-    TL_TRY(tl::sort_pairs(B, ik, k_out, perm_a, perm_b, n, st));
+    ADH_TRY(sess::sort_pairs(B, ik, k_out, perm_a, perm_b, n, 64, st));
     hipLaunchKernelGGL(tl::take_kernel, dim3(tl::grid_for(n)), dim3(tl::kBlock), 0, st, pk, perm_b, n, k_in);
     HIP_TRY(hipGetLastError());
-    TL_TRY(tl::sort_pairs(B, k_in, k_out, perm_b, perm_a, n, st));
+    ADH_TRY(sess::sort_pairs(B, k_in, k_out, perm_b, perm_a, n, 64, st));
     hipLaunchKernelGGL(tl::take_kernel, dim3(tl::grid_for(n)), dim3(tl::kBlock), 0, st, hk, perm_a, n, k_in);
     HIP_TRY(hipGetLastError());
-    TL_TRY(tl::sort_pairs(B, k_in, k_out, perm_a, perm_b, n, st));
+    ADH_TRY(sess::sort_pairs(B, k_in, k_out, perm_a, perm_b, n, 64, st));
     // heads, rank inside the peptide, keep mask, the kept rows
     hipLaunchKernelGGL(tl::head_kernel, dim3(tl::grid_for(n)), dim3(tl::kBlock), 0, st, k_out, n, head);
     HIP_TRY(hipGetLastError());
-    {
-        size_t need = 0;
-        HIP_TRY(hipcub::DeviceScan::InclusiveScan(nullptr, need, head, seg_start, hipcub::Max(), (int)n, st));
-        unsigned char *tmp = nullptr;
-        HIP_TRY(B.alloc(&tmp, need));
-        HIP_TRY(hipcub::DeviceScan::InclusiveScan(tmp, need, head, seg_start, hipcub::Max(), (int)n, st));
-    }
+    ADH_TRY(sess::cub_call(B, [&](void *tmp, size_t &bytes) {
+        return hipcub::DeviceScan::InclusiveScan(tmp, bytes, head, seg_start, hipcub::Max(), (int)n, st);
+    }));
     hipLaunchKernelGGL(tl::keep_kernel, dim3(tl::grid_for(n)), dim3(tl::kBlock), 0, st, seg_start, n, (uint32_t)keep_top, flag);
     HIP_TRY(hipGetLastError());
-    {
-        size_t need = 0;
-        HIP_TRY(hipcub::DeviceSelect::Flagged(nullptr, need, perm_b, flag, kept, n_sel, (int)n, st));
-        unsigned char *tmp = nullptr;
-        HIP_TRY(B.alloc(&tmp, need));
-        HIP_TRY(hipcub::DeviceSelect::Flagged(tmp, need, perm_b, flag, kept, n_sel, (int)n, st));
-    }
+    ADH_TRY(sess::select_flagged(B, perm_b, flag, kept, n_sel, n, st));
     uint32_t K32 = 0;
     HIP_TRY(hipMemcpyAsync(&K32, n_sel, 4, hipMemcpyDeviceToHost, st));
-    TL_TRY(t.end(g->topk_ms));
+    ADH_TRY(t.end(st, g->topk_ms));
     const int64_t K = K32;
     if (K < 1 || K > n) return fail(ADH_ERR_HIP, "adh_tl_update: inconsistent number of kept rows");
 
@@ -735,26 +635,20 @@ int adh_tl_update(adh_tl_t *g, int32_t keep_top, int64_t n_new, const void *hash
     HIP_TRY(B.alloc(&o_ik, (size_t)K));
     HIP_TRY(B.alloc(&o_start, (size_t)K));
     HIP_TRY(B.alloc(&o_stop, (size_t)K));
-    TL_TRY(t.begin());
+    ADH_TRY(t.begin(st));
     hipLaunchKernelGGL(tl::kept_start_kernel, dim3(tl::grid_for(K)), dim3(tl::kBlock), 0, st, kept, start, K, ks_in, pos_in);
     HIP_TRY(hipGetLastError());
-    TL_TRY(tl::sort_pairs(B, ks_in, ks, pos_in, ord, K, st));
+    ADH_TRY(sess::sort_pairs(B, ks_in, ks, pos_in, ord, K, 32, st));
     hipLaunchKernelGGL(tl::block_len_kernel, dim3(tl::grid_for(K)), dim3(tl::kBlock), 0, st, kept, ord, start, stop, K, len);
     HIP_TRY(hipGetLastError());
-    {
-        size_t need = 0;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, len, new_start, (int)K, st));
-        unsigned char *tmp = nullptr;
-        HIP_TRY(B.alloc(&tmp, need));
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, need, len, new_start, (int)K, st));
-    }
+    ADH_TRY(sess::exclusive_sum(B, len, new_start, K, st));
     int64_t last[2] = {0, 0};
     HIP_TRY(hipMemcpyAsync(&last[0], new_start + (K - 1), 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(&last[1], len + (K - 1), 8, hipMemcpyDeviceToHost, st));
     hipLaunchKernelGGL(tl::renumber_kernel, dim3(tl::grid_for(K)), dim3(tl::kBlock), 0, st, kept, ord, new_start, len, hk, pk, ik, K,
                        o_hk, o_pk, o_ik, o_start, o_stop);
     HIP_TRY(hipGetLastError());
-    TL_TRY(t.end(g->gather_ms));
+    ADH_TRY(t.end(st, g->gather_ms));
     const int64_t Rn = last[0] + last[1];
     if (Rn < 0 || Rn >= (int64_t)0x7FFFFFF0ll)
         return fail(ADH_ERR_UNSUPPORTED, "adh_tl_update: the kept fragment rows number 2^31 or more");
@@ -764,28 +658,23 @@ int adh_tl_update(adh_tl_t *g, int32_t keep_top, int64_t n_new, const void *hash
     HIP_TRY(B.alloc(&src_row, (size_t)Rn));
     for (int m = 0; m < g->M; ++m) HIP_TRY(B.alloc(&out[m], (size_t)Rn * C));
     if (Rn > 0) {
-        TL_TRY(t.begin());
+        ADH_TRY(t.begin(st));
         hipLaunchKernelGGL(tl::row_map_kernel, dim3(tl::grid_for(Rn)), dim3(tl::kBlock), 0, st, new_start, ks, K, Rn, src_row);
         HIP_TRY(hipGetLastError());
         for (int m = 0; m < g->M; ++m) {
-            hipLaunchKernelGGL(tl::row_gather_kernel, dim3(tl::grid_for(Rn * C)), dim3(tl::kBlock), 0, st, (const float *)g->mat[m],
+            hipLaunchKernelGGL(tl::row_gather_kernel, dim3(tl::grid_for(Rn * C)), dim3(tl::kBlock), 0, st, (const float *)g->mat[m].p,
                                run[m], src_row, R0, Rn * C, C, out[m]);
             HIP_TRY(hipGetLastError());
         }
-        TL_TRY(t.end(g->gather_ms));
+        ADH_TRY(t.end(st, g->gather_ms));
     }
     HIP_TRY(hipStreamSynchronize(st));
 
     // the new consensus replaces the old one and the run
-    for (int m = 0; m < g->M; ++m) {
-        tl::drop(g->mat[m]);
-        B.keep(out[m]);
-        g->mat[m] = out[m];
-    }
+    for (int m = 0; m < g->M; ++m) g->mat[m].adopt(B, out[m], (size_t)Rn * C);
     tl::release_staged(g);
-    tl::drop(g->hk), tl::drop(g->pk), tl::drop(g->ik), tl::drop(g->start), tl::drop(g->stop), tl::drop(g->kept);
-    B.keep(o_hk), B.keep(o_pk), B.keep(o_ik), B.keep(o_start), B.keep(o_stop), B.keep(kept);
-    g->hk = o_hk, g->pk = o_pk, g->ik = o_ik, g->start = o_start, g->stop = o_stop, g->kept = kept;
+    g->hk.adopt(B, o_hk, (size_t)K), g->pk.adopt(B, o_pk, (size_t)K), g->ik.adopt(B, o_ik, (size_t)K);
+    g->start.adopt(B, o_start, (size_t)K), g->stop.adopt(B, o_stop, (size_t)K), g->kept.adopt(B, kept, (size_t)n);
     g->n_prec = K, g->n_rows = Rn, g->n_kept = K;
     if (g->hash_signed < 0) g->hash_signed = hash_is_signed ? 1 : 0;
     *n_kept = K;
@@ -851,58 +740,42 @@ int adh_tl_qc(adh_handle_t *h, int64_t n_prec, const int64_t *frag_start, const 
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = h->stream;
     const size_t cells = (size_t)n_rows * (size_t)n_columns;
-    tl::Bufs B;
+    sess::DevBufs B;
     float *d_in = nullptr, *d_co = nullptr;
     int64_t *d_start = nullptr, *d_stop = nullptr;
     uint8_t *d_use = nullptr;
     uint32_t *list = nullptr, *d_large = nullptr;
-    HIP_TRY(B.alloc(&d_in, cells));
-    HIP_TRY(B.alloc(&d_co, cells));
-    HIP_TRY(B.alloc(&d_start, (size_t)n_prec));
-    HIP_TRY(B.alloc(&d_stop, (size_t)n_prec));
+    HIP_TRY(B.upload(&d_in, (const float *)intensity, cells, st));
+    HIP_TRY(B.upload(&d_co, correlation, cells, st));
+    HIP_TRY(B.upload(&d_start, frag_start, (size_t)n_prec, st));
+    HIP_TRY(B.upload(&d_stop, frag_stop, (size_t)n_prec, st));
     HIP_TRY(B.alloc(&d_use, (size_t)n_prec));
     HIP_TRY(B.alloc(&list, (size_t)n_prec));
     HIP_TRY(B.alloc(&d_large, 4));
-    if (cells) {
-        HIP_TRY(hipMemcpyAsync(d_in, intensity, cells * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_co, correlation, cells * 4, hipMemcpyHostToDevice, st));
-    }
-    HIP_TRY(hipMemcpyAsync(d_start, frag_start, (size_t)n_prec * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_stop, frag_stop, (size_t)n_prec * 8, hipMemcpyHostToDevice, st));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    tl::Timer t{e0, e1, st};
-    auto done = [&]() {
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    };
-    int rc = [&]() -> int {
-        TL_TRY(t.begin());
-        HIP_TRY(hipMemsetAsync(d_large, 0, 4, st));
-        const unsigned grid = (unsigned)std::min<int64_t>(n_prec, 1 << 16);
-        hipLaunchKernelGGL(tl::qc_wave_kernel, dim3(grid), dim3(tl::kWave), 0, st, d_in, (const float *)d_co,
-                           (const int64_t *)d_start, (const int64_t *)d_stop, n_prec, n_columns, cutoff, ratio, empty_passes, d_use,
-                           list, d_large);
+    sess::EventPair t;
+    ADH_TRY(t.begin(st));
+    HIP_TRY(hipMemsetAsync(d_large, 0, 4, st));
+    const unsigned grid = (unsigned)std::min<int64_t>(n_prec, 1 << 16);
+    hipLaunchKernelGGL(tl::qc_wave_kernel, dim3(grid), dim3(tl::kWave), 0, st, d_in, (const float *)d_co,
+                       (const int64_t *)d_start, (const int64_t *)d_stop, n_prec, n_columns, cutoff, ratio, empty_passes, d_use,
+                       list, d_large);
+    HIP_TRY(hipGetLastError());
+    uint32_t large = 0;
+    HIP_TRY(hipMemcpyAsync(&large, d_large, 4, hipMemcpyDeviceToHost, st));
+    ADH_TRY(t.end(st, *kernel_ms));
+    if ((int64_t)large > n_prec) return fail(ADH_ERR_HIP, "adh_tl_qc: inconsistent number of large blocks");
+    *n_large = large;
+    if (large > 0) {
+        ADH_TRY(t.begin(st));
+        hipLaunchKernelGGL(tl::qc_large_kernel, dim3(large), dim3(tl::kBlock), 0, st, d_in, (const float *)d_co,
+                           (const int64_t *)d_start, (const int64_t *)d_stop, n_columns, cutoff, ratio, d_use,
+                           (const uint32_t *)list);
         HIP_TRY(hipGetLastError());
-        uint32_t large = 0;
-        HIP_TRY(hipMemcpyAsync(&large, d_large, 4, hipMemcpyDeviceToHost, st));
-        TL_TRY(t.end(*kernel_ms));
-        if ((int64_t)large > n_prec) return fail(ADH_ERR_HIP, "adh_tl_qc: inconsistent number of large blocks");
-        *n_large = large;
-        if (large > 0) {
-            TL_TRY(t.begin());
-            hipLaunchKernelGGL(tl::qc_large_kernel, dim3(large), dim3(tl::kBlock), 0, st, d_in, (const float *)d_co,
-                               (const int64_t *)d_start, (const int64_t *)d_stop, n_columns, cutoff, ratio, d_use,
-                               (const uint32_t *)list);
-            HIP_TRY(hipGetLastError());
-            TL_TRY(t.end(*kernel_ms));
-        }
-        if (cells) HIP_TRY(hipMemcpyAsync(intensity, d_in, cells * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(use_for_ms2, d_use, (size_t)n_prec, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        return ADH_OK;
-    }();
-    done();
-    if (rc != ADH_OK) return rc;
+        ADH_TRY(t.end(st, *kernel_ms));
+    }
+    if (cells) HIP_TRY(hipMemcpyAsync(intensity, d_in, cells * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(use_for_ms2, d_use, (size_t)n_prec, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     h->d2h_bytes += cells * 4 + (uint64_t)n_prec;
     return ADH_OK;
 }
@@ -915,61 +788,51 @@ int adh_tl_rt_norm(adh_handle_t *h, int64_t n, int32_t delta_max, const void *rt
     if (n < 1) return fail(ADH_ERR_INVALID_ARGUMENT, "adh_tl_rt_norm: no rows");
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = h->stream;
-    tl::Bufs B;
+    sess::DevBufs B;
     const bool of = observed_is_f64 != 0, cf = calibrated_is_f64 != 0, lf = library_is_f64 != 0;
     const size_t ob = of ? 8 : 4, cb = cf ? 8 : 4, lb = lf ? 8 : 4;
     const size_t outb = delta_max ? ((of || cf || lf) ? 8 : 4) : ob;
     unsigned char *d_obs = nullptr, *d_cal = nullptr, *d_lib = nullptr, *d_out = nullptr;
-    HIP_TRY(B.alloc(&d_obs, (size_t)n * ob));
+    HIP_TRY(B.upload(&d_obs, rt_observed, (size_t)n * ob, st));
     HIP_TRY(B.alloc(&d_out, (size_t)n * outb));
-    HIP_TRY(hipMemcpyAsync(d_obs, rt_observed, (size_t)n * ob, hipMemcpyHostToDevice, st));
     if (delta_max) {
-        HIP_TRY(B.alloc(&d_cal, (size_t)n * cb));
-        HIP_TRY(B.alloc(&d_lib, (size_t)n * lb));
-        HIP_TRY(hipMemcpyAsync(d_cal, rt_calibrated, (size_t)n * cb, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_lib, rt_library, (size_t)n * lb, hipMemcpyHostToDevice, st));
+        HIP_TRY(B.upload(&d_cal, rt_calibrated, (size_t)n * cb, st));
+        HIP_TRY(B.upload(&d_lib, rt_library, (size_t)n * lb, st));
     }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    tl::Timer t{e0, e1, st};
+    sess::EventPair t;
     *kernel_ms = 0.0;
-    int rc = [&]() -> int {
-        TL_TRY(t.begin());
-        if (!delta_max) {
-            if (of) {
-                double *mx = nullptr;
-                TL_TRY((tl::reduce_max<double, true>(B, (const double *)d_obs, n, &mx, st)));
-                hipLaunchKernelGGL((tl::rt_max_norm_kernel<double>), dim3(tl::grid_for(n)), dim3(tl::kBlock), 0, st,
-                                   (const double *)d_obs, (const double *)mx, n, (double *)d_out);
-            } else {
-                float *mx = nullptr;
-                TL_TRY((tl::reduce_max<float, true>(B, (const float *)d_obs, n, &mx, st)));
-                hipLaunchKernelGGL((tl::rt_max_norm_kernel<float>), dim3(tl::grid_for(n)), dim3(tl::kBlock), 0, st,
-                                   (const float *)d_obs, (const float *)mx, n, (float *)d_out);
-            }
-            HIP_TRY(hipGetLastError());
+    ADH_TRY(t.begin(st));
+    if (!delta_max) {
+        if (of) {
+            double *mx = nullptr;
+            ADH_TRY((tl::reduce_max<double, true>(B, (const double *)d_obs, n, &mx, st)));
+            hipLaunchKernelGGL((tl::rt_max_norm_kernel<double>), dim3(tl::grid_for(n)), dim3(tl::kBlock), 0, st,
+                               (const double *)d_obs, (const double *)mx, n, (double *)d_out);
         } else {
-            const int which = (of ? 4 : 0) | (cf ? 2 : 0) | (lf ? 1 : 0);
-            int r = ADH_OK;
-            switch (which) {
-                case 0: r = tl::rt_delta_max<float, float, float>(B, d_obs, d_cal, d_lib, n, d_out, st); break;
-                case 1: r = tl::rt_delta_max<float, float, double>(B, d_obs, d_cal, d_lib, n, d_out, st); break;
-                case 2: r = tl::rt_delta_max<float, double, float>(B, d_obs, d_cal, d_lib, n, d_out, st); break;
-                case 3: r = tl::rt_delta_max<float, double, double>(B, d_obs, d_cal, d_lib, n, d_out, st); break;
-                case 4: r = tl::rt_delta_max<double, float, float>(B, d_obs, d_cal, d_lib, n, d_out, st); break;
-                case 5: r = tl::rt_delta_max<double, float, double>(B, d_obs, d_cal, d_lib, n, d_out, st); break;
-                case 6: r = tl::rt_delta_max<double, double, float>(B, d_obs, d_cal, d_lib, n, d_out, st); break;
-                default: r = tl::rt_delta_max<double, double, double>(B, d_obs, d_cal, d_lib, n, d_out, st); break;
-            }
-            if (r != ADH_OK) return r;
+            float *mx = nullptr;
+            ADH_TRY((tl::reduce_max<float, true>(B, (const float *)d_obs, n, &mx, st)));
+            hipLaunchKernelGGL((tl::rt_max_norm_kernel<float>), dim3(tl::grid_for(n)), dim3(tl::kBlock), 0, st,
+                               (const float *)d_obs, (const float *)mx, n, (float *)d_out);
         }
-        TL_TRY(t.end(*kernel_ms));
-        HIP_TRY(hipMemcpyAsync(rt_norm, d_out, (size_t)n * outb, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        return ADH_OK;
-    }();
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (rc != ADH_OK) return rc;
+        HIP_TRY(hipGetLastError());
+    } else {
+        const int which = (of ? 4 : 0) | (cf ? 2 : 0) | (lf ? 1 : 0);
+        int r = ADH_OK;
+        switch (which) {
+            case 0: r = tl::rt_delta_max<float, float, float>(B, d_obs, d_cal, d_lib, n, d_out, st); break;
+            case 1: r = tl::rt_delta_max<float, float, double>(B, d_obs, d_cal, d_lib, n, d_out, st); break;
+            case 2: r = tl::rt_delta_max<float, double, float>(B, d_obs, d_cal, d_lib, n, d_out, st); break;
+            case 3: r = tl::rt_delta_max<float, double, double>(B, d_obs, d_cal, d_lib, n, d_out, st); break;
+            case 4: r = tl::rt_delta_max<double, float, float>(B, d_obs, d_cal, d_lib, n, d_out, st); break;
+            case 5: r = tl::rt_delta_max<double, float, double>(B, d_obs, d_cal, d_lib, n, d_out, st); break;
+            case 6: r = tl::rt_delta_max<double, double, float>(B, d_obs, d_cal, d_lib, n, d_out, st); break;
+            default: r = tl::rt_delta_max<double, double, double>(B, d_obs, d_cal, d_lib, n, d_out, st); break;
+        }
+        ADH_TRY(r);
+    }
+    ADH_TRY(t.end(st, *kernel_ms));
+    HIP_TRY(hipMemcpyAsync(rt_norm, d_out, (size_t)n * outb, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     h->d2h_bytes += (uint64_t)n * outb;
     return ADH_OK;
 }

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import weakref
 
 import numpy as np
 
@@ -531,9 +532,17 @@ class Context:
         self.comm_rank = 0
         # one more per scoring call that replaces the device tables (a resident result checks it is still current)
         self.tables_serial = 0
+        self._sessions = weakref.WeakSet()  # the live _DeviceSession objects of this handle
+
+    def _close_sessions(self):
+        """Destroy every live session while the handle still exists: a session's native destroy reads the handle's
+        device and stream, and one that outlived the handle could only leak its device memory."""
+        for s in list(self._sessions):
+            s.close()
 
     def close(self):
         if self._h:
+            self._close_sessions()
             lib.adh_destroy(self._h)
             self._h = C.c_void_p()
             self.pinned.close()
@@ -681,7 +690,7 @@ class Context:
         p = lambda a, t: a.ctypes.data_as(C.POINTER(t)) if a is not None else None  # noqa: E731
         _check(
             lib.adh_fdr_resident(
-                self._h, mlp._m, p(ga, C.c_int64), p(gb, C.c_int64), p(tb, C.c_int64), p(cyc, C.c_double),
+                self._h, mlp._s, p(ga, C.c_int64), p(gb, C.c_int64), p(tb, C.c_int64), p(cyc, C.c_double),
                 C.c_int32(cyc.shape[1] if cyc is not None else 0), C.c_int32(cyc.shape[2] if cyc is not None else 0),
                 C.c_double(float(rt_tol_seconds)), C.c_double(float(mass_tol_ppm)), C.c_double(float(fdr_heuristic)),
                 C.byref(n_out), p(rows, C.c_int64), p(proba, C.c_float), p(qval, C.c_double)),
@@ -1298,25 +1307,27 @@ class Context:
         return DeviceMbr(self)
 
 
-class DeviceMlp:
-    """An ``adh_mlp_t``: the classifier network with its parameters, optimiser moments and the
-    staged feature matrix in HBM."""
+class _DeviceSession:
+    """A native object that lives on a ``Context``'s handle (``adh_mlp_t``, ``adh_quant_t``, ...).  The subclass
+    fills ``self._s`` with its create call.  The context closes its live sessions before it destroys the handle, so
+    the native destroy always finds the handle it reads, and a session closed that way makes no native call later.
+    (The subclass makes its own two calls by name, ``lib.adh_x_destroy(s)`` and ``lib.adh_x_time_ms(...)``: the ABI
+    tests read the wrapper classes for the exports they call.)"""
 
-    def __init__(self, ctx: Context, input_dim: int, layers, output_dim: int = 2):
+    def __init__(self, ctx: Context):
         self._ctx = ctx  # keeps the handle alive
-        self.arch = _abi.pack_mlp_arch(input_dim, layers, output_dim)
-        self.input_dim, self.layers, self.output_dim = int(input_dim), [int(x) for x in layers], int(output_dim)
-        n = C.c_int64(0)
-        _check(lib.adh_mlp_param_count(C.byref(self.arch), C.byref(n)), "adh_mlp_param_count")
-        self.n_params = int(n.value)
-        self._m = C.c_void_p()
-        _check(lib.adh_mlp_create(ctx._h, C.byref(self.arch), C.byref(self._m)), "adh_mlp_create")
-        self.n_rows = 0
+        self._s = C.c_void_p()
+        ctx._sessions.add(self)
+
+    def _native_destroy(self, s):
+        """The subclass calls its destroy export on ``s``."""
+        raise NotImplementedError
 
     def close(self):
-        if self._m:
-            lib.adh_mlp_destroy(self._m)
-            self._m = C.c_void_p()
+        s = getattr(self, "_s", None)  # (absent when __init__ failed early)
+        if s:
+            self._s = C.c_void_p()
+            self._native_destroy(s)
 
     def __del__(self):
         try:
@@ -1328,13 +1339,39 @@ class DeviceMlp:
     def _p(a, t):
         return a.ctypes.data_as(C.POINTER(t))
 
+    @staticmethod
+    def _times(n: int, call) -> tuple:
+        """The ``n`` HIP-event times (ms) that ``call`` fills: it gets ``n`` doubles by reference and returns the
+        status of a ``*_time_ms`` export."""
+        t = [C.c_double(0.0) for _ in range(n)]
+        _check(call(*(C.byref(x) for x in t)), "time_ms")
+        return tuple(float(x.value) for x in t)
+
+
+class DeviceMlp(_DeviceSession):
+    """An ``adh_mlp_t``: the classifier network with its parameters, optimiser moments and the
+    staged feature matrix in HBM."""
+
+    def __init__(self, ctx: Context, input_dim: int, layers, output_dim: int = 2):
+        super().__init__(ctx)
+        self.arch = _abi.pack_mlp_arch(input_dim, layers, output_dim)
+        self.input_dim, self.layers, self.output_dim = int(input_dim), [int(x) for x in layers], int(output_dim)
+        n = C.c_int64(0)
+        _check(lib.adh_mlp_param_count(C.byref(self.arch), C.byref(n)), "adh_mlp_param_count")
+        self.n_params = int(n.value)
+        _check(lib.adh_mlp_create(ctx._h, C.byref(self.arch), C.byref(self._s)), "adh_mlp_create")
+        self.n_rows = 0
+
+    def _native_destroy(self, s):
+        lib.adh_mlp_destroy(s)
+
     def set_state(self, params, running_mean, running_var, num_batches_tracked: int = 0):
         pa = _abi.as_c(params, np.float32)
         rm = _abi.as_c(running_mean, np.float32)
         rv = _abi.as_c(running_var, np.float32)
         if pa.shape != (self.n_params,) or rm.shape != (self.input_dim,) or rv.shape != (self.input_dim,):
             raise ValueError("state arrays do not match the architecture")
-        _check(lib.adh_mlp_set_state(self._m, self._p(pa, C.c_float), self._p(rm, C.c_float), self._p(rv, C.c_float),
+        _check(lib.adh_mlp_set_state(self._s, self._p(pa, C.c_float), self._p(rm, C.c_float), self._p(rv, C.c_float),
                                      C.c_int64(int(num_batches_tracked))), "adh_mlp_set_state")
 
     def get_state(self):
@@ -1342,7 +1379,7 @@ class DeviceMlp:
         rm = np.zeros(self.input_dim, dtype=np.float32)
         rv = np.zeros(self.input_dim, dtype=np.float32)
         nbt = C.c_int64(0)
-        _check(lib.adh_mlp_get_state(self._m, self._p(pa, C.c_float), self._p(rm, C.c_float), self._p(rv, C.c_float),
+        _check(lib.adh_mlp_get_state(self._s, self._p(pa, C.c_float), self._p(rm, C.c_float), self._p(rv, C.c_float),
                                      C.byref(nbt)), "adh_mlp_get_state")
         return pa, rm, rv, int(nbt.value)
 
@@ -1355,7 +1392,7 @@ class DeviceMlp:
             ya = _abi.as_c(y, np.float32)
             if ya.shape != (xa.shape[0],):
                 raise ValueError("y must hold one target per row")
-        _check(lib.adh_mlp_stage_rows(self._m, self._p(xa, C.c_float), C.c_int64(xa.shape[0]), C.c_int32(xa.shape[1]),
+        _check(lib.adh_mlp_stage_rows(self._s, self._p(xa, C.c_float), C.c_int64(xa.shape[0]), C.c_int32(xa.shape[1]),
                                       self._p(ya, C.c_float) if ya is not None else None), "adh_mlp_stage_rows")
         self.n_rows = xa.shape[0]
 
@@ -1374,7 +1411,7 @@ class DeviceMlp:
         arr = (C.POINTER(C.c_float) * max(len(extras), 1))(*[self._p(e, C.c_float) for e in extras])
         nt, nd = C.c_int64(0), C.c_int64(0)
         if part is None:
-            _check(lib.adh_mlp_stage_rows_device(self._m, self._p(sc, C.c_int32), C.c_int32(sc.shape[0]), arr,
+            _check(lib.adh_mlp_stage_rows_device(self._s, self._p(sc, C.c_int32), C.c_int32(sc.shape[0]), arr,
                                                  C.c_int32(len(extras)), self._p(de, C.c_uint8), C.c_int64(de.shape[0]),
                                                  C.byref(nt), C.byref(nd)), "adh_mlp_stage_rows_device")
         else:
@@ -1386,7 +1423,7 @@ class DeviceMlp:
                                       f"{de.shape[0]}: one per row of the device tables is needed")
             target, decoy_channel, by_channel = part
             _check(lib.adh_mlp_stage_rows_device_part(
-                self._m, self._p(sc, C.c_int32), C.c_int32(sc.shape[0]), arr, C.c_int32(len(extras)),
+                self._s, self._p(sc, C.c_int32), C.c_int32(sc.shape[0]), arr, C.c_int32(len(extras)),
                 self._p(de, C.c_uint8), C.c_int64(de.shape[0]), self._p(ch, C.c_int64), C.c_int64(int(target)),
                 C.c_int64(int(decoy_channel)), C.c_int32(int(bool(by_channel))), C.byref(nt), C.byref(nd)),
                 "adh_mlp_stage_rows_device_part")
@@ -1395,11 +1432,11 @@ class DeviceMlp:
 
     def staged_rows(self) -> np.ndarray:
         rows = np.zeros(self.n_rows, dtype=np.int64)
-        _check(lib.adh_mlp_staged_rows(self._m, self._p(rows, C.c_int64), C.c_int64(rows.shape[0])), "adh_mlp_staged_rows")
+        _check(lib.adh_mlp_staged_rows(self._s, self._p(rows, C.c_int64), C.c_int64(rows.shape[0])), "adh_mlp_staged_rows")
         return rows
 
     def predict_resident(self) -> None:
-        _check(lib.adh_mlp_predict_resident(self._m), "adh_mlp_predict_resident")
+        _check(lib.adh_mlp_predict_resident(self._s), "adh_mlp_predict_resident")
 
     def fit(self, train_rows, batch_start, batch_size: int, learning_rate: float, weight_decay: float,
             dropout: float, seed: int = 0, first_step: int = 0, betas=(0.9, 0.999), eps: float = 1e-8) -> np.ndarray:
@@ -1413,7 +1450,7 @@ class DeviceMlp:
         f.beta1, f.beta2, f.eps = float(betas[0]), float(betas[1]), float(eps)
         f.seed, f.first_step = int(seed) & (2**64 - 1), int(first_step)
         loss = np.zeros(bs.shape[0], dtype=np.float32)
-        _check(lib.adh_mlp_fit(self._m, C.byref(f), self._p(loss, C.c_float)), "adh_mlp_fit")
+        _check(lib.adh_mlp_fit(self._s, C.byref(f), self._p(loss, C.c_float)), "adh_mlp_fit")
         return loss
 
     def predict(self, rows=None) -> np.ndarray:
@@ -1423,41 +1460,30 @@ class DeviceMlp:
             ra = _abi.as_c(rows, np.int64)
             n, rp = ra.shape[0], self._p(ra, C.c_int64)
         out = np.zeros((n, self.output_dim), dtype=np.float32)
-        _check(lib.adh_mlp_predict(self._m, rp, C.c_int64(n), self._p(out, C.c_float)), "adh_mlp_predict")
+        _check(lib.adh_mlp_predict(self._s, rp, C.c_int64(n), self._p(out, C.c_float)), "adh_mlp_predict")
         return out
 
     def time_ms(self):
-        a, b = C.c_double(0.0), C.c_double(0.0)
-        _check(lib.adh_mlp_time_ms(self._m, C.byref(a), C.byref(b)), "adh_mlp_time_ms")
-        return float(a.value), float(b.value)
+        return self._times(2, lambda *t: lib.adh_mlp_time_ms(self._s, *t))
 
 
-class DeviceQuant:
+class DeviceQuant(_DeviceSession):
     """An ``adh_quant_t``: the kept frag rows of every run, then their union of ion keys and one column-major
     ``n_keys x n_runs`` float32 matrix per quantity column, in HBM (include/alphadia_hip.h: adh_quant_*)."""
 
     def __init__(self, ctx: Context, n_columns: int, psm_precursor_idx):
-        self._ctx = ctx  # keeps the handle alive
+        super().__init__(ctx)
         self.n_columns = int(n_columns)
         psm = np.ascontiguousarray(psm_precursor_idx, dtype=np.uint32)
-        self._q = C.c_void_p()
         _check(lib.adh_quant_create(ctx._h, self.n_columns, psm.ctypes.data_as(C.POINTER(C.c_uint32)), psm.shape[0],
-                                    C.byref(self._q)), "adh_quant_create")
+                                    C.byref(self._s)), "adh_quant_create")
         self.n_runs = 0
         self.n_rows = 0
         self.n_keys = 0
         self.duplicate = False
 
-    def close(self):
-        if self._q:
-            lib.adh_quant_destroy(self._q)
-            self._q = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _native_destroy(self, s):
+        lib.adh_quant_destroy(s)
 
     @staticmethod
     def _cols(arrays):
@@ -1474,7 +1500,7 @@ class DeviceQuant:
             raise ValueError("add_run: every column must hold one value per row, one array per quantity column")
         kept = C.c_int64(0)
         u8 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint8))  # noqa: E731
-        _check(lib.adh_quant_add_run(self._q, n, p.ctypes.data_as(C.POINTER(C.c_uint32)), *[u8(x) for x in b],
+        _check(lib.adh_quant_add_run(self._s, n, p.ctypes.data_as(C.POINTER(C.c_uint32)), *[u8(x) for x in b],
                                      self._cols(cols), C.byref(kept)), "adh_quant_add_run")
         self.n_runs += 1
         self.n_rows += int(kept.value)
@@ -1483,21 +1509,21 @@ class DeviceQuant:
     def build(self) -> tuple[int, bool]:
         """The union of keys and the matrices; returns ``(n_keys, duplicate)``."""
         nk, dup = C.c_int64(0), C.c_int32(0)
-        _check(lib.adh_quant_build(self._q, C.byref(nk), C.byref(dup)), "adh_quant_build")
+        _check(lib.adh_quant_build(self._s, C.byref(nk), C.byref(dup)), "adh_quant_build")
         self.n_keys, self.duplicate = int(nk.value), bool(dup.value)
         return self.n_keys, self.duplicate
 
     def keys(self):
         ion = np.empty(self.n_keys, dtype=np.int64)
         pidx = np.empty(self.n_keys, dtype=np.uint32)
-        _check(lib.adh_quant_keys(self._q, ion.ctypes.data_as(C.POINTER(C.c_int64)),
+        _check(lib.adh_quant_keys(self._s, ion.ctypes.data_as(C.POINTER(C.c_int64)),
                                   pidx.ctypes.data_as(C.POINTER(C.c_uint32))), "adh_quant_keys")
         return ion, pidx
 
     def matrix(self, column: int) -> np.ndarray:
         """Quantity column ``column`` as a C-ordered ``(n_runs, n_keys)`` float32 array (one row per run)."""
         out = np.empty((self.n_runs, self.n_keys), dtype=np.float32)
-        _check(lib.adh_quant_matrix(self._q, int(column), out.ctypes.data_as(C.POINTER(C.c_float))), "adh_quant_matrix")
+        _check(lib.adh_quant_matrix(self._s, int(column), out.ctypes.data_as(C.POINTER(C.c_float))), "adh_quant_matrix")
         return out
 
     def rows(self):
@@ -1505,7 +1531,7 @@ class DeviceQuant:
         n = self.n_rows
         ion, pidx, run = np.empty(n, np.int64), np.empty(n, np.uint32), np.empty(n, np.uint32)
         cols = [np.empty(n, np.float32) for _ in range(self.n_columns)]
-        _check(lib.adh_quant_rows(self._q, ion.ctypes.data_as(C.POINTER(C.c_int64)),
+        _check(lib.adh_quant_rows(self._s, ion.ctypes.data_as(C.POINTER(C.c_int64)),
                                   pidx.ctypes.data_as(C.POINTER(C.c_uint32)), run.ctypes.data_as(C.POINTER(C.c_uint32)),
                                   self._cols(cols)), "adh_quant_rows")
         return ion, pidx, run, cols
@@ -1516,7 +1542,7 @@ class DeviceQuant:
         n = cols[0].shape[0] if cols else 0
         if any(c.shape != (n,) for c in cols):
             raise ValueError("set_matrix: run columns differ in length")
-        _check(lib.adh_quant_set_matrix(self._q, n, len(cols), self._cols(cols)), "adh_quant_set_matrix")
+        _check(lib.adh_quant_set_matrix(self._s, n, len(cols), self._cols(cols)), "adh_quant_set_matrix")
         self.n_runs, self.n_keys = len(cols), n
 
     def filter(self, column: int, group, n_groups: int, top_n: float, threshold: float):
@@ -1527,7 +1553,7 @@ class DeviceQuant:
         total = np.empty(self.n_keys, np.float32)
         rank = np.empty(self.n_keys, np.float64)
         mask = np.empty(self.n_keys, np.uint8)
-        _check(lib.adh_quant_filter(self._q, int(column), g.ctypes.data_as(C.POINTER(C.c_int32)), int(n_groups),
+        _check(lib.adh_quant_filter(self._s, int(column), g.ctypes.data_as(C.POINTER(C.c_int32)), int(n_groups),
                                     float(top_n), float(threshold), total.ctypes.data_as(C.POINTER(C.c_float)),
                                     rank.ctypes.data_as(C.POINTER(C.c_double)), mask.ctypes.data_as(C.POINTER(C.c_uint8))),
                "adh_quant_filter")
@@ -1535,34 +1561,23 @@ class DeviceQuant:
 
     def time_ms(self):
         """HIP-event times (ms) of the build and of the last filter."""
-        a, b = C.c_double(0.0), C.c_double(0.0)
-        _check(lib.adh_quant_time_ms(self._q, C.byref(a), C.byref(b)), "adh_quant_time_ms")
-        return float(a.value), float(b.value)
+        return self._times(2, lambda *t: lib.adh_quant_time_ms(self._s, *t))
 
 
-class DeviceProteinGroups:
+class DeviceProteinGroups(_DeviceSession):
     """An ``adh_pg_t``: the set cover of protein inference over (pattern, id) edges and its heuristic filter
     (include/alphadia_hip.h: adh_pg_*)."""
 
     def __init__(self, ctx: Context):
-        self._ctx = ctx  # keeps the handle alive
-        self._g = C.c_void_p()
-        _check(lib.adh_pg_create(ctx._h, C.byref(self._g)), "adh_pg_create")
+        super().__init__(ctx)
+        _check(lib.adh_pg_create(ctx._h, C.byref(self._s)), "adh_pg_create")
         self.n_patterns = self.n_ids = self.n_edges = 0
 
-    def close(self):
-        if self._g:
-            lib.adh_pg_destroy(self._g)
-            self._g = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _native_destroy(self, s):
+        lib.adh_pg_destroy(s)
 
     @staticmethod
-    def _p(a):
+    def _i32(a):
         return a.ctypes.data_as(C.POINTER(C.c_int32))
 
     def solve(self, edge_pattern, edge_id, weight, n_ids: int):
@@ -1572,8 +1587,8 @@ class DeviceProteinGroups:
             raise ValueError("solve: one pattern and one id per edge, one weight per pattern")
         master = np.empty(w.shape[0], np.int32)
         emptied = np.empty(max(int(n_ids), 0), np.int32)
-        _check(lib.adh_pg_solve(self._g, w.shape[0], int(n_ids), ep.shape[0], self._p(ep), self._p(ei), self._p(w),
-                                self._p(master), self._p(emptied)), "adh_pg_solve")
+        _check(lib.adh_pg_solve(self._s, w.shape[0], int(n_ids), ep.shape[0], self._i32(ep), self._i32(ei), self._i32(w),
+                                self._i32(master), self._i32(emptied)), "adh_pg_solve")
         self.n_patterns, self.n_ids, self.n_edges = w.shape[0], int(n_ids), ep.shape[0]
         return master, emptied
 
@@ -1585,24 +1600,22 @@ class DeviceProteinGroups:
         off = np.empty(self.n_patterns + 1, np.int32)
         ids = np.empty(max(self.n_edges, 1), np.int32)
         kept = C.c_int64(0)
-        _check(lib.adh_pg_filter(self._g, int(n_strings), self._p(s), self._p(r), self._p(off), self._p(ids),
+        _check(lib.adh_pg_filter(self._s, int(n_strings), self._i32(s), self._i32(r), self._i32(off), self._i32(ids),
                                  C.byref(kept)), "adh_pg_filter")
         return off, ids[: int(kept.value)]
 
     def stats(self) -> tuple[int, int, int]:
         """(components, components of more than 64 ids, labelling rounds) of the last solve."""
         a, b, c = C.c_int32(0), C.c_int32(0), C.c_int32(0)
-        _check(lib.adh_pg_stats(self._g, C.byref(a), C.byref(b), C.byref(c)), "adh_pg_stats")
+        _check(lib.adh_pg_stats(self._s, C.byref(a), C.byref(b), C.byref(c)), "adh_pg_stats")
         return int(a.value), int(b.value), int(c.value)
 
     def time_ms(self) -> tuple[float, float, float]:
         """HIP-event times (ms) of the component labelling, the cover and the filter."""
-        a, b, c = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
-        _check(lib.adh_pg_time_ms(self._g, C.byref(a), C.byref(b), C.byref(c)), "adh_pg_time_ms")
-        return float(a.value), float(b.value), float(c.value)
+        return self._times(3, lambda *t: lib.adh_pg_time_ms(self._s, *t))
 
 
-class DeviceProteinFdr:
+class DeviceProteinFdr(_DeviceSession):
     """An ``adh_pfdr_t``: the (pg, decoy) group features of a precursor table, sklearn's MLPClassifier trained one
     epoch per launch, and the gather of a per-group value to the rows (include/alphadia_hip.h: adh_pfdr_*)."""
 
@@ -1610,25 +1623,12 @@ class DeviceProteinFdr:
     N_PARAMS = 901
 
     def __init__(self, ctx: Context):
-        self._ctx = ctx  # keeps the handle alive
-        self._g = C.c_void_p()
-        _check(lib.adh_pfdr_create(ctx._h, C.byref(self._g)), "adh_pfdr_create")
+        super().__init__(ctx)
+        _check(lib.adh_pfdr_create(ctx._h, C.byref(self._s)), "adh_pfdr_create")
         self.n_rows = self.n_groups = self.n_train = 0
 
-    def close(self):
-        if self._g:
-            lib.adh_pfdr_destroy(self._g)
-            self._g = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @staticmethod
-    def _p(a, t):
-        return a.ctypes.data_as(C.POINTER(t))
+    def _native_destroy(self, s):
+        lib.adh_pfdr_destroy(s)
 
     def features(self, pg, decoy, precursor_idx, sequence, run, proba, with_row_group: bool = False):
         """``(group_pg, group_decoy, features [groups, 7])`` of ``adh_pfdr_features``, the groups ascending by
@@ -1642,7 +1642,7 @@ class DeviceProteinFdr:
         if pg.ndim != 1 or any(a.shape != (n,) for a in (seq, rn, de, pi, pr)):
             raise ValueError("features: one value of every column per row")
         groups = C.c_int64(0)
-        _check(lib.adh_pfdr_features(self._g, n, self._p(pg, C.c_int32), self._p(de, C.c_uint8), self._p(pi, C.c_int64),
+        _check(lib.adh_pfdr_features(self._s, n, self._p(pg, C.c_int32), self._p(de, C.c_uint8), self._p(pi, C.c_int64),
                                      self._p(seq, C.c_int32), self._p(rn, C.c_int32), C.c_void_p(pr.ctypes.data),
                                      int(pr.dtype == np.float64), C.byref(groups)), "adh_pfdr_features")
         self.n_rows, self.n_groups = n, int(groups.value)
@@ -1650,7 +1650,7 @@ class DeviceProteinFdr:
         gde = np.empty(self.n_groups, np.uint8)
         x = np.empty((self.n_groups, self.N_FEATURES), np.float64)
         row_group = np.empty(n, np.int32) if with_row_group else None
-        _check(lib.adh_pfdr_read_features(self._g, self._p(gpg, C.c_int32), self._p(gde, C.c_uint8), self._p(x, C.c_double),
+        _check(lib.adh_pfdr_read_features(self._s, self._p(gpg, C.c_int32), self._p(gde, C.c_uint8), self._p(x, C.c_double),
                                           self._p(row_group, C.c_int32) if with_row_group else None),
                "adh_pfdr_read_features")
         return (gpg, gde, x, row_group) if with_row_group else (gpg, gde, x)
@@ -1662,7 +1662,7 @@ class DeviceProteinFdr:
         p = _abi.as_c(params, np.float64)
         if x.ndim != 2 or x.shape[1] != self.N_FEATURES or y.shape != (x.shape[0],) or p.shape != (self.N_PARAMS,):
             raise ValueError("fit_begin: x [rows, 7], one label per row, 901 parameters")
-        _check(lib.adh_pfdr_fit_begin(self._g, x.shape[0], self._p(x, C.c_double), self._p(y, C.c_uint8),
+        _check(lib.adh_pfdr_fit_begin(self._s, x.shape[0], self._p(x, C.c_double), self._p(y, C.c_uint8),
                                       self._p(p, C.c_double)), "adh_pfdr_fit_begin")
         self.n_train = x.shape[0]
 
@@ -1673,7 +1673,7 @@ class DeviceProteinFdr:
         if o.shape != (self.n_train,) or lr.ndim != 1:
             raise ValueError("epoch: one position per training row, one step size per batch")
         loss = C.c_double(0.0)
-        _check(lib.adh_pfdr_epoch(self._g, self._p(o, C.c_int32), lr.shape[0], self._p(lr, C.c_double), C.byref(loss)),
+        _check(lib.adh_pfdr_epoch(self._s, self._p(o, C.c_int32), lr.shape[0], self._p(lr, C.c_double), C.byref(loss)),
                "adh_pfdr_epoch")
         return float(loss.value)
 
@@ -1682,7 +1682,7 @@ class DeviceProteinFdr:
         if x.ndim != 2 or x.shape[1] != self.N_FEATURES:
             raise ValueError("predict: x [rows, 7]")
         out = np.empty(x.shape[0], np.float64)
-        _check(lib.adh_pfdr_predict(self._g, x.shape[0], self._p(x, C.c_double), self._p(out, C.c_double)),
+        _check(lib.adh_pfdr_predict(self._s, x.shape[0], self._p(x, C.c_double), self._p(out, C.c_double)),
                "adh_pfdr_predict")
         return out
 
@@ -1692,42 +1692,26 @@ class DeviceProteinFdr:
         if v.shape != (self.n_groups,):
             raise ValueError("gather: one value per group of the last features call")
         out = np.empty(self.n_rows, np.float64)
-        _check(lib.adh_pfdr_gather(self._g, v.shape[0], self._p(v, C.c_double), self._p(out, C.c_double)), "adh_pfdr_gather")
+        _check(lib.adh_pfdr_gather(self._s, v.shape[0], self._p(v, C.c_double), self._p(out, C.c_double)), "adh_pfdr_gather")
         return out
 
     def time_ms(self) -> tuple[float, float, float, float]:
         """HIP-event times (ms) of the features, all epochs of the last fit, the last predict and the last gather."""
-        t = [C.c_double(0.0) for _ in range(4)]
-        _check(lib.adh_pfdr_time_ms(self._g, *(C.byref(x) for x in t)), "adh_pfdr_time_ms")
-        return tuple(float(x.value) for x in t)
+        return self._times(4, lambda *t: lib.adh_pfdr_time_ms(self._s, *t))
 
 
-class DeviceTransferLibrary:
+class DeviceTransferLibrary(_DeviceSession):
     """An ``adh_tl_t``: the consensus of the transfer-learning library in HBM - sort keys, dense-row blocks and dense
     matrices - updated run by run (include/alphadia_hip.h: adh_tl_*)."""
 
     def __init__(self, ctx: Context, n_columns: int, n_matrices: int):
-        self._ctx = ctx  # keeps the handle alive
-        self._g = C.c_void_p()
+        super().__init__(ctx)
         self.n_columns, self.n_matrices = int(n_columns), int(n_matrices)
-        _check(lib.adh_tl_create(ctx._h, self.n_columns, self.n_matrices, C.byref(self._g)), "adh_tl_create")
+        _check(lib.adh_tl_create(ctx._h, self.n_columns, self.n_matrices, C.byref(self._s)), "adh_tl_create")
         self.n_kept = self.n_rows = 0
 
-    def close(self):
-        if self._g:
-            if self._ctx._h:  # (at interpreter exit the context may be finalised first: its handle and stream are gone)
-                lib.adh_tl_destroy(self._g)
-            self._g = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @staticmethod
-    def _p(a, t):
-        return a.ctypes.data_as(C.POINTER(t))
+    def _native_destroy(self, s):
+        lib.adh_tl_destroy(s)
 
     def scatter(self, n_rows: int, row, col, mz, intensity, correlation) -> bool:
         """``adh_tl_scatter``: stages a run from its flat rows; True when a cell was written twice (nothing staged)."""
@@ -1736,7 +1720,7 @@ class DeviceTransferLibrary:
         if r.ndim != 1 or any(a.shape != r.shape for a in (c, *v)):
             raise ValueError("scatter: one value of every column per flat row")
         dup = C.c_int32(0)
-        _check(lib.adh_tl_scatter(self._g, int(n_rows), r.shape[0], self._p(r, C.c_int64), self._p(c, C.c_int32),
+        _check(lib.adh_tl_scatter(self._s, int(n_rows), r.shape[0], self._p(r, C.c_int64), self._p(c, C.c_int32),
                                   *(self._p(a, C.c_float) for a in v), C.byref(dup)), "adh_tl_scatter")
         return bool(dup.value)
 
@@ -1760,56 +1744,40 @@ class DeviceTransferLibrary:
                 raise ValueError("update: every dense matrix is [n_new_rows, n_columns]")
             mats = (C.POINTER(C.c_float) * len(held))(*(self._p(m, C.c_float) for m in held))
         kept_n, rows_n = C.c_int64(0), C.c_int64(0)
-        _check(lib.adh_tl_update(self._g, int(keep_top), n, C.c_void_p(h.ctypes.data), int(h.dtype == np.int64),
+        _check(lib.adh_tl_update(self._s, int(keep_top), n, C.c_void_p(h.ctypes.data), int(h.dtype == np.int64),
                                  C.c_void_p(pr.ctypes.data), int(pr.dtype == np.float64), self._p(pi, C.c_int64),
                                  self._p(fs, C.c_int64), self._p(fe, C.c_int64), int(n_new_rows), mats, C.byref(kept_n),
                                  C.byref(rows_n)), "adh_tl_update")
         self.n_kept, self.n_rows = int(kept_n.value), int(rows_n.value)
         kept, start, stop = (np.empty(self.n_kept, np.int64) for _ in range(3))
-        _check(lib.adh_tl_read_kept(self._g, self._p(kept, C.c_int64), self._p(start, C.c_int64), self._p(stop, C.c_int64)),
+        _check(lib.adh_tl_read_kept(self._s, self._p(kept, C.c_int64), self._p(start, C.c_int64), self._p(stop, C.c_int64)),
                "adh_tl_read_kept")
         return kept, start, stop
 
     def matrix(self, m: int) -> np.ndarray:
         """``adh_tl_read_matrix``: dense matrix ``m`` of the consensus."""
         out = np.empty((self.n_rows, self.n_columns), np.float32)
-        _check(lib.adh_tl_read_matrix(self._g, int(m), self._p(out, C.c_float)), "adh_tl_read_matrix")
+        _check(lib.adh_tl_read_matrix(self._s, int(m), self._p(out, C.c_float)), "adh_tl_read_matrix")
         return out
 
     def time_ms(self) -> tuple[float, float, float]:
         """HIP-event times (ms) of the last update's top-k and row gather and of the last scatter."""
-        t = [C.c_double(0.0) for _ in range(3)]
-        _check(lib.adh_tl_time_ms(self._g, *(C.byref(x) for x in t)), "adh_tl_time_ms")
-        return tuple(float(x.value) for x in t)
+        return self._times(3, lambda *t: lib.adh_tl_time_ms(self._s, *t))
 
 
-class DeviceMbr:
+class DeviceMbr(_DeviceSession):
     """An ``adh_mbr_t``: the PSM aggregates, the elution groups that passed and the filtered library of the
     match-between-runs library in HBM (include/alphadia_hip.h: adh_mbr_*)."""
 
     def __init__(self, ctx: Context):
-        self._ctx = ctx  # keeps the handle alive
-        self._g = C.c_void_p()
-        _check(lib.adh_mbr_create(ctx._h, C.byref(self._g)), "adh_mbr_create")
+        super().__init__(ctx)
+        _check(lib.adh_mbr_create(ctx._h, C.byref(self._s)), "adh_mbr_create")
         self.n_passed = self.n_by_group = self.n_by_hash = self.n_groups = 0
         self.n_kept = self.n_rows = self.n_columns = 0
         self._rt_dtype = self._hash_dtype = self._group_dtype = None
 
-    def close(self):
-        if self._g:
-            if self._ctx._h:  # (at interpreter exit the context may be finalised first: its handle and stream are gone)
-                lib.adh_mbr_destroy(self._g)
-            self._g = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @staticmethod
-    def _p(a, t):
-        return a.ctypes.data_as(C.POINTER(t))
+    def _native_destroy(self, s):
+        lib.adh_mbr_destroy(s)
 
     @staticmethod
     def _group(a, what):
@@ -1843,7 +1811,7 @@ class DeviceMbr:
         if q.ndim != 1 or any(a.shape != (n,) for a in (d, eg, h, rt, pg)):
             raise ValueError("aggregate: one value of every column per PSM row")
         out = [C.c_int64(0) for _ in range(4)]
-        _check(lib.adh_mbr_aggregate(self._g, n, self._p(q, C.c_double), self._p(d, C.c_uint8), C.c_void_p(eg.ctypes.data),
+        _check(lib.adh_mbr_aggregate(self._s, n, self._p(q, C.c_double), self._p(d, C.c_uint8), C.c_void_p(eg.ctypes.data),
                                      int(eg.dtype == np.uint32), C.c_void_p(h.ctypes.data), int(h.dtype == np.int64),
                                      C.c_void_p(rt.ctypes.data), int(rt.dtype == np.float64), self._p(pg, C.c_uint8),
                                      float(fdr), int(bool(keep_decoys)), *(C.byref(x) for x in out)), "adh_mbr_aggregate")
@@ -1859,14 +1827,14 @@ class DeviceMbr:
         n = (self.n_by_group, self.n_by_hash)[which]
         keys = np.empty(n, np.int64 if which == 0 else self._hash_dtype)
         med, first = np.empty(n, self._rt_dtype), np.empty(n, np.int64)
-        _check(lib.adh_mbr_read_table(self._g, int(which), C.c_void_p(keys.ctypes.data), C.c_void_p(med.ctypes.data),
+        _check(lib.adh_mbr_read_table(self._s, int(which), C.c_void_p(keys.ctypes.data), C.c_void_p(med.ctypes.data),
                                       self._p(first, C.c_int64)), "adh_mbr_read_table")
         return (keys.astype(self._group_dtype) if which == 0 else keys), med, first
 
     def groups(self) -> np.ndarray:
         """The elution groups that passed, ascending."""
         keys = np.empty(self.n_groups, np.int64)
-        _check(lib.adh_mbr_read_table(self._g, 2, C.c_void_p(keys.ctypes.data), None, None), "adh_mbr_read_table")
+        _check(lib.adh_mbr_read_table(self._s, 2, C.c_void_p(keys.ctypes.data), None, None), "adh_mbr_read_table")
         return keys.astype(self._group_dtype)
 
     def filter(self, elution_group_idx, frag_start, frag_stop, n_rows: int, matrices=None, source_rows: bool = False):
@@ -1888,14 +1856,14 @@ class DeviceMbr:
             n_cols = held[0].shape[1]
             mats = (C.POINTER(C.c_float) * len(held))(*(self._p(m, C.c_float) for m in held))
         kept_n, rows_n = C.c_int64(0), C.c_int64(0)
-        _check(lib.adh_mbr_filter(self._g, n, C.c_void_p(eg.ctypes.data), int(eg.dtype == np.uint32), self._p(fs, C.c_int64),
+        _check(lib.adh_mbr_filter(self._s, n, C.c_void_p(eg.ctypes.data), int(eg.dtype == np.uint32), self._p(fs, C.c_int64),
                                   self._p(fe, C.c_int64), int(n_rows), int(n_cols), len(held), mats, C.byref(kept_n),
                                   C.byref(rows_n)), "adh_mbr_filter")
         self.n_kept, self.n_rows, self.n_columns = int(kept_n.value), int(rows_n.value), int(n_cols)
         kept, start, stop = (np.empty(self.n_kept, np.int64) for _ in range(3))
         src = np.empty(self.n_rows, np.int64) if source_rows else None
         if self.n_kept:
-            _check(lib.adh_mbr_read_filter(self._g, self._p(kept, C.c_int64), self._p(start, C.c_int64),
+            _check(lib.adh_mbr_read_filter(self._s, self._p(kept, C.c_int64), self._p(start, C.c_int64),
                                            self._p(stop, C.c_int64), self._p(src, C.c_int64) if source_rows else None),
                    "adh_mbr_read_filter")
         return kept, start, stop, src
@@ -1904,7 +1872,7 @@ class DeviceMbr:
         """``adh_mbr_read_matrix``: gathered dense matrix ``m`` of the last filter."""
         out = np.empty((self.n_rows, self.n_columns), np.float32)
         if self.n_kept:
-            _check(lib.adh_mbr_read_matrix(self._g, int(m), self._p(out, C.c_float)), "adh_mbr_read_matrix")
+            _check(lib.adh_mbr_read_matrix(self._s, int(m), self._p(out, C.c_float)), "adh_mbr_read_matrix")
         return out
 
     def assign(self, elution_group_idx, mod_seq_charge_hash):
@@ -1916,7 +1884,7 @@ class DeviceMbr:
         if eg.ndim != 1 or h.shape != (n,):
             raise ValueError("assign: one value of every column per precursor")
         rt, row, missing = np.empty(n, self._rt_dtype), np.empty(n, np.int64), C.c_int64(0)
-        _check(lib.adh_mbr_assign(self._g, n, C.c_void_p(eg.ctypes.data), int(eg.dtype == np.uint32), C.c_void_p(h.ctypes.data),
+        _check(lib.adh_mbr_assign(self._s, n, C.c_void_p(eg.ctypes.data), int(eg.dtype == np.uint32), C.c_void_p(h.ctypes.data),
                                   int(h.dtype == np.int64), C.c_void_p(rt.ctypes.data), self._p(row, C.c_int64),
                                   C.byref(missing)), "adh_mbr_assign")
         return rt, row, int(missing.value)
@@ -1926,7 +1894,7 @@ class DeviceMbr:
         columns in an order-preserving uint64 form."""
         t, k = _abi.as_c(target_keys, np.uint64), _abi.as_c(lookup_keys, np.uint64)
         out, dup = np.empty(t.shape[0], np.int64), C.c_int32(0)
-        _check(lib.adh_mbr_index(self._g, t.shape[0], self._p(t, C.c_uint64), k.shape[0], self._p(k, C.c_uint64),
+        _check(lib.adh_mbr_index(self._s, t.shape[0], self._p(t, C.c_uint64), k.shape[0], self._p(k, C.c_uint64),
                                  self._p(out, C.c_int64), C.byref(dup)), "adh_mbr_index")
         return out, bool(dup.value)
 
@@ -1934,7 +1902,7 @@ class DeviceMbr:
         """HIP-event times (ms) of the last aggregate, filter, gather and assign; bytes over PCIe since creation."""
         t = [C.c_double(0.0) for _ in range(4)]
         b = [C.c_uint64(0), C.c_uint64(0)]
-        _check(lib.adh_mbr_stats(self._g, *(C.byref(x) for x in t), *(C.byref(x) for x in b)), "adh_mbr_stats")
+        _check(lib.adh_mbr_stats(self._s, *(C.byref(x) for x in t), *(C.byref(x) for x in b)), "adh_mbr_stats")
         return dict(aggregate_ms=t[0].value, filter_ms=t[1].value, gather_ms=t[2].value, assign_ms=t[3].value,
                     h2d_bytes=int(b[0].value), d2h_bytes=int(b[1].value))
 
