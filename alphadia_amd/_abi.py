@@ -800,9 +800,12 @@ STAGE_LIB_PROTOTYPES = {
 N_PLAN_CLASSES = 37
 # launch groups of the generic class (small layouts, layouts up to the LDS of a CU, the spill path): adh_generic_launch_stats
 N_GENERIC_GROUPS = 3
+# ... and of the dynamic route of the ion-mobility feature kernel: adh_im_launch_stats
+N_IM_GROUPS = 3
 PLAN_PROTOTYPES = {
     "adh_plan_class_counts": [C.c_void_p, C.POINTER(C.c_int64), C.c_int32],
     "adh_generic_launch_stats": [C.c_void_p, C.POINTER(C.c_int64), C.c_int32],
+    "adh_im_launch_stats": [C.c_void_p, C.POINTER(C.c_int64), C.c_int32],
 }
 
 

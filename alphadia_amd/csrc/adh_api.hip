@@ -328,6 +328,13 @@ struct Plan {
     int64_t lds_generic[ADH_GENERIC_GROUPS] = {0};
     uint64_t generic_over = 0;
     bool spill_all = false;        // ADH_DEBUG_GENERIC_SPILL
+    // ion-mobility plans: the same per plan class (slots 0, 1, ADH_CLASS_IM_SMALL, generic) for the launches that take
+    // the dynamic route (adh_feature_im_layout.h); `im_over` != 0: a candidate beyond the spill bound (PlanMeta::im_over)
+    int64_t n_im[ADH_IM_CLASS_SLOTS][ADH_IM_GROUPS] = {{0}};
+    int64_t lds_im[ADH_IM_CLASS_SLOTS][ADH_IM_GROUPS] = {{0}};
+    uint64_t im_over = 0;
+    int64_t im_over_shape[4] = {0};  // K, O, S, F of that candidate
+    bool im_spill_all = false;     // ADH_DEBUG_IM_SPILL
     Caps caps_all;
 };
 
@@ -425,6 +432,8 @@ struct adh_handle {
     int64_t class_counts[ADH_N_CLASSES] = {0};  // candidates per kernel class of every launched plan (adh_plan_class_counts)
     // generic launch groups of every launched plan: candidates per group, largest dynamic LDS per group (adh_generic_launch_stats)
     int64_t generic_stats[2 * ADH_GENERIC_GROUPS] = {0};
+    // ... and the launch groups of the dynamic route of every launched ion-mobility plan (adh_im_launch_stats)
+    int64_t im_stats[2 * ADH_IM_GROUPS] = {0};
     // page-locked staging of upload_staged (H2D of a caller's pageable arrays): per lane two buffers, their events, a stream
     struct UpLane {
         void *buf[2] = {nullptr, nullptr};
@@ -620,8 +629,10 @@ int adh_create(adh_handle_t **handle, int device) {
     (void)hipFuncSetAttribute((const void *)adh_gather_kernel,
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     // (this kernel also has ADH_IM_STATIC_LDS bytes of static LDS)
-    (void)hipFuncSetAttribute((const void *)adh_feature_im_kernel<featim::Layout>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - ADH_IM_STATIC_LDS);
+    (void)hipFuncSetAttribute((const void *)adh_feature_im_own_kernel<false>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, ADH_IM_LDS_LIMIT);
+    (void)hipFuncSetAttribute((const void *)adh_feature_im_own_kernel<true>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, ADH_IM_LDS_LIMIT);
     (void)hipFuncSetAttribute((const void *)adh_feature_im_kernel<featim::LayoutCommon>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - ADH_IM_STATIC_LDS);
     (void)hipFuncSetAttribute((const void *)adh_feature_im_kernel<featim::LayoutSmall>,

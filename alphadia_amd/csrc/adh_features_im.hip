@@ -19,6 +19,7 @@
 // BLAS SGEMM in the reference): one v_mfma_f32_16x16x4_f32 tile per observation.
 #include "adh_device.h"
 #include "adh_feature_common.h"
+#include "adh_feature_im_layout.h"
 
 namespace featim {
 using feat::Assemble;
@@ -185,111 +186,7 @@ __device__ __forceinline__ void precursor_features_rows(float *ft, int I, int O,
     }
 }
 
-// LDS capacities of a launch: taken from the launch's Caps (DimsDyn) or fixed at compile time (DimsFix), which
-// turns every array address below into an instruction offset - with run-time capacities the ~60 array bases
-// are scalar registers, more than there are, and the kernel spends a sixth of its instructions moving
-// them between scalar registers and the lanes of spill registers
-struct DimsDyn {
-    int Kc, Oc, Sc, Fc, Ic, SFc;  // SFc: cells of one (scan, cycle) plane
-    __host__ __device__ DimsDyn(const Caps &c) : Kc(c.k), Oc(c.o), Sc(c.s), Fc(c.f), Ic(c.i), SFc(c.s * c.f) {}
-};
-template <int K, int O, int S, int F, int I, int SF>
-struct DimsFix {
-    static constexpr int Kc = K, Oc = O, Sc = S, Fc = F, Ic = I, SFc = SF;
-    __host__ __device__ DimsFix(const Caps &) {}
-    __host__ __device__ static bool holds(const Caps &c) { return holds_axes(c) && c.s * c.f <= SF; }
-    // (without the plane size: for a launch whose candidates were admitted one by one, plan class ADH_CLASS_IM_SMALL)
-    __host__ __device__ static bool holds_axes(const Caps &c) {
-        return c.k <= K && c.o <= O && c.s <= S && c.f <= F && c.i <= I;
-    }
-};
-template <class D>
-struct LayoutT : D {
-    __host__ __device__ LayoutT(const Caps &c) : D(c) {}
-    // doubles
-    // (the transfer function is dead after the template; the per-fragment results and the frame times,
-    // born later, take its place)
-    __host__ __device__ int d_qtf() const { return 0; }                      // [Ic][Oc][Sc], early
-    __host__ __device__ int qtf_size() const {
-        const int a = D::Ic * D::Oc * D::Sc, b = 4 * D::Kc + D::Fc;
-        return a > b ? a : b;
-    }
-    __host__ __device__ int d_pk() const { return d_qtf(); }                 // [4][Kc], late
-    __host__ __device__ int d_frt() const { return d_qtf() + 4 * D::Kc; }       // [Fc] frame rt (float64), late
-    __host__ __device__ int d_omz() const { return d_qtf() + qtf_size(); }
-    __host__ __device__ int d_ohe() const { return d_omz() + D::Kc * D::Oc; }
-    __host__ __device__ int d_omzu() const { return d_ohe() + D::Kc * D::Oc; }  // per selected fragment,
-    __host__ __device__ int d_oheu() const { return d_omzu() + D::Kc * D::Oc; } // before the presence mask
-    __host__ __device__ int d_accw() const { return d_oheu() + D::Kc * D::Oc; } // [2][Kc*Oc] weight sums
-    __host__ __device__ int d_po() const { return d_accw() + 2 * D::Kc * D::Oc; }   // [2][Oc]
-    __host__ __device__ int d_pi() const { return d_po() + 2 * D::Oc; }     // [2][Ic]
-    __host__ __device__ int n_double() const { return d_pi() + 2 * D::Ic; }
-    // floats
-    __host__ __device__ int smax() const { return D::Sc > D::Fc ? D::Sc : D::Fc; }
-    __host__ __device__ int f_wb() const { return 0; }                            // work [Kc*Oc*max(Sc,Fc)]
-    // Two regions are used twice.  R1 holds the template until its profiles are taken, then the masked
-    // frame / scan profiles; R2 holds the profiles before the presence mask, then the scan envelopes and
-    // the quantification profiles.  (LDS per block is what bounds the resident waves of this kernel, and
-    // the kernel's time follows them: 26 KB -> 40 KB per block costs 38 %.)
-    __host__ __device__ int f_work_end() const { return f_wb() + D::Kc * D::Oc * smax(); }
-    __host__ __device__ int r1_size() const {
-        const int a = D::Oc * D::SFc, b = D::Kc * D::Oc * (D::Fc + D::Sc);
-        return a > b ? a : b;
-    }
-    __host__ __device__ int f_r1() const { return f_work_end(); }
-    __host__ __device__ int f_r2() const { return f_r1() + r1_size(); }
-    __host__ __device__ int f_tpl() const { return f_r1(); }                      // [Oc*Sc*Fc]       R1, early
-    __host__ __device__ int f_ffp() const { return f_r1(); }                      // [Kc*Oc*Fc]       R1, late
-    __host__ __device__ int f_fspr() const { return f_r1() + D::Kc * D::Oc * D::Fc; }      // [Kc*Oc*Sc] raw   R1, late
-    __host__ __device__ int f_ffpu() const { return f_r2(); }                     // [Kc*Oc*Fc] before the mask  R2, early
-    __host__ __device__ int f_fspu() const { return f_r2() + D::Kc * D::Oc * D::Fc; }      // [Kc*Oc*Sc] before the mask  R2, early
-    __host__ __device__ int f_fspe() const { return f_r2(); }                     // [Kc*Oc*Sc] envelope  R2, late
-    __host__ __device__ int f_bp() const { return f_r2() + D::Kc * D::Oc * D::Sc; }        // [Kc*Fc]          R2, late
-    __host__ __device__ int f_tfp() const { return f_r2() + D::Kc * D::Oc * (D::Fc + D::Sc); }  // [Oc*Fc]
-    __host__ __device__ int f_tsp() const { return f_tfp() + 2 * D::Oc * D::Fc; }       // [2][Oc*Sc] (tfp: raw, env)
-    __host__ __device__ int f_qm() const { return f_tsp() + 2 * D::Oc * D::Sc; }        // [Oc*Sc] qtf mask
-    __host__ __device__ int f_pk() const { return f_qm() + D::Oc * D::Sc; }             // [8][Kc]
-    __host__ __device__ int f_pko() const { return f_pk() + 8 * D::Kc; }             // [4][Kc*Oc]
-    __host__ __device__ int f_po() const { return f_pko() + 4 * D::Kc * D::Oc; }        // [4][Oc]
-    __host__ __device__ int f_pi() const { return f_po() + 4 * D::Oc; }              // [3][Ic]
-    __host__ __device__ int f_pf() const { return f_pi() + 3 * D::Ic; }              // [2][Fc]
-    __host__ __device__ int f_feat() const { return f_pf() + 2 * D::Fc; }
-    __host__ __device__ int n_float() const { return f_feat() + ADH_NUM_FEATURES; }
-    // ints
-    __host__ __device__ int i_pk() const { return 0; }                   // [4][Kc]
-    __host__ __device__ int i_pko() const { return i_pk() + 4 * D::Kc; }    // [Kc*Oc]
-    __host__ __device__ int i_obs() const { return i_pko() + D::Kc * D::Oc; }  // [Oc]
-    __host__ __device__ int n_int() const { return i_obs() + D::Oc; }
-    __host__ __device__ int n_byte() const { return ((5 * D::Kc + 7) / 8) * 8; }
-    __host__ __device__ size_t bytes() const {
-        size_t b = (size_t)n_double() * 8;
-        b += ((size_t)n_float() * 4 + 7) / 8 * 8;
-        b += ((size_t)n_int() * 4 + 7) / 8 * 8;
-        b += n_byte();
-        return b;
-    }
-};
-using Layout = LayoutT<DimsDyn>;
-// the common shape: up to 12 fragments, one observation, 40 scans, 32 cycles, 1152 cells per plane, 3 isotopes
-// (13 704 + 2 560 static bytes: ten blocks per CU, as the specified 38 x 29 tiles get with run-time capacities)
-using DimsCommon = DimsFix<12, 1, 40, 32, 3, 1152>;
-using LayoutCommon = LayoutT<DimsCommon>;
-// the same shape with two observations (plan class 1; only the tile part of the split path uses it)
-using DimsCommon2 = DimsFix<12, 2, 40, 32, 3, 1152>;
-using LayoutCommon2 = LayoutT<DimsCommon2>;
-// small tiles (plan class ADH_CLASS_IM_SMALL): 10 248 + 2 560 bytes, twelve blocks per CU
-using DimsSmall = DimsFix<ADH_IM_SMALL_K, 1, ADH_IM_SMALL_S, ADH_IM_SMALL_F, 3, ADH_IM_SMALL_SF>;
-using LayoutSmall = LayoutT<DimsSmall>;
-
 }  // namespace featim
-
-#define ADH_IM_STAGE 128          // cells staged per round of the tile passes (two per lane)
-#define ADH_IM_STATIC_LDS (ADH_IM_STAGE * 20)  // static LDS of adh_feature_im_kernel (chunk lists / Gram matrices: 2 176 B)
-size_t adh_feature_im_lds_bytes(const Caps &c) {
-    return featim::DimsSmall::holds(c)    ? featim::LayoutSmall(c).bytes()
-           : featim::DimsCommon::holds(c) ? featim::LayoutCommon(c).bytes()
-                                          : featim::Layout(c).bytes();
-}
 
 // SPLIT (round 4, fixed layouts only): the kernel ends after the passes over the tiles and writes the candidate's
 // ImProfRec<LAY::Fc, LAY::Sc> to `prof` (record blockIdx.x); adh_feature_im_profiles_kernel does the rest, four
@@ -298,11 +195,29 @@ size_t adh_feature_im_lds_bytes(const Caps &c) {
 // DYNPOOL: the 2.5 KB of chunk lists behind the layout in the dynamic LDS block instead of a static array - for the
 // kernels that take the rare materialised tiles through this body in a few blocks of a grid whose other blocks should
 // not pay for it (adh_feature_im_fused4_kernel, adh_feature_im_tile4_kernel: LDS is their occupancy).
+// LAY::spilled (featim::LayoutSpill, the spill instantiation): the work region and the profile regions R1 and R2 are
+// in the candidate's spill block in `spill` (the scratch slab again, writable and not restrict: `scratch` stays the
+// read-only view of the gather's cells), which only this wavefront touches.  Lanes hand data over through them as they
+// do through LDS, so every hand-over point of the body is a workgroup barrier there (im_sync), as in the generic kernel's
+// spill instantiation: its release / acquire fences order the wavefront's global writes and reads.  What this rests on
+// (DESIGN 4.1): a workgroup-scope fence makes a store visible at the CU's L1, and all lanes of the one wavefront of a
+// block read through that same L1 in program order - an ASSUMPTION about how gfx950 implements workgroup scope for a
+// single-wavefront block, not a guarantee of the memory model; the bit-equality tests of the spill instantiation against
+// the LDS one are its evidence.
+// `scratch` is const __restrict__ and `spill` points into the SAME slab: correct only because a candidate's gather cells
+// (read through `scratch`) and its spill block (read and written through `spill`) are disjoint byte ranges.  Never read a
+// spilled plane through `scratch`.
+template <bool GLOBAL>
+__device__ __forceinline__ void im_sync() {
+    if constexpr (GLOBAL) __syncthreads();
+    else adh_wave_sync();
+}
+
 template <class LAY, bool SPLIT, bool DYNPOOL = false>
 __device__ __forceinline__ void adh_feature_im_body(
     const int ci, const DevTims &run, const CandRecIM *__restrict__ plan, const float *__restrict__ iso_table,
     int32_t n_iso_cols, const adh_scoring_config_t &cfg, const unsigned char *__restrict__ scratch, const DevOut &out,
-    const Caps &caps, unsigned char *__restrict__ prof) {
+    const Caps &caps, unsigned char *__restrict__ prof, unsigned char *spill = nullptr) {
     using namespace featim;
     extern __shared__ __align__(16) unsigned char smem[];
     // ordered list of the non-zero cells of one 64-cell chunk (see the tile passes below)
@@ -346,19 +261,25 @@ __device__ __forceinline__ void adh_feature_im_body(
     if (lane == 0 && out.stat_matched_peaks) out.stat_matched_peaks[row] = header[1];
     if (caps.stop_phase == 10) return;  // developer ablation switches (ADH_DEBUG_IM)
 
-    float *const work_b = Fl + lay.f_wb();
-    float *const ffp_u = Fl + lay.f_ffpu();
-    float *const fsp_u = Fl + lay.f_fspu();
-    float *const ffp = Fl + lay.f_ffp();
-    float *const fsp_raw = Fl + lay.f_fspr();
-    float *const fsp = Fl + lay.f_fspe();
+    // the regions that grow with K * O * (S + F): in LDS, or in the spill block behind the candidate's gather cells
+    // (work region, R1, R2 in the order and with the sizes of the LDS layout: featim::spill_floats)
+    float *const sp_work = LAY::spilled ? reinterpret_cast<float *>(spill + r.scratch_off + adh_im_scratch_bytes(r.k_cap, r.n_obs, S, F, I, r.n_ms1))
+                                        : nullptr;
+    float *const sp_r1 = LAY::spilled ? sp_work + lay.work_size() : nullptr;
+    float *const sp_r2 = LAY::spilled ? sp_r1 + lay.prof_size() : nullptr;
+    float *const work_b = LAY::spilled ? sp_work : Fl + lay.f_wb();
+    float *const ffp_u = LAY::spilled ? sp_r2 : Fl + lay.f_ffpu();
+    float *const fsp_u = LAY::spilled ? sp_r2 + Kc * Oc * Fc : Fl + lay.f_fspu();
+    float *const ffp = LAY::spilled ? sp_r1 : Fl + lay.f_ffp();
+    float *const fsp_raw = LAY::spilled ? sp_r1 + Kc * Oc * Fc : Fl + lay.f_fspr();
+    float *const fsp = LAY::spilled ? sp_r2 : Fl + lay.f_fspe();
     float *const tpl = Fl + lay.f_tpl();
     float *const tfp_raw = Fl + lay.f_tfp();
     float *const tfp = tfp_raw + Oc * Fc;
     float *const tsp_raw = Fl + lay.f_tsp();
     float *const tsp = tsp_raw + Oc * Sc;
     float *const qmask = Fl + lay.f_qm();
-    float *const bp = Fl + lay.f_bp();
+    float *const bp = LAY::spilled ? sp_r2 + Kc * Oc * Sc : Fl + lay.f_bp();
     float *const oi = Fl + lay.f_po();
     float *const tsum = oi + Oc;
     float *const medpk = tsum + Oc;
@@ -413,7 +334,7 @@ __device__ __forceinline__ void adh_feature_im_body(
         if (lane < O) obs[lane] = r.obs[lane];
         if (lane < ADH_NUM_FEATURES) featv[lane] = 0.0f;
     }
-    adh_wave_sync();
+    im_sync<LAY::spilled>();
 
     // ---- quadrupole transfer function per (isotope, observation, scan) (quadrupole.py:261-301)
     for (int c = lane; c < I * O * S; c += ADH_WAVE) {
@@ -424,13 +345,13 @@ __device__ __forceinline__ void adh_feature_im_body(
         const QuadParams qp = adh_quad_params(cfg);
         qtf[c] = logistic(x, cy[0] + qp.delta_lo, qp.sigma_lo) - logistic(x, cy[1] + qp.delta_hi, qp.sigma_hi);
     }
-    adh_wave_sync();
+    im_sync<LAY::spilled>();
     for (int c = lane; c < O * S; c += ADH_WAVE) {
         double sum = 0;
         for (int i = 0; i < I; ++i) sum += qtf[i * O * S + c];
         qmask[c] = (float)(sum / (double)I);  // candidate.py:287-289
     }
-    adh_wave_sync();
+    im_sync<LAY::spilled>();
     // (the qtf mask of candidate.py:290 is applied while the fragment tile is streamed)
     double *const hp = D + lay.d_pi();
     double *const omzp = hp + Ic;
@@ -476,7 +397,7 @@ __device__ __forceinline__ void adh_feature_im_body(
                 c_y[e] = en.y;
                 c_w[e] = exp(-0.1 * sqrt(ds * ds + df * df));
             }
-            adh_wave_sync();
+            im_sync<LAY::spilled>();
             if (base + cnt < n_pe) {  // never cut the isotopes of a cell in two: stop at the last cell start
                 const int e = cnt - ADH_WAVE + lane;
                 const unsigned long long st = __ballot((c_cell[e] >> 4) != (c_cell[e - 1] >> 4));
@@ -537,7 +458,7 @@ __device__ __forceinline__ void adh_feature_im_body(
                     }
                 }
             }
-            adh_wave_sync();
+            im_sync<LAY::spilled>();
             base += cnt;
         }
         const int il = lane < I ? lane : 0;
@@ -560,7 +481,7 @@ __device__ __forceinline__ void adh_feature_im_body(
         tpl[c] = (float)acc;
     }
     }
-    adh_wave_sync();
+    im_sync<LAY::spilled>();
 
     if (caps.stop_phase == 1) return;  // developer ablation switches (ADH_DEBUG_IM)
     // ---- observation importance (quadrupole.py:327-335), fragment presence (candidate.py:319-329)
@@ -580,7 +501,7 @@ __device__ __forceinline__ void adh_feature_im_body(
     if (sparse_tpl) {
         for (int c = lane; c < S; c += ADH_WAVE) tsp_raw[c] = 0.0f;
         for (int c = lane; c < F; c += ADH_WAVE) tfp_raw[c] = 0.0f;
-        adh_wave_sync();
+        im_sync<LAY::spilled>();
         if (lane == 0) {
             // the list is in (scan, cycle) order: a scan's cells are consecutive and in cycle order (its sum =
             // np.sum over the cycle axis), a cycle's cells come in scan order (the sum over the scan axis), and
@@ -608,14 +529,14 @@ __device__ __forceinline__ void adh_feature_im_body(
             esc[0] = (isum > 0) ? ssum / isum : 0.0;
             efc[0] = (isum > 0) ? fsum / isum : 0.0;
         }
-        adh_wave_sync();
+        im_sync<LAY::spilled>();
         if (lane < O) tsum[lane] = osum<SR>(tsp_raw + lane * S, 1, S);
-        adh_wave_sync();
+        im_sync<LAY::spilled>();
     } else {
     for (int c = lane; c < O * S; c += ADH_WAVE) tsp_raw[c] = osum<FR>(tpl + c * F, 1, F);
-    adh_wave_sync();
+    im_sync<LAY::spilled>();
     if (lane < O) tsum[lane] = osum<SR>(tsp_raw + lane * S, 1, S);
-    adh_wave_sync();
+    im_sync<LAY::spilled>();
     // ---- template centre of mass and the weight tables (fragment_features.py:20-68,
     // features_utils.py:9-25): they only depend on the precursor tile and are needed by the pass
     // over the fragment tile
@@ -636,13 +557,13 @@ __device__ __forceinline__ void adh_feature_im_body(
                 l_ti[pos] = (double)sc * (double)v;
                 l_tm[pos] = (double)f * (double)v;
             }
-            adh_wave_sync();
+            im_sync<LAY::spilled>();
             const int n_ent = __popcll(mask);
             if (lane < 3) {
                 const double *src = lane == 0 ? l_w : (lane == 1 ? l_ti : l_tm);
                 for (int e = 0; e < n_ent; ++e) acc += src[e];
             }
-            adh_wave_sync();
+            im_sync<LAY::spilled>();
         }
         const double isum = __shfl(acc, 0), ssum = __shfl(acc, 1), fsum = __shfl(acc, 2);
         if (lane == 0) {
@@ -653,7 +574,7 @@ __device__ __forceinline__ void adh_feature_im_body(
     }
     for (int c = lane; c < K0 * O * F; c += ADH_WAVE) ffp_u[c] = 0.0f;
     for (int c = lane; c < K0 * O * S; c += ADH_WAVE) fsp_u[c] = 0.0f;
-    adh_wave_sync();
+    im_sync<LAY::spilled>();
     if (caps.stop_phase == 2) return;
     // ---- ONE pass over the fragment tile [k][o][s][f]:
     //   scan profile  fsp[s] = sum_f x[s][f]            (scoring/utils.py:56-66 input)
@@ -680,7 +601,7 @@ __device__ __forceinline__ void adh_feature_im_body(
                 pl_beg[c] = 0;
                 pl_end[c] = 0;
             }
-            adh_wave_sync();
+            im_sync<LAY::spilled>();
             for (int e = lane; e < n_fe; e += ADH_WAVE) {
                 const int pc = (int)entries[e].cell / SF;
                 const int pp = e > 0 ? (int)entries[e - 1].cell / SF : -1;
@@ -696,7 +617,7 @@ __device__ __forceinline__ void adh_feature_im_body(
                 pl_end[c] = (c + 1) * SF;
             }
         }
-        adh_wave_sync();
+        im_sync<LAY::spilled>();
         // cell e of the list (sparse form) or of the tile (dense form)
         auto fetch = [&](int e) -> ImEntry {
             if (compact) return entries[e];
@@ -766,7 +687,7 @@ __device__ __forceinline__ void adh_feature_im_body(
                         s_w[slot] = w;
                     }
                 }
-                adh_wave_sync();
+                im_sync<LAY::spilled>();
                 if (fl) {
                     const int cnt = min(QT, end_f - (beg_f + rr * QT));
                     for (int t = 0; t < cnt; ++t) {
@@ -790,7 +711,7 @@ __device__ __forceinline__ void adh_feature_im_body(
                         wm += tm > 0.0 ? w : 0.0;
                     }
                 }
-                adh_wave_sync();
+                im_sync<LAY::spilled>();
             }
             if (fl) {
                 if (cur_sc >= 0) fsp_u[p * S + cur_sc] = fs;
@@ -800,14 +721,14 @@ __device__ __forceinline__ void adh_feature_im_body(
                 acc_wm[p] = wm;
             }
         }
-        adh_wave_sync();
+        im_sync<LAY::spilled>();
         for (int c = lane; c < K0 * O; c += ADH_WAVE) {
             const double vi = acc_vi[c], wi = acc_wi[c], vm = acc_vm[c], wm = acc_wm[c];
             ohe_u[c] = (wi > 0) ? vi / wi : 0.0;  // weights are exp(...) > 0: "any non-zero cell" == "wi > 0"
             omz_u[c] = (wm > 0) ? vm / wm : 0.0;
         }
     }
-    adh_wave_sync();
+    im_sync<LAY::spilled>();
     if (caps.stop_phase == 3) return;
     // Dense-mode candidates (rare: a tile that had to be materialised): the isotope sums and centre means the
     // sparse form gets from its precursor pass.  Independent of everything between here and its call.
@@ -818,7 +739,7 @@ __device__ __forceinline__ void adh_feature_im_body(
         for (int f = 0; f < F; ++f) sf += prec_int(c / S, (c % S) * F + f);
         work_b[c] = sf;
     }
-    adh_wave_sync();
+    im_sync<LAY::spilled>();
     if (lane < I) {
         float ss = 0;
         for (int sc = 0; sc < S; ++sc) ss += work_b[lane * S + sc];
@@ -848,7 +769,7 @@ __device__ __forceinline__ void adh_feature_im_body(
                 l_rx[pos] = vi;
                 l_ry[pos] = vm;
             }
-            adh_wave_sync();
+            im_sync<LAY::spilled>();
             const int n_ent = __popcll(mask);
             if (lane < 4) {
                 const float *flag = (lane < 2) ? l_rx : l_ry;
@@ -856,7 +777,7 @@ __device__ __forceinline__ void adh_feature_im_body(
                 for (int e = 0; e < n_ent; ++e)
                     if (flag[e] > 0.0f) acc += src[e];
             }
-            adh_wave_sync();
+            im_sync<LAY::spilled>();
         }
         const double vh = __shfl(acc, 0), wh = __shfl(acc, 1), vmz = __shfl(acc, 2), wmz = __shfl(acc, 3);
         if (lane == 0) {
@@ -868,7 +789,7 @@ __device__ __forceinline__ void adh_feature_im_body(
     if constexpr (SPLIT) {
         if (!compact) {
             dense_precursor_sums();
-            adh_wave_sync();
+            im_sync<LAY::spilled>();
         }
         // ---- hand-over: profiles, template profiles and the per-plane means of this candidate
         static_assert(LAY::Oc <= 2 && LAY::Kc <= ADH_IM_PROF_K && LAY::Ic <= 4, "the split path takes one or two observations");
@@ -922,7 +843,7 @@ __device__ __forceinline__ void adh_feature_im_body(
         }
         present[k] = so > 0.0f;
     }
-    adh_wave_sync();
+    im_sync<LAY::spilled>();
     {
         float tot = 0;
         for (int o = 0; o < O; ++o) tot += tsum[o];
@@ -937,7 +858,7 @@ __device__ __forceinline__ void adh_feature_im_body(
     }
     if (K < 2) return;  // candidate.py:323
     const int n_present = K;
-    adh_wave_sync();
+    im_sync<LAY::spilled>();
 
     float *const g_mzlib = Fl + lay.f_pk();
     float *const g_mz = g_mzlib + Kc;
@@ -966,13 +887,13 @@ __device__ __forceinline__ void adh_feature_im_body(
             g_pos[k] = rec.position;
         }
     }
-    adh_wave_sync();
+    im_sync<LAY::spilled>();
     {
         float sum1 = 0;
         for (int k = 0; k < K; ++k) sum1 += g_int[k];
-        adh_wave_sync();
+        im_sync<LAY::spilled>();
         for (int k = lane; k < K; k += ADH_WAVE) g_int[k] = g_int[k] / sum1;
-        adh_wave_sync();
+        im_sync<LAY::spilled>();
         float sum2 = 0;
         for (int k = 0; k < K; ++k) sum2 += g_int[k];
         for (int k = lane; k < K; k += ADH_WAVE) g_fin[k] = g_int[k] / sum2;
@@ -985,7 +906,7 @@ __device__ __forceinline__ void adh_feature_im_body(
         tfp_raw[c] = osum<SR>(tpl + o * S * F + f, F, S);
     }
     // (tsp_raw: the per-scan sums taken for the observation importance above)
-    adh_wave_sync();
+    im_sync<LAY::spilled>();
     for (int c = lane; c < K * O * F; c += ADH_WAVE) {
         int k = c / (O * F), rem = c - k * O * F;
         ffp[c] = ffp_u[kmap[k] * O * F + rem];
@@ -1000,7 +921,7 @@ __device__ __forceinline__ void adh_feature_im_body(
         omz[c] = omz_u[kmap[k] * O + o];
     }
     for (int f = lane; f < F; f += ADH_WAVE) frame_rt[f] = run.rt[r.frame_start + f * L];
-    adh_wave_sync();
+    im_sync<LAY::spilled>();
     // OR-envelopes: interior points lower than a neighbour become the neighbours' mean
     for (int c = lane; c < O * F; c += ADH_WAVE) {
         int f = c % F;
@@ -1029,13 +950,13 @@ __device__ __forceinline__ void adh_feature_im_body(
         }
         tsp[c] = rr;
     }
-    adh_wave_sync();
+    im_sync<LAY::spilled>();
 
     if (caps.stop_phase == 4) return;
     // =========================== features ===========================
     // isotope intensity sums / centre means of a dense-mode candidate (sparse form: done with the template above)
     if (!compact) dense_precursor_sums();
-    adh_wave_sync();
+    im_sync<LAY::spilled>();
 
     double *const mzmean = D + lay.d_pk();
     double *const height = mzmean + Kc;
@@ -1099,7 +1020,7 @@ __device__ __forceinline__ void adh_feature_im_body(
         for (int i = 0; i < W; ++i) t += p[i];
         obs_int[k] = t;
     }
-    adh_wave_sync();
+    im_sync<LAY::spilled>();
     if (caps.stop_phase == 45) return;
     for (int k = lane; k < K; k += ADH_WAVE) {
         float ws = 0;
@@ -1142,7 +1063,7 @@ __device__ __forceinline__ void adh_feature_im_body(
         }
         ord[rk] = k;
     }
-    adh_wave_sync();
+    im_sync<LAY::spilled>();
     if (caps.stop_phase == 46) return;
 
     Assemble asmv;
@@ -1213,7 +1134,7 @@ __device__ __forceinline__ void adh_feature_im_body(
             u[3] = isb ? oint : 0.0f;
             u[4] = isy ? oint : 0.0f;
         }
-        adh_wave_sync();
+        im_sync<LAY::spilled>();
         {
             // lane j < 6: float64 sum j; 6 <= j < 11: float32 sum j - 6; lane 11: mean_top3 mass error, by rank
             double s64 = 0.0;
@@ -1268,7 +1189,7 @@ __device__ __forceinline__ void adh_feature_im_body(
             if (lane == 11) ft[41] = (float)quo;
             if (lane == 15) ft[28] = (float)quo, ft[17] = (float)O;
         }
-        adh_wave_sync();
+        im_sync<LAY::spilled>();
         {
             // np.corrcoef terms (feat::corrcoef01): area vs intensity, height vs intensity
             const double mx_a = red64[0], mx_h = red64[1], my = red64[2];
@@ -1282,7 +1203,7 @@ __device__ __forceinline__ void adh_feature_im_body(
                 t[4] = h * b;
             }
         }
-        adh_wave_sync();
+        im_sync<LAY::spilled>();
         {
             double v64[KR], s64 = 0.0;
             const int c64 = min(lane, 4);
@@ -1292,7 +1213,7 @@ __device__ __forceinline__ void adh_feature_im_body(
             for (int j = 0; j < KR; ++j) s64 += (j < K) ? v64[j] : 0.0;
             if (lane < 5) red64[7 + lane] = s64;
         }
-        adh_wave_sync();
+        im_sync<LAY::spilled>();
         if (lane < 2) {
             // lane 0: feature 18 (areas), lane 1: feature 19 (heights)
             const double fact = fmax((double)K - 1.0, 0.0);
@@ -1320,7 +1241,7 @@ __device__ __forceinline__ void adh_feature_im_body(
     if (caps.stop_phase == 5) return;
     // =========================== fragment_mobility_correlation (fragment_features.py:430-480)
     // centred scan profiles go to the second work buffer, centred frame profiles later
-    adh_wave_sync();
+    im_sync<LAY::spilled>();
     float *cen = work_b;
     {
         // fragments whose scan profiles hold any signal (fragment_features.py:447-452), in order
@@ -1346,7 +1267,7 @@ __device__ __forceinline__ void adh_feature_im_body(
                 }
             }
         }
-        adh_wave_sync();
+        im_sync<LAY::spilled>();
         const bool rows = S <= SR;  // scan rows fit the registers
         if (Km >= 3) {
             float isum = 0;
@@ -1390,7 +1311,7 @@ __device__ __forceinline__ void adh_feature_im_body(
                 mfw[c] = sqrtf(q / (float)S);
             }
             }
-            adh_wave_sync();
+            im_sync<LAY::spilled>();
             // np.dot(profile_centered, profile_centered.T) over the scan axis (scoring/utils.py:559, BLAS
             // SGEMM in the reference): one MFMA tile per observation, as in adh_feature_kernel; more
             // than 16 fragments use ordered dot products
@@ -1410,10 +1331,10 @@ __device__ __forceinline__ void adh_feature_im_body(
                         const float v = (i < Km && sc < S) ? cen[(i * O + o) * S + sc] : 0.0f;
                         d = __builtin_amdgcn_mfma_f32_16x16x4f32(v, v, d, 0, 0, 0);
                     }
-                    adh_wave_sync();
+                    im_sync<LAY::spilled>();
 #pragma unroll
                     for (int rr = 0; rr < 4; ++rr) gram[4 * kq + rr][i] = d[rr];
-                    adh_wave_sync();
+                    im_sync<LAY::spilled>();
                     // one (a, b) pair per lane and round: every pair has its own float64 division
                     for (int pr = lane; pr < Km * Km; pr += ADH_WAVE) {
                         const int a = pr / Km, b = pr - a * Km;
@@ -1424,7 +1345,7 @@ __device__ __forceinline__ void adh_feature_im_body(
                     }
 
                 }
-                adh_wave_sync();
+                im_sync<LAY::spilled>();
                 for (int a = lane; a < Km; a += ADH_WAVE) {
                     float ra[KR], rb[KR], acc = 0;
 #pragma unroll
@@ -1475,7 +1396,7 @@ __device__ __forceinline__ void adh_feature_im_body(
                 float sm = mfw[c] * ysd;
                 ftc[o * Km + a] = (float)((double)cov / ((double)sm + 1e-12));
             }
-            adh_wave_sync();
+            im_sync<LAY::spilled>();
             if (lane == 0) {
                 float lsum = 0;
                 for (int a = 0; a < Km; ++a) lsum += mlist[a];
@@ -1490,7 +1411,7 @@ __device__ __forceinline__ void adh_feature_im_body(
             }
         }
     }
-    adh_wave_sync();
+    im_sync<LAY::spilled>();
 
     if (caps.stop_phase == 6) return;
     // =========================== profile features (profile_features.py:18-206)
@@ -1502,7 +1423,7 @@ __device__ __forceinline__ void adh_feature_im_body(
             for (int o = 0; o < O; ++o) a += ffp[(k * O + o) * F + f];
             isl[c] = a;
         }
-        adh_wave_sync();
+        im_sync<LAY::spilled>();
         int cidx = F / 2, wa, wb;
         py_slice(cidx - 1, cidx + 2, F, wa, wb);
         for (int k = lane; k < K; k += ADH_WAVE) {
@@ -1512,7 +1433,7 @@ __device__ __forceinline__ void adh_feature_im_body(
             for (int f = 0; f < F; ++f)
                 nrm[k * F + f] = (ci > 0) ? (float)((double)isl[k * F + f] / ci) : 0.0f;
         }
-        adh_wave_sync();
+        im_sync<LAY::spilled>();
         for (int f = lane; f < F; f += ADH_WAVE) {
             float lo_v = 0, hi_v = 0;
             int r_lo = (K - 1) / 2, r_hi = K / 2;
@@ -1535,12 +1456,12 @@ __device__ __forceinline__ void adh_feature_im_body(
             }
             med[f] = m;
         }
-        adh_wave_sync();
+        im_sync<LAY::spilled>();
         float sx = 0;
         for (int f = 0; f < F; ++f) sx += med[f];
         float mx = (float)((double)sx / (double)F);
         for (int f = lane; f < F; f += ADH_WAVE) xm[f] = med[f] - mx;
-        adh_wave_sync();
+        im_sync<LAY::spilled>();
         float sxx = 0;
         for (int f = 0; f < F; ++f) sxx += xm[f] * xm[f];
         double var_x = (double)sxx / (double)F;
@@ -1570,7 +1491,7 @@ __device__ __forceinline__ void adh_feature_im_body(
             for (int f = 0; f < F; ++f) q += cen[c * F + f] * cen[c * F + f];
             fw[c] = sqrtf(q / (float)F);
         }
-        adh_wave_sync();
+        im_sync<LAY::spilled>();
         for (int a = lane; a < K; a += ADH_WAVE) {
             float acc = 0;
             for (int b = 0; b < K; ++b) {
@@ -1589,7 +1510,7 @@ __device__ __forceinline__ void adh_feature_im_body(
             corr[a] = acc;
         }
     }
-    adh_wave_sync();
+    im_sync<LAY::spilled>();
     if (caps.stop_phase == 71) return;
     float top3 = 0.0f;
     if (lane == 0) {
@@ -1618,7 +1539,7 @@ __device__ __forceinline__ void adh_feature_im_body(
             top3 = (float)((double)sm / (double)(n3 * n3));
         }
     }
-    adh_wave_sync();
+    im_sync<LAY::spilled>();
     const double rt_width = run.rt[r.frame_stop - 1] - run.rt[r.frame_start];
     const double mob_width = run.mobility[r.scan_start] - run.mobility[r.scan_stop - 1];
     const bool reg_rows = F <= FR && S <= SR;
@@ -1721,7 +1642,7 @@ __device__ __forceinline__ void adh_feature_im_body(
         double fracs = (double)n_ab / (double)S;
         mfw[c] = (float)(fracs * mob_width);
     }
-    adh_wave_sync();
+    im_sync<LAY::spilled>();
     if (caps.stop_phase == 72) return;
     if (lane < O) {
         int o = lane;
@@ -1739,7 +1660,7 @@ __device__ __forceinline__ void adh_feature_im_body(
         double m = (K & 1) ? (double)hi_v : (double)(lo_v + hi_v) / 2.0;
         medpk[o] = (float)m;
     }
-    adh_wave_sync();
+    im_sync<LAY::spilled>();
     if (lanes_ok) {
         // features 31-40 (feat::assemble_part2 is the loop form), lane-parallel as above
         const bool kl = lane < K;
@@ -1763,7 +1684,7 @@ __device__ __forceinline__ void adh_feature_im_body(
             u[4] = (isb && __popcll(bb & below) < 3) ? co : 0.0f;
             u[5] = (isy && __popcll(by & below) < 3) ? co : 0.0f;
         }
-        adh_wave_sync();
+        im_sync<LAY::spilled>();
         {
             float v32[KR], s32 = 0.0f;
             const int c32 = min(lane, 5);
@@ -1800,7 +1721,7 @@ __device__ __forceinline__ void adh_feature_im_body(
         }
         featv[39] = agg;
     }
-    adh_wave_sync();
+    im_sync<LAY::spilled>();
     if (caps.stop_phase == 73) return;
 
     if (lane < ADH_NUM_FEATURES) out.features[(int64_t)row * ADH_NUM_FEATURES + lane] = featv[lane];
@@ -1839,4 +1760,28 @@ __global__ __launch_bounds__(ADH_WAVE, 3) void adh_feature_im_kernel(
     int32_t n_iso_cols, adh_scoring_config_t cfg, const unsigned char *__restrict__ scratch,
     DevOut out, Caps caps, unsigned char *__restrict__ prof = nullptr) {
     adh_feature_im_body<LAY, SPLIT>((int)blockIdx.x, run, plan, iso_table, n_iso_cols, cfg, scratch, out, caps, prof);
+}
+
+// The dynamic route (launch groups of adh_feature_im_layout.h): every block lays its LDS out by its candidate's OWN
+// capacities - what the plan sized its launch group by (adh_plan_rec_im_kernel) - and not by the launch's; `caps`
+// carries the developer switches only.  SPILL = false: the whole layout in LDS (groups 0 and 1); SPILL = true: work
+// region and profile regions in the candidate's spill block of `spill` (the slab `scratch` points to as well: the
+// restrict on `scratch` holds because the spill block and the gather cells are disjoint; see adh_feature_im_body).
+template <bool SPILL>
+__global__ __launch_bounds__(ADH_WAVE, 3) void adh_feature_im_own_kernel(
+    DevTims run, const CandRecIM *__restrict__ plan, const float *__restrict__ iso_table,
+    int32_t n_iso_cols, adh_scoring_config_t cfg, const unsigned char *__restrict__ scratch,
+    unsigned char *spill, DevOut out, Caps caps) {
+    const CandRecIM &r = plan[blockIdx.x];
+    const int L = run.cycle_len, z = run.zeroth;
+    Caps own = featim::own_caps(r.k_cap, r.n_obs, max(r.scan_stop - r.scan_start, 0),
+                                max((r.frame_stop - z) / L - (r.frame_start - z) / L, 0),
+                                min(n_iso_cols, (int)cfg.top_k_isotopes));
+    own.stop_phase = caps.stop_phase;
+    own.dbg_drop_dense = caps.dbg_drop_dense;
+    if constexpr (SPILL)
+        adh_feature_im_body<featim::LayoutSpill, false>((int)blockIdx.x, run, plan, iso_table, n_iso_cols, cfg, scratch, out, own,
+                                                        nullptr, spill);
+    else
+        adh_feature_im_body<featim::Layout, false>((int)blockIdx.x, run, plan, iso_table, n_iso_cols, cfg, scratch, out, own, nullptr);
 }

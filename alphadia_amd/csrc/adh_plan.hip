@@ -19,8 +19,10 @@
 // the launch groups of the generic class and the scratch size come back to the host in one record
 // (PlanMeta).  Nothing of this depends on the order of candidates in the input, and the output rows are the input rows.
 #pragma once
+#include <stddef.h>
 #include "adh_device.h"
 #include "adh_feature_layout.h"
+#include "adh_feature_im_layout.h"
 
 // kernel classes, in processing order:
 //   0 ..  6  fused gather + feature kernel (adh_fused.hip), one observation, FM = 8, 12, ..., 32 registers
@@ -37,12 +39,9 @@
 //            ADH_GENERIC_GROUPS launch groups by their own LDS layout (sort classes 36, 37, 38: adh_feature_layout.h),
 //            the last of them the spill instantiation
 // ion-mobility plans use classes 0 (one observation), 1 (two), ADH_CLASS_IM_SMALL (one observation, a tile
-// within the limits below: a feature-kernel instantiation with 12.8 KB of LDS instead of 16.3) and the generic one
-#define ADH_CLASS_IM_SMALL 2
-#define ADH_IM_SMALL_K 12
-#define ADH_IM_SMALL_S 32
-#define ADH_IM_SMALL_F 24
-#define ADH_IM_SMALL_SF 640
+// within the limits ADH_IM_SMALL_* of adh_feature_im_layout.h: a feature-kernel instantiation with 12.8 KB of LDS instead
+// of 16.3) and the generic one; inside the plan the candidates of each of the four sort into ADH_IM_GROUPS launch groups
+// by their own dynamic LDS layout (sort classes 3 * slot + group), the last of them the spill instantiation
 #define ADH_CLASS_FUSED0 0
 #define ADH_CLASS_FUSED2 7
 #define ADH_CLASS_FAST2 14
@@ -92,6 +91,10 @@ struct PlanMeta {
     int32_t pad2;
     // largest spill layout BEYOND the LDS limit (refused by the host): bytes << 32 | min(K, 2^24 - 1) << 8 | O
     unsigned long long gen_over;
+    // ion-mobility plans: the same per plan class (slot) and launch group of the dynamic route, and the largest spill
+    // layout beyond ADH_IM_LDS_LIMIT as bytes << 32 | ~(row of the batch): the host names the candidate from its record
+    int32_t im_lds[ADH_IM_CLASS_SLOTS][ADH_IM_GROUPS];
+    unsigned long long im_over;
 };
 
 struct PlanArgs {
@@ -107,7 +110,8 @@ struct PlanArgs {
     int32_t fast_cfg, quant_all;  // fast_cfg: bit 0 the register kernels, bit 1 their wide form
     int32_t fused_cfg;      // the fused kernel may be used (one MS1 row per cycle, <= 3 isotopes): bit 0 for one, bit 1 for two observations
     int32_t n_cyc_bins;     // first-cycle bins per class in the sort key
-    int32_t spill_all;      // developer switch ADH_DEBUG_GENERIC_SPILL: every generic candidate takes the spill path
+    int32_t spill_all;      // developer switch ADH_DEBUG_GENERIC_SPILL (ion mobility: ADH_DEBUG_IM_SPILL): every candidate of
+                            // the generic class (of the dynamic route) takes the spill path
 };
 
 namespace plan {
@@ -301,6 +305,9 @@ __global__ __launch_bounds__(256) void adh_plan_rec_im_kernel(DevCands c, const 
     uint64_t nbytes = 0;
     int32_t mx_k = 0, mx_o = 0, mx_f = 0, mx_s = 0, mx_p = 0, mx_l = 0;
     bool small_tile = false;
+    uint32_t lds = 0;
+    unsigned long long over = 0;
+    int group = 0;
     if (!(r.flags & ADH_FLAG_SKIP)) {
         int err = 0;
         const int64_t z = p.zeroth;
@@ -357,8 +364,58 @@ __global__ __launch_bounds__(256) void adh_plan_rec_im_kernel(DevCands c, const 
             nbytes = adh_im_scratch_bytes(r.k_cap, r.n_obs, S, F, p.I, r.n_ms1);
             if (live) mx_k = (int32_t)r.k_cap, mx_o = r.n_obs, mx_f = F, mx_s = S, mx_p = r.n_ms1, mx_l = (int32_t)nl;
             small_tile = r.k_cap <= ADH_IM_SMALL_K && S <= ADH_IM_SMALL_S && F <= ADH_IM_SMALL_F && S * F <= ADH_IM_SMALL_SF;
+            // the launch group by the candidate's OWN dynamic layout (what its block asks for when the launch of its
+            // class takes the dynamic route: the host decides that from the maxima, launch_scoring_im); beyond the LDS
+            // of a CU the profile regions go to a spill block behind the gather cells of the same scratch block.
+            // EVERY candidate is grouped and sized here, whatever route its class will take: the route follows from the
+            // maxima of the plan, which are not known before this kernel has ended.  A class that ends on a fixed layout
+            // holds candidates of ONE group (0; the spill group under ADH_DEBUG_IM_SPILL) and the host launches it as one
+            // run (its groups and im_lds go unused);
+            // what it pays is this arithmetic per candidate and, under ADH_DEBUG_IM_SPILL alone, spill blocks in the
+            // scratch slab that no kernel touches.
+            const Caps own = featim::own_caps(r.k_cap, r.n_obs, S, F, p.I);
+            lds = featim::own_layout_bytes(own, false);
+            group = lds <= (uint32_t)ADH_GENERIC_SMALL_LDS ? 0 : 1;
+            if (lds > (uint32_t)ADH_IM_LDS_LIMIT || p.spill_all) {
+                group = ADH_IM_GROUP_SPILL;
+                lds = featim::own_layout_bytes(own, true);
+                if (lds > (uint32_t)ADH_IM_LDS_LIMIT) {
+                    if (live) over = ((unsigned long long)lds << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)j);
+                    lds = 0;  // (never launched)
+                } else {
+                    nbytes += featim::spill_bytes(own);
+                }
+            }
         }
     }
+    // feature launches by observation count (class 0: one, class 1: two, generic: more) and, with one observation,
+    // by tile size (class ADH_CLASS_IM_SMALL): the LDS of the ion-mobility feature kernel scales with both, its
+    // resident blocks with the LDS and its time with the resident blocks; most precursors sit in one isolation window
+    const int cls = (r.flags & ADH_FLAG_SKIP) ? ADH_CLASS_GENERIC
+                    : (r.n_obs <= 1 ? (small_tile ? ADH_CLASS_IM_SMALL : 0) : (r.n_obs == 2 ? 1 : ADH_CLASS_GENERIC));
+    const int slot = cls == ADH_CLASS_GENERIC ? ADH_IM_CLASS_SLOTS - 1 : cls;
+    // Largest own layout per (class, group).  NO LDS in this kernel: the plan of a chunk runs beside the scoring kernels of
+    // the chunk before it, whose blocks fill the LDS of every CU (adh_feature_im_fused4_kernel: eight of 20 KB); a plan
+    // block that holds an LDS granule keeps one of them off its CU (measured: 288 bytes of static LDS here cost the common
+    // class's fused kernel 45 us of 800 per chunk).  No block barrier either: the cycle-row loop above is very uneven, and
+    // a wavefront that is done leaves its SIMD at once.  So: one wavefront reduction per (class, group) PRESENT in the
+    // wavefront (three on an ordinary batch), and the record's words read once, early, by lanes 0 .. 11 - a stale value
+    // only means an atomic that changes nothing - so that no reduction ends in a round trip to L2.
+    constexpr int N_SG = ADH_IM_CLASS_SLOTS * ADH_IM_GROUPS;
+    const int wl = (int)(threadIdx.x % ADH_WAVE);
+    const int32_t seen = wl < N_SG ? *reinterpret_cast<volatile int32_t *>(&meta->im_lds[0][0] + wl) : 0;
+    const int sg = live && lds > 0 ? slot * ADH_IM_GROUPS + group : -1;
+    for (unsigned long long todo = __ballot(sg >= 0); todo != 0;) {
+        const int lead = __ffsll(todo) - 1;
+        const int k = __shfl(sg, lead);
+        int32_t v = sg == k ? (int32_t)lds : 0;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off));
+        const int32_t was = __shfl(seen, k);  // (every lane takes part in the shuffle)
+        if (wl == lead && v > was) atomicMax(&meta->im_lds[0][0] + k, v);
+        todo &= ~__ballot(sg == k);
+    }
+    if (__any(over != 0ull)) plan::raise_max64(&meta->im_over, over);  // (a refusal: rare)
     plan::raise_max(&meta->all_k, mx_k);
     plan::raise_max(&meta->all_o, mx_o);
     plan::raise_max(&meta->all_f, mx_f);
@@ -366,12 +423,8 @@ __global__ __launch_bounds__(256) void adh_plan_rec_im_kernel(DevCands c, const 
     plan::raise_max(&meta->all_op, mx_p);
     plan::raise_max(&meta->all_n_lib, mx_l);
     if (!live) return;
-    // feature launches by observation count (class 0: one, class 1: two, generic: more) and, with one observation,
-    // by tile size (class ADH_CLASS_IM_SMALL): the LDS of the ion-mobility feature kernel scales with both, its
-    // resident blocks with the LDS and its time with the resident blocks; most precursors sit in one isolation window
-    const int cls = (r.flags & ADH_FLAG_SKIP) ? ADH_CLASS_GENERIC
-                    : (r.n_obs <= 1 ? (small_tile ? ADH_CLASS_IM_SMALL : 0) : (r.n_obs == 2 ? 1 : ADH_CLASS_GENERIC));
-    const uint32_t key = (uint32_t)cls * (uint32_t)p.n_cyc_bins + min(bin, (uint32_t)p.n_cyc_bins - 1u);
+    // (rows flagged to be skipped and rows with an error: the first group of the generic class, no LDS of their own)
+    const uint32_t key = (uint32_t)(slot * ADH_IM_GROUPS + group) * (uint32_t)p.n_cyc_bins + min(bin, (uint32_t)p.n_cyc_bins - 1u);
     recs[j] = r;
     keys[j] = key;
     idx[j] = (uint32_t)j;

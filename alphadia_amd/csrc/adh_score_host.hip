@@ -250,12 +250,14 @@ int check_candidate_args(adh_handle *h, const adh_candidates_t *c) {
 
 // ---------------------------------------------------------------- the plan (adh_plan.hip)
 __global__ void adh_plan_init_kernel(PlanMeta *meta, int32_t I) {
-    PlanMeta m;
-    memset(&m, 0, sizeof(m));
-    m.all_k = m.all_o = m.all_f = m.all_n_lib = m.all_s = m.all_op = 1;
-    m.gen_k = m.gen_o = m.gen_f = m.gen_n_lib = 1;
+    // a word per lane into the record itself (a private copy of the record is scratch memory): the ten maxima
+    // all_k ... gen_n_lib start at 1, everything else at 0
+    static_assert(offsetof(PlanMeta, class_first) - offsetof(PlanMeta, all_k) == 10 * sizeof(int32_t) && sizeof(PlanMeta) % 4 == 0,
+                  "PlanMeta: the maxima are ten consecutive words");
+    constexpr unsigned w0 = offsetof(PlanMeta, all_k) / 4, w1 = offsetof(PlanMeta, class_first) / 4;
+    int32_t *const words = reinterpret_cast<int32_t *>(meta);
+    for (unsigned w = threadIdx.x; w < sizeof(PlanMeta) / 4; w += blockDim.x) words[w] = (w >= w0 && w < w1) ? 1 : 0;
     (void)I;
-    *meta = m;
 }
 
 int plan_reserve(adh_handle *h, PlanSlot &s, int64_t n, bool im) {
@@ -296,7 +298,7 @@ int plan_reserve(adh_handle *h, PlanSlot &s, int64_t n, bool im) {
 
 struct PlanKey {
     uint32_t top_k_fragments, top_k_isotopes;
-    bool fast_cfg, quant_all, fused_cfg, wide_cfg, spill_all;
+    bool fast_cfg, quant_all, fused_cfg, wide_cfg, spill_all, im_spill_all;
 };
 
 PlanKey plan_key(const adh_scoring_config_t *cfg) {
@@ -304,7 +306,8 @@ PlanKey plan_key(const adh_scoring_config_t *cfg) {
     return PlanKey{cfg->top_k_fragments, cfg->top_k_isotopes, fast, cfg->quant_all != 0,
                    fast && !getenv("ADH_DEBUG_NO_FUSED"),   // developer switches: two-kernel path only
                    fast && !getenv("ADH_DEBUG_NO_WIDE"),    // ... more than 16 kept fragments through the generic kernel
-                   getenv("ADH_DEBUG_GENERIC_SPILL") != nullptr};  // ... every generic candidate through the spill instantiation
+                   getenv("ADH_DEBUG_GENERIC_SPILL") != nullptr,   // ... every generic candidate through the spill instantiation
+                   getenv("ADH_DEBUG_IM_SPILL") != nullptr};       // ... every ion-mobility candidate of the dynamic route likewise
 }
 
 // enqueue the plan of rows [row0, row0 + n) on `st`; plan_finish() waits for it
@@ -321,10 +324,10 @@ int plan_enqueue(adh_handle *h, PlanSlot &s, const adh_scoring_config_t *cfg, in
     p.top_k = cfg->top_k_fragments;
     p.fast_cfg = (key.fast_cfg ? 1 : 0) | (key.wide_cfg ? 2 : 0);
     p.quant_all = key.quant_all ? 1 : 0;
-    p.spill_all = key.spill_all ? 1 : 0;
+    p.spill_all = (im ? key.im_spill_all : key.spill_all) ? 1 : 0;
     p.fused_cfg = (key.fused_cfg && !im && h->run.n_ms1_obs == 1 && p.I <= 4) ? (getenv("ADH_DEBUG_NO_FUSED2") ? 1 : 3) : 0;
     const unsigned blocks = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(adh_plan_init_kernel, dim3(1), dim3(1), 0, st, s.d_meta, p.I);
+    hipLaunchKernelGGL(adh_plan_init_kernel, dim3(1), dim3(128), 0, st, s.d_meta, p.I);
     const int64_t n_frames = im ? h->tims.n_frames : h->run.n_spectra;
     const int L = im ? h->tims.cycle_len : h->run.cycle_len;
     p.L = L;
@@ -428,6 +431,30 @@ int plan_finish(adh_handle *h, PlanSlot &s, const adh_scoring_config_t *cfg, int
     }
     p.generic_over = m.gen_over;
     p.spill_all = key.spill_all;
+    p.im_spill_all = key.im_spill_all;
+    if (h->tims_staged) {
+        // the launch groups of a class are consecutive sort classes (3 * slot + group): one class to everything outside the plan
+        static const int slot_class[ADH_IM_CLASS_SLOTS] = {0, 1, ADH_CLASS_IM_SMALL, ADH_CLASS_GENERIC};
+        for (int c = 0; c < ADH_N_CLASSES; ++c) p.n_class[c] = 0;
+        for (int sl = 0; sl < ADH_IM_CLASS_SLOTS; ++sl)
+            for (int g = 0; g < ADH_IM_GROUPS; ++g) {
+                const int sc = sl * ADH_IM_GROUPS + g;
+                p.n_im[sl][g] = (int64_t)m.class_first[sc + 1] - (int64_t)m.class_first[sc];
+                p.lds_im[sl][g] = m.im_lds[sl][g];
+                p.n_class[slot_class[sl]] += p.n_im[sl][g];
+            }
+        p.im_over = m.im_over;
+        if (m.im_over != 0) {  // (a refusal: the record of the largest candidate, for the message)
+            CandRecIM rec;
+            const uint32_t j = 0xFFFFFFFFu - (uint32_t)(m.im_over & 0xFFFFFFFFu);
+            HIP_TRY(hipMemcpy(&rec, static_cast<const CandRecIM *>(s.recs) + j, sizeof(rec), hipMemcpyDeviceToHost));
+            const int L = h->tims.cycle_len, z = h->tims.zeroth;
+            p.im_over_shape[0] = rec.k_cap;
+            p.im_over_shape[1] = std::max<int>(rec.n_obs, 1);
+            p.im_over_shape[2] = std::max(rec.scan_stop - rec.scan_start, 0);
+            p.im_over_shape[3] = std::max((rec.frame_stop - z) / L - (rec.frame_start - z) / L, 0);
+        }
+    }
     p.caps_all = Caps{m.all_k, m.all_o, m.all_f, std::max(I, 1), m.all_n_lib, 0, m.all_s, m.all_op};
     p.scratch_bytes = std::max<uint64_t>(m.scratch_bytes, 32);
     p.top_k_fragments = key.top_k_fragments;
@@ -502,6 +529,32 @@ void fold_timed(adh_handle *h, bool wait) {
     h->timed.resize(keep);
 }
 
+// What an ion-mobility plan is still refused for, before anything is launched or counted.  No candidate is refused for
+// the product of the call's maxima: every block of the dynamic route asks for its candidate's own layout.
+int refuse_im(const Plan &p) {
+    char buf[256];
+    if (p.im_over != 0) {
+        // even the spill path keeps everything indexed by K * O and K, the template and the scan tables in LDS
+        // (featim::LayoutSpill)
+        snprintf(buf, sizeof(buf),
+                 "candidate needs %llu bytes of LDS on the spill path of the ion-mobility feature kernel (K=%lld O=%lld S=%lld F=%lld): "
+                 "exceeds the bound of %d bytes",
+                 (unsigned long long)(p.im_over >> 32), (long long)p.im_over_shape[0], (long long)p.im_over_shape[1],
+                 (long long)p.im_over_shape[2], (long long)p.im_over_shape[3], (int)ADH_IM_LDS_LIMIT);
+        return fail(ADH_ERR_UNSUPPORTED, buf);
+    }
+    size_t g_pad = 0;
+    if (const char *dbg = getenv("ADH_DEBUG_IM_GATHER_LDS_PAD")) g_pad = (size_t)atoi(dbg);
+    const size_t g_lds = adh_gather_im_lds_bytes(p.caps_all) + g_pad;
+    if (g_lds > 160 * 1024) {
+        snprintf(buf, sizeof(buf),
+                 "library slice of %d fragments needs %zu bytes of LDS in the ion-mobility gather kernel: exceeds 160 KiB",
+                 p.caps_all.n_lib, g_lds);
+        return fail(ADH_ERR_UNSUPPORTED, buf);
+    }
+    return ADH_OK;
+}
+
 int launch_scoring_im(adh_handle *h, Plan &p, const adh_scoring_config_t *cfg, adh_output_t *out, hipStream_t st) {
     if (cfg->collect_fragments && p.caps_all.k > out->top_k)
         return fail(ADH_ERR_INVALID_ARGUMENT, "output top_k smaller than config.top_k_fragments");
@@ -512,15 +565,7 @@ int launch_scoring_im(adh_handle *h, Plan &p, const adh_scoring_config_t *cfg, a
     size_t g_pad = 0, f_pad = 0;  // developer switches: extra LDS per block, to see what occupancy is worth
     if (const char *dbg = getenv("ADH_DEBUG_IM_GATHER_LDS_PAD")) g_pad = (size_t)atoi(dbg);
     if (const char *dbg = getenv("ADH_DEBUG_IM_FEATURE_LDS_PAD")) f_pad = (size_t)atoi(dbg);
-    const size_t g_lds = adh_gather_im_lds_bytes(p.caps_all) + g_pad;
-    const size_t f_lds = adh_feature_im_lds_bytes(p.caps_all) + f_pad;
-    if (f_lds > 160 * 1024 - ADH_IM_STATIC_LDS || g_lds > 160 * 1024) {
-        char buf[256];
-        snprintf(buf, sizeof(buf),
-                 "ion-mobility tile needs %zu bytes of LDS (K=%d O=%d S=%d F=%d): exceeds 160 KiB", f_lds,
-                 p.caps_all.k, p.caps_all.o, p.caps_all.s, p.caps_all.f);
-        return fail(ADH_ERR_UNSUPPORTED, buf);
-    }
+    const size_t g_lds = adh_gather_im_lds_bytes(p.caps_all) + g_pad;  // (within the LDS of a CU: refuse_im)
     // Split feature path (adh_features_im2.hip): the one-observation classes with a fixed layout leave a profile
     // record per candidate behind the scratch blocks, and a second kernel with four candidates per wavefront
     // finishes them.  ADH_DEBUG_IM_NO_SPLIT=1: the one-kernel path for everything (the GPU suite holds both to
@@ -690,10 +735,30 @@ int launch_scoring_im(adh_handle *h, Plan &p, const adh_scoring_config_t *cfg, a
                     hipLaunchKernelGGL(adh_feature_im_kernel<featim::LayoutCommon>, dim3((unsigned)cnt), dim3(ADH_WAVE),
                                        featim::LayoutCommon(cc).bytes() + f_pad, st, h->tims, p.d_recs_im + first, h->cs.iso, n_iso,
                                        *cfg, d_scratch, *out, cc);
-                else
-                    hipLaunchKernelGGL(adh_feature_im_kernel<featim::Layout>, dim3((unsigned)cnt), dim3(ADH_WAVE),
-                                       featim::Layout(cc).bytes() + f_pad, st, h->tims, p.d_recs_im + first, h->cs.iso, n_iso, *cfg,
-                                       d_scratch, *out, cc);
+                else {
+                    // the dynamic route: one launch per group of own layouts, each with the LDS of its largest candidate
+                    // (the plan sorted the class by group); the last group keeps its profile regions in the spill blocks
+                    // of the scratch slab
+                    const int sl = c == ADH_CLASS_GENERIC ? ADH_IM_CLASS_SLOTS - 1 : c;
+                    int64_t at = 0;
+                    for (int g = 0; g < ADH_IM_GROUPS; ++g) {
+                        const int64_t ng = p.n_im[sl][g];
+                        if (ng == 0) continue;
+                        const size_t lds = (size_t)p.lds_im[sl][g];
+                        const size_t lds_pad = std::min<size_t>(lds + f_pad, ADH_IM_LDS_LIMIT);
+                        if (g == ADH_IM_GROUP_SPILL)
+                            hipLaunchKernelGGL(adh_feature_im_own_kernel<true>, dim3((unsigned)ng), dim3(ADH_WAVE), lds_pad, st, h->tims,
+                                               p.d_recs_im + first + at, h->cs.iso, n_iso, *cfg, d_scratch, d_scratch, *out, cc);
+                        else
+                            hipLaunchKernelGGL(adh_feature_im_own_kernel<false>, dim3((unsigned)ng), dim3(ADH_WAVE), lds_pad, st, h->tims,
+                                               p.d_recs_im + first + at, h->cs.iso, n_iso, *cfg, d_scratch, (unsigned char *)nullptr,
+                                               *out, cc);
+                        HIP_TRY(hipGetLastError());
+                        h->im_stats[g] += ng;
+                        h->im_stats[ADH_IM_GROUPS + g] = std::max<int64_t>(h->im_stats[ADH_IM_GROUPS + g], (int64_t)lds);
+                        at += ng;
+                    }
+                }
                 HIP_TRY(hipGetLastError());
             }
             first += cnt;
@@ -717,6 +782,10 @@ int launch_scoring(adh_handle *h, Plan &p, const adh_scoring_config_t *cfg, adh_
                  (unsigned long long)(p.generic_over >> 32), (unsigned long long)((p.generic_over >> 8) & 0xFFFFFFu),
                  (unsigned long long)(p.generic_over & 0xFFu), (int)ADH_GENERIC_LDS_LIMIT);
         return fail(ADH_ERR_UNSUPPORTED, buf);
+    }
+    if (h->tims_staged) {
+        const int rc = refuse_im(p);
+        if (rc != ADH_OK) return rc;
     }
     for (int c = 0; c < ADH_N_CLASSES; ++c) h->class_counts[c] += p.n_class[c];
     if (h->tims_staged) return launch_scoring_im(h, p, cfg, out, st);
@@ -1105,7 +1174,7 @@ int adh_score_uploaded(adh_handle_t *h, const adh_scoring_config_t *cfg, adh_out
     const PlanKey key = plan_key(cfg);
     if (!(p.ready && p.top_k_fragments == key.top_k_fragments && p.top_k_isotopes == key.top_k_isotopes &&
           p.fast_ok == key.fast_cfg && p.fused_ok == key.fused_cfg && p.wide_ok == key.wide_cfg && p.quant_all == key.quant_all &&
-          p.spill_all == key.spill_all)) {
+          p.spill_all == key.spill_all && p.im_spill_all == key.im_spill_all)) {
         p = Plan();
         rc = plan_enqueue(h, h->slots[0], cfg, 0, h->cs.n, st);
         if (rc == ADH_OK) rc = plan_finish(h, h->slots[0], cfg, 0, h->cs.n, p);
@@ -1156,6 +1225,15 @@ int adh_generic_launch_stats(adh_handle_t *h, int64_t *stats, int32_t reset) {
     for (int i = 0; i < 2 * ADH_GENERIC_GROUPS; ++i) {
         stats[i] = h->generic_stats[i];
         if (reset) h->generic_stats[i] = 0;
+    }
+    return ADH_OK;
+}
+
+int adh_im_launch_stats(adh_handle_t *h, int64_t *stats, int32_t reset) {
+    if (!h || !stats) return fail(ADH_ERR_INVALID_ARGUMENT, "NULL argument");
+    for (int i = 0; i < 2 * ADH_IM_GROUPS; ++i) {
+        stats[i] = h->im_stats[i];
+        if (reset) h->im_stats[i] = 0;
     }
     return ADH_OK;
 }

@@ -98,6 +98,7 @@ EXPORTED_SYMBOLS = [
     "adh_staged_fragments_read",
     "adh_plan_class_counts",
     "adh_generic_launch_stats",
+    "adh_im_launch_stats",
     "adh_pg_create",
     "adh_pg_destroy",
     "adh_pg_solve",
@@ -1052,6 +1053,17 @@ class Context:
             "adh_generic_launch_stats",
         )
         return {"candidates": stats[: _abi.N_GENERIC_GROUPS].copy(), "lds_bytes": stats[_abi.N_GENERIC_GROUPS :].copy()}
+
+    def im_launch_stats(self, reset: bool = False) -> dict:
+        """Launch groups of the dynamic route of the ion-mobility feature kernel (small layouts, layouts up to the LDS of
+        a CU, the spill path) of every plan launched on this handle since the last reset: ``candidates`` per group and
+        the largest dynamic ``lds_bytes`` a launch of the group asked for."""
+        stats = np.zeros(2 * _abi.N_IM_GROUPS, dtype=np.int64)
+        _check(
+            lib.adh_im_launch_stats(self._h, stats.ctypes.data_as(C.POINTER(C.c_int64)), C.c_int32(int(reset))),
+            "adh_im_launch_stats",
+        )
+        return {"candidates": stats[: _abi.N_IM_GROUPS].copy(), "lds_bytes": stats[_abi.N_IM_GROUPS :].copy()}
 
     # -- fragment competition -------------------------------------------
     def select_candidates(self, precursors: _abi.Marshalled, cfg, kernel) -> dict:

@@ -479,6 +479,22 @@ int adh_plan_class_counts(adh_handle_t *handle, int64_t *counts, int32_t reset);
 #define ADH_GENERIC_LAUNCH_STATS 6
 int adh_generic_launch_stats(adh_handle_t *handle, int64_t *stats, int32_t reset);
 
+/*
+ * Launch groups of the dynamic route of an ion-mobility plan: the launches of the feature kernel whose blocks lay
+ * their LDS out at run time (a plan class whose maxima no fixed layout holds; every class with
+ * ADH_DEBUG_IM_DYNAMIC_LAYOUT set).  Inside its class a candidate is launched in one of three groups by the LDS
+ * layout it needs on its own (fragments kept x observations x (scans + cycles)):
+ *   group 0  layouts up to 38 784 bytes (several blocks share a CU)
+ *   group 1  layouts up to 161 280 bytes (160 KiB less the kernel's 2 560 bytes of static LDS)
+ *   group 2  larger ones: the spill instantiation, with the work and profile regions in the scratch slab
+ * `stats[0..2]`: candidates per group of every plan whose launches took the dynamic route on the handle since the
+ * last reset, summed over classes, chunks and entry points; `stats[3..5]`: the largest dynamic LDS (bytes) any
+ * such launch of the group asked for.  Nothing is counted for a refused call.
+ * ADH_DEBUG_IM_SPILL (set to any value) sends every candidate of the dynamic route to group 2.
+ */
+#define ADH_IM_LAUNCH_STATS 6
+int adh_im_launch_stats(adh_handle_t *handle, int64_t *stats, int32_t reset);
+
 /* ------------------------------------------------------------------------
  * Multi-GPU: one process per GPU, candidates sharded by contiguous score-group ranges
  * (score groups are independent, search/scoring/containers/score_group.py:66-75), ONE RCCL
