@@ -687,6 +687,20 @@ RESIDENT_PROTOTYPES = {
 }
 
 
+# ... of the selection -> scoring hand-over in HBM (adh_select_handover.hip)
+HANDOVER_PROTOTYPES = {
+    "adh_select_candidates_resident": [C.c_void_p, C.POINTER(Precursors), C.POINTER(SelectionConfig), C.POINTER(C.c_float),
+                                       C.c_int32, C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8),
+                                       C.POINTER(C.c_uint8)],
+    "adh_assemble_selected": [C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.POINTER(C.c_int64),
+                              C.POINTER(C.c_int64), C.POINTER(C.c_int32)],
+    "adh_select_handover_stats": [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)],
+    "adh_score_selected_resident": [C.c_void_p, C.c_void_p],
+    "adh_selected_ids": [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.c_int64],
+    "adh_take_selected": [C.c_void_p, C.POINTER(C.c_int64), C.c_int64, C.POINTER(CandidateTable), C.POINTER(C.c_uint32)],
+}
+
+
 # ... of the staging of one part of a channel-wise decoy strategy
 _f32pp = C.POINTER(C.POINTER(C.c_float))
 STAGE_PART_PROTOTYPES = {
@@ -810,9 +824,9 @@ PLAN_PROTOTYPES = {
 
 
 def declare(lib) -> None:
-    """Argument types of the entries listed in RESIDENT_PROTOTYPES, STAGE_PART_PROTOTYPES, APPEND_PROTOTYPES,
+    """Argument types of the entries listed in RESIDENT_PROTOTYPES, HANDOVER_PROTOTYPES, STAGE_PART_PROTOTYPES, APPEND_PROTOTYPES,
     QUANT_PROTOTYPES, PG_PROTOTYPES, PFDR_PROTOTYPES, TL_PROTOTYPES, MBR_PROTOTYPES, STAGE_LIB_PROTOTYPES and PLAN_PROTOTYPES (the others are called with explicit casts)."""
-    for name, argtypes in {**RESIDENT_PROTOTYPES, **STAGE_PART_PROTOTYPES, **APPEND_PROTOTYPES, **QUANT_PROTOTYPES,
+    for name, argtypes in {**RESIDENT_PROTOTYPES, **HANDOVER_PROTOTYPES, **STAGE_PART_PROTOTYPES, **APPEND_PROTOTYPES, **QUANT_PROTOTYPES,
                            **PG_PROTOTYPES, **PFDR_PROTOTYPES, **TL_PROTOTYPES, **MBR_PROTOTYPES, **STAGE_LIB_PROTOTYPES, **PLAN_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes

@@ -397,6 +397,23 @@ struct adh_handle {
     bool big_staged = false;
     void *sel_slab = nullptr;       // precursor columns + candidate table of adh_select_candidates (grow-only)
     size_t sel_slab_bytes = 0;
+    // the selection hand-over (adh_select_handover.hip): where adh_select_candidates_resident left the table and the
+    // precursor columns in the slab, and what adh_assemble_selected made of them
+    struct Selected {
+        int stage = 0;  // 0: nothing; 1: the slab holds a selection; 2: ... and `cs` the table assembled from it
+        int64_t n_prec = 0, cand_count = 0, n_kept = 0, n_selected = 0;
+        int32_t n_iso_cols = 0;
+        const uint32_t *precursor_idx = nullptr, *frag_start = nullptr, *frag_stop = nullptr, *elution_group = nullptr;
+        const uint8_t *charge = nullptr, *decoy = nullptr, *channel = nullptr;
+        const float *mz = nullptr, *iso = nullptr;
+        const uint32_t *t_u32[9] = {nullptr};  // the candidate table, in the order of adh_candidate_table_t (1: u8, 2: f32)
+        uint32_t longest = 0;                  // longest library slice of the assembled table
+        int64_t im_cells = 1;                  // largest scans x cycles tile of the assembled table
+        int32_t stats[4] = {0, 0, 0, 0};       // was_sorted, radix passes, score-group scans, rows flagged FLAG_SKIP
+        double assemble_ms = 0.0;              // HIP-event time of the assemble kernels of the last call
+    } sel;
+    void *sel_rows = nullptr;       // per assembled row: its row in the selection table, then its position among score > 0
+    size_t sel_rows_bytes = 0;
     void *scratch_slab = nullptr;   // per-candidate scratch blocks (grow-only, shared by all chunks)
     uint64_t scratch_slab_bytes = 0;
     DevTables tables[2];            // slot 1 only with a communicator (double-buffered all-gather)
@@ -703,6 +720,7 @@ int adh_destroy(adh_handle_t *h) {
     if (h->cs.base) (void)hipFree(h->cs.base);
     if (h->scratch_slab) (void)hipFree(h->scratch_slab);
     if (h->sel_slab) (void)hipFree(h->sel_slab);
+    if (h->sel_rows) (void)hipFree(h->sel_rows);
     for (hipStream_t st : h->stream_aux)
         if (st) (void)hipStreamDestroy(st);
     for (hipEvent_t e : h->ev_aux)
@@ -872,6 +890,7 @@ int adh_stage_alpharaw(adh_handle_t *h, const adh_alpharaw_t *d) {
     h->run_buf.release();
     h->plan = Plan();
     h->cands_uploaded = false;  // the resident table was planned against the previous run
+    h->sel.stage = 0;           // ... and so was a selection left in the slab
     h->run_staged = false;
     h->tims_staged = false;
 
@@ -1109,6 +1128,7 @@ int adh_stage_timstof(adh_handle_t *h, const adh_timstof_t *d) {
     h->run_buf.release();
     h->plan = Plan();
     h->cands_uploaded = false;  // the resident table was planned against the previous run
+    h->sel.stage = 0;           // ... and so was a selection left in the slab
     h->run_staged = false;
     h->tims_staged = false;
     // validate the index arrays on the host: kernels use them unchecked
@@ -1232,6 +1252,7 @@ int adh_stage_fragments(adh_handle_t *h, const adh_fragments_t *f) {
     h->lib_staged = false;
     h->plan = Plan();
     h->cands_uploaded = false;  // fragment slices of the resident table refer to the previous library
+    h->sel.stage = 0;           // ... and those of a selection left in the slab
     std::vector<LibRec> recs((size_t)f->n);
     for (int64_t i = 0; i < f->n; ++i) {
         LibRec &r = recs[(size_t)i];
@@ -1259,10 +1280,38 @@ int adh_stage_fragments(adh_handle_t *h, const adh_fragments_t *f) {
 
 namespace {
 
+// the per-precursor id columns of adh_select_candidates_resident (host)
+struct SelIds {
+    const uint32_t *elution_group_idx;
+    const uint8_t *decoy, *channel;
+};
+
+// what a resident selection left in the slab, for adh_assemble_selected
+void note_selected(adh_handle *h, const adh_precursors_t *pc, const adh_selection_config_t *cfg, unsigned char *slab,
+                   const size_t *o_prec, const size_t *o_out) {
+    adh_handle::Selected &s = h->sel;
+    s = adh_handle::Selected();
+    s.n_prec = pc->n;
+    s.cand_count = cfg->candidate_count;
+    s.n_iso_cols = pc->n_isotope_cols;
+    s.precursor_idx = reinterpret_cast<const uint32_t *>(slab + o_prec[0]);
+    s.frag_start = reinterpret_cast<const uint32_t *>(slab + o_prec[1]);
+    s.frag_stop = reinterpret_cast<const uint32_t *>(slab + o_prec[2]);
+    s.charge = slab + o_prec[3];
+    s.mz = reinterpret_cast<const float *>(slab + o_prec[4]);
+    s.iso = reinterpret_cast<const float *>(slab + o_prec[5]);
+    s.elution_group = reinterpret_cast<const uint32_t *>(slab + o_prec[6]);
+    s.decoy = slab + o_prec[7];
+    s.channel = slab + o_prec[8];
+    for (int f = 0; f < 9; ++f) s.t_u32[f] = reinterpret_cast<const uint32_t *>(slab + o_out[f]);
+    s.stage = 1;
+}
+
 // Candidate selection on the staged ion-mobility run (see adh_select_im.hip); the caller has
-// validated the arguments and zero-filled the host table.
+// validated the arguments and zero-filled the host table.  `ids` (adh_select_candidates_resident): the table stays in
+// the slab, with the id columns and the isotope columns beside it, and nothing is copied out.
 int select_candidates_im(adh_handle *h, const adh_precursors_t *pc, const adh_selection_config_t *cfg,
-                         const float *kernel, int32_t k0, int32_t k1, adh_candidate_table_t *out) {
+                         const float *kernel, int32_t k0, int32_t k1, adh_candidate_table_t *out, const SelIds *ids) {
     const int64_t n = pc->n;
     const DevTims &T = h->tims;
     const int L = T.cycle_len, SM = T.scan_max, z = T.zeroth;
@@ -1306,6 +1355,11 @@ int select_candidates_im(adh_handle *h, const adh_precursors_t *pc, const adh_se
     HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, (unsigned long long *)nullptr, (unsigned long long *)nullptr, (int)n,
                                              h->stream));
     const size_t o_tmp = carve(scan_bytes);
+    size_t o_iso = 0, o_eg = 0, o_dc = 0, o_chn = 0;
+    if (ids) {
+        o_iso = carve((size_t)n * pc->n_isotope_cols * 4);
+        o_eg = carve((size_t)n * 4), o_dc = carve((size_t)n), o_chn = carve((size_t)n);
+    }
     size_t o_out[9];
     for (int f = 0; f < 9; ++f) o_out[f] = carve((size_t)out->n * width[f]);
     if (h->sel_slab_bytes < off) {
@@ -1330,6 +1384,12 @@ int select_candidates_im(adh_handle *h, const adh_precursors_t *pc, const adh_se
     if (e == hipSuccess) e = put(o_mz, pc->mz, (size_t)n * 4);
     if (e == hipSuccess) e = put(o_ku, ku.data(), (size_t)k0 * 8);
     if (e == hipSuccess) e = put(o_kv, kv.data(), (size_t)k1 * 8);
+    if (ids) {
+        if (e == hipSuccess) e = put(o_iso, pc->isotope_intensity, (size_t)n * pc->n_isotope_cols * 4);
+        if (e == hipSuccess) e = put(o_eg, ids->elution_group_idx, (size_t)n * 4);
+        if (e == hipSuccess) e = put(o_dc, ids->decoy, (size_t)n);
+        if (e == hipSuccess) e = put(o_chn, ids->channel, (size_t)n);
+    }
     if (e == hipSuccess) e = hipMemsetAsync(slab + o_red, 0, 64, h->stream);
     if (e == hipSuccess) e = hipMemsetAsync(slab + o_out[0], 0, off - o_out[0], h->stream);  // (rows without a candidate stay zero)
     if (e != hipSuccess) return fail(ADH_ERR_HIP, std::string("selection upload: ") + hipGetErrorString(e));
@@ -1470,10 +1530,11 @@ int select_candidates_im(adh_handle *h, const adh_precursors_t *pc, const adh_se
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipEventRecord(e1, h->stream);
-        for (int f = 0; f < 9 && e == hipSuccess; ++f)
+        for (int f = 0; f < 9 && e == hipSuccess && !ids; ++f)
             e = hipMemcpyAsync(host_out[f], slab + o_out[f], (size_t)out->n * width[f], hipMemcpyDeviceToHost, h->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
         if (e != hipSuccess) rc = fail(ADH_ERR_HIP, std::string("ion-mobility selection kernels: ") + hipGetErrorString(e));
+        if (rc == ADH_OK && !ids) h->d2h_bytes += (uint64_t)out->n * 33;
         float ms = 0.0f;
         if (rc == ADH_OK && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) total_ms += ms;
         (void)hipEventDestroy(e0);
@@ -1481,6 +1542,10 @@ int select_candidates_im(adh_handle *h, const adh_precursors_t *pc, const adh_se
     }
     const double t_kernels = now();
     if (rc == ADH_OK) h->last_select_ms = total_ms;
+    if (rc == ADH_OK && ids) {
+        const size_t o_prec[9] = {o_idx, o_fs, o_fe, o_ch, o_mz, o_iso, o_eg, o_dc, o_chn};
+        note_selected(h, pc, cfg, slab, o_prec, o_out);
+    }
     const double t_copy = now();
     if (timing)
         fprintf(stderr, "[adh] select_candidates_im n=%lld: upload + plan %.2f ms, batches %.2f, kernels + copy-out %.2f (kernels %.2f)\n",
@@ -1489,11 +1554,12 @@ int select_candidates_im(adh_handle *h, const adh_precursors_t *pc, const adh_se
     return rc;
 }
 
-}  // namespace
-
-int adh_select_candidates(adh_handle_t *h, const adh_precursors_t *pc, const adh_selection_config_t *cfg,
-                          const float *kernel, int32_t k_rows, int32_t k_cols, adh_candidate_table_t *out) {
+// adh_select_candidates (`ids` NULL: the table is copied into `out`) and adh_select_candidates_resident (`ids` set:
+// `out` only carries the row count; the table, the precursor columns and the id columns stay in the slab)
+int select_candidates_run(adh_handle_t *h, const adh_precursors_t *pc, const adh_selection_config_t *cfg,
+                          const float *kernel, int32_t k_rows, int32_t k_cols, adh_candidate_table_t *out, const SelIds *ids) {
     if (!h || !pc || !cfg || !kernel || !out) return fail(ADH_ERR_INVALID_ARGUMENT, "NULL argument");
+    h->sel.stage = 0;  // (the slab is rewritten)
     if (!h->run_staged && !h->tims_staged) return fail(ADH_ERR_NOT_STAGED, "no run staged");
     if (!h->d_lib) return fail(ADH_ERR_NOT_STAGED, "no fragment library staged");
     if (pc->n < 0 || cfg->candidate_count <= 0 || cfg->candidate_count > sel::MAX_CAND)
@@ -1516,13 +1582,21 @@ int adh_select_candidates(adh_handle_t *h, const adh_precursors_t *pc, const adh
     void *host_out[] = {out->precursor_idx, out->rank, out->score, out->scan_center, out->scan_start,
                         out->scan_stop, out->frame_center, out->frame_start, out->frame_stop};
     const size_t width[] = {4, 1, 4, 4, 4, 4, 4, 4, 4};
-    for (int f = 0; f < 9; ++f) {
+    for (int f = 0; f < 9 && !ids; ++f) {
         if (!host_out[f]) return fail(ADH_ERR_INVALID_ARGUMENT, "candidate table buffer is NULL");
         memset(host_out[f], 0, (size_t)out->n * width[f]);
     }
     lap("memset");
-    if (n == 0) return ADH_OK;
-    if (h->tims_staged) return select_candidates_im(h, pc, cfg, kernel, k_rows, k_cols, out);
+    if (n == 0) {
+        if (ids) {  // (an empty selection: nothing in the slab is read)
+            h->sel = adh_handle::Selected();
+            h->sel.cand_count = cfg->candidate_count;
+            h->sel.n_iso_cols = pc->n_isotope_cols;
+            h->sel.stage = 1;
+        }
+        return ADH_OK;
+    }
+    if (h->tims_staged) return select_candidates_im(h, pc, cfg, kernel, k_rows, k_cols, out, ids);
     // One grow-only slab of the handle holds the precursor columns, the tile limits and the candidate table of a
     // call (19 allocations and as many frees cost more than the kernel).  The per-precursor limits - two searches
     // over the retention times of 3e5 spectra each: 17 ms per 100 000 precursors on one host core - and the checks
@@ -1577,6 +1651,8 @@ int adh_select_candidates(adh_handle_t *h, const adh_precursors_t *pc, const adh
                  o_rt = carve((size_t)n * 4), o_mz = carve((size_t)n * 4), o_iso = carve((size_t)n * pc->n_isotope_cols * 4),
                  o_cs = carve((size_t)n * 4), o_cc = carve((size_t)n * 4), o_red = carve(16),
                  o_kern = carve((size_t)k_rows * k_cols * 4);
+    size_t o_eg = 0, o_dc = 0, o_chn = 0;
+    if (ids) o_eg = carve((size_t)n * 4), o_dc = carve((size_t)n), o_chn = carve((size_t)n);
     size_t o_out[9];
     for (int f = 0; f < 9; ++f) o_out[f] = carve((size_t)out->n * width[f]);
     if (h->sel_slab_bytes < off) {
@@ -1600,6 +1676,11 @@ int adh_select_candidates(adh_handle_t *h, const adh_precursors_t *pc, const adh
     if (e == hipSuccess) e = put(o_mz, pc->mz, (size_t)n * 4);
     if (e == hipSuccess) e = put(o_iso, pc->isotope_intensity, (size_t)n * pc->n_isotope_cols * 4);
     if (e == hipSuccess) e = put(o_kern, kernel, (size_t)k_rows * k_cols * 4);
+    if (ids) {
+        if (e == hipSuccess) e = put(o_eg, ids->elution_group_idx, (size_t)n * 4);
+        if (e == hipSuccess) e = put(o_dc, ids->decoy, (size_t)n);
+        if (e == hipSuccess) e = put(o_chn, ids->channel, (size_t)n);
+    }
     if (e == hipSuccess) e = hipMemsetAsync(slab + o_red, 0, 16, h->stream);
     if (e == hipSuccess) e = hipMemsetAsync(slab + o_out[0], 0, off - o_out[0], h->stream);  // (the candidate table: rows without a candidate stay zero)
     if (e != hipSuccess) return fail(ADH_ERR_HIP, std::string("selection upload: ") + hipGetErrorString(e));
@@ -1672,10 +1753,15 @@ int adh_select_candidates(adh_handle_t *h, const adh_precursors_t *pc, const adh
                            (SelectArgs{h->run, h->d_lib, dp, (int64_t)n, *cfg, reinterpret_cast<const float *>(slab + o_kern), taps, caps, dt}));
         e = hipGetLastError();
         (void)hipEventRecord(e1, h->stream);
-        for (int f = 0; f < 9 && e == hipSuccess; ++f)
+        for (int f = 0; f < 9 && e == hipSuccess && !ids; ++f)
             e = hipMemcpyAsync(host_out[f], slab + o_out[f], (size_t)out->n * width[f], hipMemcpyDeviceToHost, h->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
         if (e != hipSuccess) rc = fail(ADH_ERR_HIP, std::string("selection kernel: ") + hipGetErrorString(e));
+        if (rc == ADH_OK && !ids) h->d2h_bytes += (uint64_t)out->n * 33;
+        if (rc == ADH_OK && ids) {
+            const size_t o_prec[9] = {o_idx, o_fs, o_fe, o_ch, o_mz, o_iso, o_eg, o_dc, o_chn};
+            note_selected(h, pc, cfg, slab, o_prec, o_out);
+        }
         float ms = 0.0f;
         if (rc == ADH_OK && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) h->last_select_ms = ms;
         (void)hipEventDestroy(e0);
@@ -1683,6 +1769,13 @@ int adh_select_candidates(adh_handle_t *h, const adh_precursors_t *pc, const adh
     }
     lap("kernel + copy out");
     return rc;
+}
+
+}  // namespace
+
+int adh_select_candidates(adh_handle_t *h, const adh_precursors_t *pc, const adh_selection_config_t *cfg,
+                          const float *kernel, int32_t k_rows, int32_t k_cols, adh_candidate_table_t *out) {
+    return select_candidates_run(h, pc, cfg, kernel, k_rows, k_cols, out, nullptr);
 }
 
 namespace {
@@ -2008,6 +2101,7 @@ int adh_fragcomp_stats(adh_handle_t *h, double *kernel_ms, int64_t *pairs, int64
 #include "adh_take_rows.hip"
 #include "adh_resident_append.hip"
 #include "adh_session.h"  // behind fail, HIP_TRY and the hipMalloc / hipFree macros: its allocations go through the block cache
+#include "adh_select_handover.hip"
 #include "adh_quant.hip"
 #include "adh_grouping.hip"
 #include "adh_protein_fdr.hip"

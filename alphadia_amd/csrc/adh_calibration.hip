@@ -238,6 +238,7 @@ int library_changes(adh_handle *h) {
     HIP_TRY(hipDeviceSynchronize());
     h->plan = Plan();
     h->cands_uploaded = false;
+    h->sel.stage = 0;
     return ADH_OK;
 }
 

@@ -1151,6 +1151,7 @@ int adh_upload_candidates(adh_handle_t *h, const adh_candidates_t *c) {
     if (rc != ADH_OK) return rc;
     h->plan = Plan();
     h->cands_uploaded = false;
+    h->sel.stage = std::min(h->sel.stage, 1);  // (a table assembled from a selection is replaced)
     rc = cand_reserve(h, c->n, c->n_isotope_cols);
     if (rc != ADH_OK) return rc;
     rc = cand_upload_range(h, c, 0, c->n, h->stream);
@@ -1243,10 +1244,12 @@ namespace {
 // ion-mobility candidates reserve a scratch block sized for their dense tiles (116 KB at 38 scans x 29 cycles,
 // although ~1 % of it is touched): *max_rows bounds a chunk so that the slab stays within a third of the free device
 // memory (0: no bound).  Tile sizes from the host columns; K <= top_k fragments, 3 observations assumed.
-int im_chunk_bound(adh_handle *h, const adh_candidates_t *c, const adh_scoring_config_t *cfg, int64_t *max_rows) {
+// (`cells_known` > 0: the largest tile of a table assembled on the device, whose columns the host does not hold)
+int im_chunk_bound(adh_handle *h, const adh_candidates_t *c, const adh_scoring_config_t *cfg, int64_t *max_rows,
+                   int64_t cells_known = 0) {
     *max_rows = 0;
-    int64_t cells = 1;
-    for (int64_t i = 0; i < c->n; ++i) {
+    int64_t cells = std::max<int64_t>(cells_known, 1);
+    for (int64_t i = 0; i < c->n && cells_known <= 0; ++i) {
         const int64_t S = std::max<int64_t>(c->scan_stop[i] - c->scan_start[i], 1);
         const int64_t F = std::max<int64_t>((c->frame_stop[i] - c->frame_start[i]) / std::max(h->tims.cycle_len, 1) + 1, 1);
         cells = std::max(cells, S * F);
@@ -1294,12 +1297,17 @@ struct PipelineUnwind {
 // the host -> host pipeline behind adh_score_candidates (padded tables into `out`) and adh_score_candidates_compact
 // (`cop` set: `out` only carries n and top_k, the compacted columns go to `cop`) and adh_score_candidates_resident
 // (`resident`: `out` only carries n and top_k, nothing is copied back).  This is the schedule of the three streams;
-// how the results leave the device is the copy-out mode's part (adh_copyout.hip).
+// how the results leave the device is the copy-out mode's part (adh_copyout.hip).  `device_cands`
+// (adh_score_selected_resident): the candidate columns are in the handle's slab already (adh_assemble_selected wrote
+// them there), `c` only carries n and n_isotope_cols, and nothing is uploaded.
 int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring_config_t *cfg, adh_output_t *out,
-                   adh_compact_output_t *cop, bool resident = false) {
+                   adh_compact_output_t *cop, bool resident = false, bool device_cands = false) {
     if (!h || !c || !cfg || !out) return fail(ADH_ERR_INVALID_ARGUMENT, "NULL argument");
     if (out->n != c->n) return fail(ADH_ERR_INVALID_ARGUMENT, "output rows != candidates");
-    int rc = check_candidate_args(h, c);
+    adh_candidates_t shape_only = *c;  // (what check_candidate_args looks at when the columns are on the device)
+    shape_only.n = 0;
+    int rc = check_candidate_args(h, device_cands ? &shape_only : c);
+    if (rc == ADH_OK && c->n > 0x7FFFFFFFll) rc = fail(ADH_ERR_UNSUPPORTED, "more than 2^31 candidates in one batch");
     if (rc == ADH_OK) rc = check_score_args(h, cfg, out);
     if (rc != ADH_OK) return rc;
     for (int i = 0; i < kNumOutFields && !cop && !resident; ++i)
@@ -1313,8 +1321,15 @@ int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring
     h->cands_uploaded = false;
     h->acc_live = false;         // ... and so are accumulated tables (adh_score_candidates_resident_append)
     h->acc_rows = 0;
-    rc = cand_reserve(h, n, c->n_isotope_cols);
+    if (device_cands && (h->sel.stage != 2 || h->cs.n != n || h->cs.n_iso_cols != c->n_isotope_cols))
+        return fail(ADH_ERR_NOT_STAGED, "no table assembled from a selection in the candidate slab");
+    if (!device_cands) h->sel.stage = std::min(h->sel.stage, 1);  // (the slab's columns are replaced)
+    rc = cand_reserve(h, n, c->n_isotope_cols);  // (the same rows and isotope columns: the same layout, nothing moves)
     if (rc != ADH_OK) return rc;
+    if (device_cands) h->cs.d.flags = h->cs.flags;
+    auto cand_upload = [&](int64_t a, int64_t b, hipStream_t st) {
+        return device_cands ? (int)ADH_OK : cand_upload_range(h, c, a, b, st);
+    };
     // device tables: with a communicator attached the layout is padded to the largest shard and
     // double-buffered (the all-gather of call i overlaps call i + 1)
     if (h->comm_attached() && n > h->comm_rows)
@@ -1356,7 +1371,7 @@ int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring
     // chunk boundaries: at most max_rows rows per chunk
     int64_t max_rows = 0;
     if (h->tims_staged) {
-        rc = im_chunk_bound(h, c, cfg, &max_rows);
+        rc = im_chunk_bound(h, c, cfg, &max_rows, device_cands ? h->sel.im_cells : 0);
         if (rc != ADH_OK) return rc;
     }
     if (cop || compact_wanted) {  // (a chunk's slot offsets are 32-bit words of the packed count)
@@ -1393,9 +1408,9 @@ int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring
     // had ended and the copy-out had a hole of 1.15 ms (profiles/headline_pipeline.json, `before`).  The burst
     // overlaps the copy-out of chunks 0 and 1 in both orders: that copy runs at 47 - 49 instead of 56 GB/s.
     trace.mark_start(si);
-    rc = cand_upload_range(h, c, 0, cut[1], si);
+    rc = cand_upload(0, cut[1], si);
     if (rc == ADH_OK) rc = plan_enqueue(h, h->slots[0], cfg, 0, cut[1], si);
-    if (rc == ADH_OK && n_chunks > 1) rc = cand_upload_range(h, c, cut[1], cut[2], si);
+    if (rc == ADH_OK && n_chunks > 1) rc = cand_upload(cut[1], cut[2], si);
     if (rc != ADH_OK) return rc;
     // the host teams start now that the device has work: started in front of the first copy-in, the 16 threads made
     // the call's set-up 0.4 - 0.5 ms instead of 0.07 - 0.10 (profiles/headline_pipeline.json, `setup_ms`)
@@ -1409,8 +1424,8 @@ int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring
             if (ci >= 1) HIP_TRY(hipStreamWaitEvent(si, h->ev_k[ps ^ 1], 0));
             rc = plan_enqueue(h, h->slots[ps ^ 1], cfg, a2, b2 - a2, si);
             // (the rows of chunk 2 behind the plan of chunk 1, ALL later rows behind the plan of chunk 2: see above)
-            if (rc == ADH_OK && ci == 0 && n_chunks > 2) rc = cand_upload_range(h, c, cut[2], cut[3], si);
-            if (rc == ADH_OK && ci == 1 && n_chunks > 3) rc = cand_upload_range(h, c, cut[3], n, si);
+            if (rc == ADH_OK && ci == 0 && n_chunks > 2) rc = cand_upload(cut[2], cut[3], si);
+            if (rc == ADH_OK && ci == 1 && n_chunks > 3) rc = cand_upload(cut[3], n, si);
             if (rc != ADH_OK) return rc;
         }
         Plan p;

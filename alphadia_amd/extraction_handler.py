@@ -22,6 +22,7 @@ INTEGRATION.md shows the three-line patch that registers the backend.
 from __future__ import annotations
 
 import logging
+import os
 import time
 
 import numpy as np
@@ -75,11 +76,15 @@ class HipExtractionHandler:
 
     def _select_candidates(self, dia_data, spectral_library) -> pd.DataFrame:
         """extraction_handler.py:411-446 with ``CandidateSelection`` replaced by the GPU operator."""
+        return self._candidate_selection(dia_data, spectral_library)(thread_count=self._config["general"]["thread_count"])
+
+    def _candidate_selection(self, dia_data, spectral_library) -> HipCandidateSelection:
+        """The selection operator of extraction_handler.py:411-446, configured by the optimisation manager."""
         om = self._optimization_manager
         self._selection_config.update(dict(
             rt_tolerance=om.rt_error, mobility_tolerance=om.mobility_error, candidate_count=om.num_candidates,
             precursor_mz_tolerance=om.ms1_error, fragment_mz_tolerance=om.ms2_error))
-        selection = HipCandidateSelection(
+        return HipCandidateSelection(
             dia_data,
             spectral_library.precursor_df,
             spectral_library.fragment_df,
@@ -92,7 +97,6 @@ class HipExtractionHandler:
             fwhm_mobility=om.fwhm_mobility,
             device=self._device,
         )
-        return selection(thread_count=self._config["general"]["thread_count"])
 
     def select_candidates(self, dia_data, spectral_library, apply_cutoff: bool = False) -> pd.DataFrame:
         """extraction_handler.py:121-154; both run layouts are selected on the GPU.  A selection
@@ -160,19 +164,51 @@ class HipExtractionHandler:
         that branch builds them - the features frame's columns, ``_decoy``, ``proba``, ``qval`` (``_candidate_idx``
         and ``valid`` when fragments competed), ``candidate_idx``; the PSMs in the FDR output order, the fragments in
         candidate / slot order - each with a fresh RangeIndex.  Channel-wise FDR, an FDR manager that is not a
-        ``HipFDRManager`` and an attached communicator take the chained calls instead (the reason is logged once)."""
+        ``HipFDRManager`` and an attached communicator take the chained calls instead (the reason is logged once).
+        Where the handler's own GPU selection runs, the candidate table goes from selection to scoring in HBM as well
+        (``select_handover``; ``last_timings["path"]`` is then ``"resident_select"``)."""
         t_0 = time.perf_counter()
-        candidates_df = self.select_candidates(dia_data, spectral_library, apply_cutoff=True)
         reason = self.resident_refusal()
+        if reason is None and self.select_handover():
+            return self._extract_selected(dia_data, spectral_library, t_0)
+        candidates_df = self.select_candidates(dia_data, spectral_library, apply_cutoff=True)
         if reason is not None:
             if reason not in self._fallbacks_logged:
                 self._fallbacks_logged.add(reason)
                 self._reporter.log_string(f"Resident extraction not used: {reason}", verbosity="info")
                 logger.info("resident extraction not used: %s", reason)
             return self._extract_chained(candidates_df, dia_data, spectral_library, t_0)
-        fdr_config = self._config["fdr"]
         t_1 = time.perf_counter()
         resident = self._candidate_scoring(dia_data, spectral_library).score_resident(candidates_df)
+        return self._extract_scored(resident, "resident", t_0, t_1)
+
+    def select_handover(self) -> bool:
+        """Whether ``extract`` hands the candidate table from selection to scoring in HBM: the
+        handler's own GPU selection runs (no ``selection_handler``) and ``ADH_DEBUG_NO_SELECT_HANDOVER`` is unset."""
+        return self._selection_handler is None and not os.environ.get("ADH_DEBUG_NO_SELECT_HANDOVER")
+
+    def _extract_selected(self, dia_data, spectral_library, t_0: float) -> tuple[pd.DataFrame, pd.DataFrame]:
+        """``extract`` with the candidate table handed from selection to scoring in HBM: ``select_candidates(...,
+        apply_cutoff=True)`` and ``score_resident`` without the frame in between.  Logs what ``select_candidates`` logs."""
+        cutoff = self._optimization_manager.score_cutoff
+        self._reporter.log_string(
+            f"Extracting batch of {len(spectral_library.precursor_df)} precursors", verbosity="progress"
+        )
+        scorer = self._candidate_scoring(dia_data, spectral_library)  # (stages the run and the library)
+        selected = self._candidate_selection(dia_data, spectral_library).select_resident(
+            apply_cutoff=True, score_cutoff=cutoff, score_grouped=self._scoring_config.score_grouped,
+            reference_channel=self._scoring_config.reference_channel)
+        self._reporter.log_string(
+            f"Removed {selected.n_selected - selected.n_kept} precursors with score below cutoff "
+            f"{cutoff}. {selected.n_kept} precursors remain.",
+            verbosity="info",
+        )
+        t_1 = time.perf_counter()
+        return self._extract_scored(scorer.score_resident(selected), "resident_select", t_0, t_1)
+
+    def _extract_scored(self, resident, path: str, t_0: float, t_1: float) -> tuple[pd.DataFrame, pd.DataFrame]:
+        """The FDR stage on the tables in HBM and the survivors' frames."""
+        fdr_config = self._config["fdr"]
         t_2 = time.perf_counter()
         psm_df = self._fdr_manager.fit_predict_resident(
             resident, competitive=fdr_config["competitive_scoring"],
@@ -190,7 +226,7 @@ class HipExtractionHandler:
                                                        fragments_df["rank"].to_numpy())
         t_4 = time.perf_counter()
         # wall time of the stages of the last call, in ms (select includes the cutoff)
-        self.last_timings = {"path": "resident", "select_ms": (t_1 - t_0) * 1e3, "score_ms": (t_2 - t_1) * 1e3,
+        self.last_timings = {"path": path, "select_ms": (t_1 - t_0) * 1e3, "score_ms": (t_2 - t_1) * 1e3,
                              "fdr_ms": (t_3 - t_2) * 1e3, "filter_ms": (t_4 - t_3) * 1e3, "total_ms": (t_4 - t_0) * 1e3}
         return precursor_df, fragments_df
 

@@ -134,6 +134,12 @@ EXPORTED_SYMBOLS = [
     "adh_mbr_index",
     "adh_mbr_notnull_objects",
     "adh_mbr_stats",
+    "adh_select_candidates_resident",
+    "adh_assemble_selected",
+    "adh_select_handover_stats",
+    "adh_score_selected_resident",
+    "adh_selected_ids",
+    "adh_take_selected",
 ]
 
 
@@ -533,6 +539,8 @@ class Context:
         self.comm_rank = 0
         # one more per scoring call that replaces the device tables (a resident result checks it is still current)
         self.tables_serial = 0
+        # ... and one more per selection or staging call (a resident selection checks it is still current)
+        self.select_serial = 0
         self._sessions = weakref.WeakSet()  # the live _DeviceSession objects of this handle
 
     def _close_sessions(self):
@@ -759,6 +767,7 @@ class Context:
             if not force and key == self._run_key:
                 return False
             m = _abi.pack_timstof(dia)
+            self.select_serial += 1
             _check(lib.adh_stage_timstof(self._h, m.ref()), "adh_stage_timstof")
             self._run_key = key
             self._run_keepalive = (dia.mz_values, dia.intensity_values, dia.push_indices, dia.tof_indptr)
@@ -767,6 +776,7 @@ class Context:
         if not force and key == self._run_key:
             return False
         m = _abi.pack_alpharaw(dia)
+        self.select_serial += 1
         _check(lib.adh_stage_alpharaw(self._h, m.ref()), "adh_stage_alpharaw")
         self._run_key = key
         self._run_keepalive = (dia.mz_values, dia.intensity_values, dia.peak_start_idx_list, dia.rt_values)
@@ -777,6 +787,7 @@ class Context:
         if not force and key == self._lib_key:
             return False
         m = _abi.pack_fragments(*columns)
+        self.select_serial += 1
         _check(lib.adh_stage_fragments(self._h, m.ref()), "adh_stage_fragments")
         self._staged_library(columns, m.struct.n, key)
         return True
@@ -797,6 +808,7 @@ class Context:
         records packed by a kernel from the uploaded columns."""
         m = _abi.pack_fragments(*columns)
         self._lib_key = None
+        self.select_serial += 1
         _check(lib.adh_stage_fragments_columns(self._h, m.ref(), None, None), "adh_stage_fragments_columns")
         self._staged_library(columns, m.struct.n, self._key(*columns))
 
@@ -810,6 +822,7 @@ class Context:
         m = _abi.pack_fragments_calibrated(*columns)
         y = np.empty(int(m.struct.n), dtype=np.float64)
         self._lib_key = None
+        self.select_serial += 1
         _check(lib.adh_stage_fragments_columns(self._h, m.ref(), C.byref(packed), y.ctypes.data_as(C.POINTER(C.c_double))),
                "adh_stage_fragments_columns")
         self._staged_library(columns, m.struct.n, None)
@@ -823,6 +836,7 @@ class Context:
         packed = _abi.pack_loess_model(model.scale_mean, model.scale_max, model.beta)
         y = np.empty(getattr(self, "_n_lib", 0), dtype=np.float64)  # (no library: the call says so)
         self._lib_key = None
+        self.select_serial += 1
         _check(lib.adh_calibrate_staged_fragments(self._h, C.byref(packed), y.ctypes.data_as(C.POINTER(C.c_double))),
                "adh_calibrate_staged_fragments")
         return y
@@ -1075,6 +1089,7 @@ class Context:
             raise ValueError("kernel must be 2-D (scan, cycle)")
         n = int(precursors.struct.n) * int(c.candidate_count)
         m_out, arrays = _abi.alloc_candidate_table(n)
+        self.select_serial += 1
         _check(
             lib.adh_select_candidates(
                 self._h, precursors.ref(), C.byref(c), k.ctypes.data_as(C.POINTER(C.c_float)),
@@ -1083,6 +1098,75 @@ class Context:
             "adh_select_candidates",
         )
         return arrays
+
+    # -- selection -> scoring hand-over in HBM ----------------------------
+    def select_resident(self, precursors: _abi.Marshalled, cfg, kernel, elution_group_idx, decoy, channel) -> int:
+        """``adh_select_candidates_resident``: the selection of ``select_candidates``, its table left in HBM with the
+        precursor columns and the three id columns (one entry per precursor).  Returns the rows of the table."""
+        c = _abi.pack_selection_config(cfg)
+        k = np.ascontiguousarray(kernel, dtype=np.float32)
+        if k.ndim != 2:
+            raise ValueError("kernel must be 2-D (scan, cycle)")
+        n = int(precursors.struct.n)
+        eg, dc, ch = _abi.as_c(elution_group_idx, np.uint32), _abi.as_c(decoy, np.uint8), _abi.as_c(channel, np.uint8)
+        if eg.shape != (n,) or dc.shape != (n,) or ch.shape != (n,):
+            raise ValueError("elution_group_idx / decoy / channel must hold one entry per precursor")
+        self.select_serial += 1
+        _check(
+            lib.adh_select_candidates_resident(
+                self._h, precursors.ref(), C.byref(c), k.ctypes.data_as(C.POINTER(C.c_float)), C.c_int32(k.shape[0]),
+                C.c_int32(k.shape[1]), eg.ctypes.data_as(C.POINTER(C.c_uint32)), dc.ctypes.data_as(C.POINTER(C.c_uint8)),
+                ch.ctypes.data_as(C.POINTER(C.c_uint8))),
+            "adh_select_candidates_resident",
+        )
+        return n * int(c.candidate_count)
+
+    def assemble_selected(self, apply_cutoff: bool, score_cutoff: float, score_grouped: bool,
+                          reference_channel: int) -> tuple[int, int, bool]:
+        """``adh_assemble_selected`` on the table of ``select_resident``: ``(n_selected, n_kept, was_sorted)``.  The
+        cutoff is rounded to the dtype NumPy compares a float32 column with it in (the device compares in float64)."""
+        cutoff = float(np.asarray(score_cutoff).astype(np.result_type(np.float32, score_cutoff)))
+        n_sel, n_kept, was_sorted = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+        _check(lib.adh_assemble_selected(self._h, C.c_int32(int(bool(apply_cutoff))), C.c_double(cutoff),
+                                         C.c_int32(int(bool(score_grouped))), C.c_int32(int(reference_channel)),
+                                         C.byref(n_sel), C.byref(n_kept), C.byref(was_sorted)), "adh_assemble_selected")
+        return int(n_sel.value), int(n_kept.value), bool(was_sorted.value)
+
+    def select_handover_stats(self) -> dict:
+        """``adh_select_handover_stats``: what the last ``assemble_selected`` did."""
+        stats, ms = (C.c_int32 * 4)(), C.c_double(0.0)
+        _check(lib.adh_select_handover_stats(self._h, stats, C.byref(ms)), "adh_select_handover_stats")
+        return {"was_sorted": bool(stats[0]), "radix_passes": int(stats[1]), "group_scans": int(stats[2]),
+                "skipped_rows": int(stats[3]), "assemble_ms": float(ms.value)}
+
+    def score_selected_resident(self, cfg_jit) -> int:
+        """``adh_score_selected_resident``: ``score_resident`` on the table ``assemble_selected`` left in HBM; returns
+        the width of the device tables."""
+        cfg = _abi.pack_config(cfg_jit)
+        self.tables_serial += 1
+        _check(lib.adh_score_selected_resident(self._h, C.byref(cfg)), "adh_score_selected_resident")
+        view = self.device_tables()
+        self.n_candidates = int(view.n)
+        return int(view.top_k)
+
+    def selected_ids(self, n: int) -> tuple[np.ndarray, np.ndarray]:
+        """``adh_selected_ids``: (row in the selection table, rank) of the ``n`` rows of the assembled table."""
+        rows, rank = np.empty(n, np.uint32), np.empty(n, np.uint8)
+        _check(lib.adh_selected_ids(self._h, rows.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                    rank.ctypes.data_as(C.POINTER(C.c_uint8)), C.c_int64(n)), "adh_selected_ids")
+        return rows, rank
+
+    def take_selected(self, rows) -> tuple[dict, np.ndarray]:
+        """``adh_take_selected``: the nine candidate columns of the listed rows of the assembled table, and their
+        positions among the rows with score > 0."""
+        r = np.ascontiguousarray(rows, dtype=np.int64)
+        if r.ndim != 1:
+            raise ValueError("rows must be one-dimensional")
+        m_out, arrays = _abi.alloc_candidate_table(r.shape[0])
+        pos = np.zeros(r.shape[0], np.uint32)
+        _check(lib.adh_take_selected(self._h, r.ctypes.data_as(C.POINTER(C.c_int64)), C.c_int64(r.shape[0]), m_out.ref(),
+                                     pos.ctypes.data_as(C.POINTER(C.c_uint32))), "adh_take_selected")
+        return arrays, pos
 
     def select_time_ms(self) -> float:
         ms = C.c_double(0.0)

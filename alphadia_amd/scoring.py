@@ -1039,6 +1039,7 @@ class ResidentScores:
         table_rows = np.asarray(table_rows, dtype=np.int64)
         sorted_rows = np.unique(table_rows)
         comp = s._ctx.take_rows(sorted_rows)
+        candidates_df, candidate_row = self._candidates_of(sorted_rows)
         # the row columns in the order asked for (comp["row"] is ascending: it is sorted_rows without invalid rows)
         pos = np.searchsorted(comp["row"], table_rows)
         found = pos < len(comp["row"])
@@ -1047,16 +1048,101 @@ class ResidentScores:
         rows_part = {name: comp[name][pos] for name, _ in _abi.COMPACT_ROW_FIELDS}
         rows_part["features"] = comp["features"][:, pos]
         features_df = collect_candidates(
-            self._candidates_df, None, s.precursors_flat_df, s.rt_column, s.mobility_column, s.precursor_mz_column,
-            row_maps=(self.order, self.prec_row), sequence_counts=s._sequence_counts(), compact=rows_part)
+            candidates_df, None, s.precursors_flat_df, s.rt_column, s.mobility_column, s.precursor_mz_column,
+            row_maps=(candidate_row, self.prec_row), sequence_counts=s._sequence_counts(), compact=rows_part)
         fragments_df = collect_fragments_compact(comp, s.precursors_flat_df, self.prec_row)
         return features_df, fragments_df
+
+    def _candidates_of(self, sorted_rows: np.ndarray) -> tuple[pd.DataFrame, np.ndarray]:
+        """A candidate frame that holds the listed table rows, and the row of every table row in it."""
+        del sorted_rows  # (the whole frame is on the host)
+        return self._candidates_df, self.order
+
+
+class ResidentSelectedScores(ResidentScores):
+    """``ResidentScores`` for a table that came from ``HipCandidateSelection.select_resident``: the candidate table
+    stayed in HBM too.  The ids come from the library through the two id columns of ``ResidentCandidates.ids`` (a
+    candidate's library row is its row in the selection table divided by the candidate count); the candidate columns
+    of the rows ``frames`` is asked for are copied back with them (``adh_take_selected``)."""
+
+    def __init__(self, scorer: "HipCandidateScoring", selected, serial: int):
+        self._scorer = scorer
+        self._selected = selected
+        self._serial = serial
+        rows, rank = selected.ids()
+        self.prec_row = (rows // np.uint32(selected.candidate_count)).astype(np.intp)
+        lib = scorer.precursors_flat_df
+
+        def take(name, dtype):
+            return np.ascontiguousarray(lib[name].to_numpy().take(self.prec_row), dtype=dtype)
+
+        channel = take("channel", np.uint8) if "channel" in lib.columns else np.zeros(len(rows), dtype=np.uint8)
+        self.metadata = pd.DataFrame({"precursor_idx": take("precursor_idx", np.uint32), "rank": rank,
+                                      "decoy": take("decoy", np.uint8),
+                                      "elution_group_idx": take("elution_group_idx", np.uint32), "channel": channel})
+        self._table_row = rows
+        self._columns = None
+        self._candidate_columns = None
+
+    @property
+    def order(self) -> np.ndarray:
+        """Row of every table row in ``ResidentCandidates.to_frame()`` (its rank in (precursor, slot) order)."""
+        return np.searchsorted(np.sort(self._table_row), self._table_row)
+
+    def _check_current(self):
+        super()._check_current()
+        self._selected._check_current()
+
+    def table_column(self, name: str) -> np.ndarray:
+        from alphadia_amd.selection import CANDIDATE_COLUMNS
+
+        if name in CANDIDATE_COLUMNS and name not in ("precursor_idx", "rank"):
+            if self._candidate_columns is None:  # (the nine columns of every table row: 33 bytes each, once)
+                self._check_current()
+                self._candidate_columns = self._scorer._ctx.take_selected(np.arange(self.n_table, dtype=np.int64))[0]
+            return self._candidate_columns[name]
+        s = self._scorer
+        if name in ("n_K", "n_R", "n_P"):
+            return np.asarray(s._sequence_counts()[("n_K", "n_R", "n_P").index(name)]).take(self.prec_row)
+        if name in self.metadata.columns:
+            return self.metadata[name].to_numpy()
+        if name in s.precursors_flat_df.columns:
+            return s.precursors_flat_df[name].to_numpy().take(self.prec_row)
+        raise KeyError(f"{name!r} is neither a candidate nor a library column")
+
+    def _candidates_of(self, sorted_rows: np.ndarray) -> tuple[pd.DataFrame, np.ndarray]:
+        frame, _ = self._selected.frame_of(sorted_rows)
+        candidate_row = np.zeros(self.n_table, dtype=np.int64)  # (only the listed rows are read)
+        candidate_row[sorted_rows] = np.arange(len(sorted_rows), dtype=np.int64)
+        return frame, candidate_row
+
+
+def _score_selected(self, selected) -> ResidentSelectedScores:
+    """``score_resident`` for a ``ResidentCandidates``: the table is in HBM already (``adh_score_selected_resident``)."""
+    sel = selected.selection
+    if selected._ctx is not self._ctx:
+        raise ValueError("the selection is resident on another GPU than this scorer's")
+    if sel.precursor_mz_column != self.precursor_mz_column or not np.array_equal(
+            sel.precursors_flat["precursor_idx"].to_numpy(), self.precursors_flat_df["precursor_idx"].to_numpy()):
+        raise ValueError("the selection and the scorer were built from different libraries or m/z columns")
+    selected._check_current()
+    cfg = self._kernel_config()
+    if (selected.score_grouped, selected.reference_channel) != (bool(self.config.score_grouped),
+                                                               int(self.config.reference_channel)):
+        selected.assemble(self.config.score_grouped, self.config.reference_channel)
+    self._ctx.score_selected_resident(cfg)
+    return ResidentSelectedScores(self, selected, self._ctx.tables_serial)
 
 
 def _score_resident(self, candidates_df: pd.DataFrame) -> ResidentScores:
     """Score ``candidates_df`` into the device tables and copy nothing back (``adh_score_candidates_resident``):
     the FDR stage runs on the tables in HBM (``perform_fdr_resident``) and ``ResidentScores.frames`` copies back
-    the rows it keeps."""
+    the rows it keeps.  A ``selection.ResidentCandidates`` (``HipCandidateSelection.select_resident``) is scored where
+    it lies in HBM; the result has the same interface."""
+    from alphadia_amd.selection import ResidentCandidates
+
+    if isinstance(candidates_df, ResidentCandidates):
+        return _score_selected(self, candidates_df)
     soa = assemble_candidates(
         candidates_df, self.precursors_flat_df, self.precursor_mz_column, score_grouped=self.config.score_grouped,
         reference_channel=self.config.reference_channel)

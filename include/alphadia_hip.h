@@ -657,6 +657,63 @@ int adh_transpose_timstof(adh_handle_t *handle, const uint32_t *tof_indices, con
 /* Duration (ms, HIP events) of the selection kernel of the last adh_select_candidates call. */
 int adh_select_time_ms(adh_handle_t *handle, double *kernel_ms);
 
+/* ------------------------------------------------------------------------
+ * Selection -> scoring hand-over in HBM (adh_select_handover.hip): the candidate table never visits the host.
+ * ---------------------------------------------------------------------- */
+
+/*
+ * adh_select_candidates without the host table: the same kernels, and the table (precursors x candidate_count rows,
+ * row p * candidate_count + slot) stays in the handle's selection slab with the precursor columns and the three
+ * per-precursor id columns scoring orders and groups by - the dtypes scoring.assemble_candidates converts them to.
+ * Nothing is copied out.  The slab stays as it is until the next selection call; staging a run or a library ends
+ * the selection.  ADH_ERR_UNSUPPORTED with a communicator attached.
+ */
+int adh_select_candidates_resident(adh_handle_t *handle, const adh_precursors_t *precursors,
+                                   const adh_selection_config_t *config, const float *kernel, int32_t kernel_rows,
+                                   int32_t kernel_cols, const uint32_t *elution_group_idx, const uint8_t *decoy,
+                                   const uint8_t *channel);
+
+/*
+ * candidate_container_to_df (config_df.py:270-298), "filter 1" of the extraction handler
+ * (extraction_handler.py:177-203) and scoring.assemble_candidates on the table of adh_select_candidates_resident, on
+ * the device.  A row is kept when score > 0 and, with apply_cutoff, score > score_cutoff - compared in float64, so
+ * the caller rounds the cutoff to the dtype NumPy compares a float32 column with it in.  The kept rows, in
+ * (precursor, slot) order, are checked for (elution_group_idx, decoy, rank, precursor_idx) order and, where they are
+ * not in it, brought into the order of np.lexsort((precursor_idx, rank, decoy, elution_group_idx)) by stable radix
+ * passes.  score_group_idx is the row number, or with score_grouped the running count of (elution_group_idx, decoy,
+ * rank) changes; a precursor_idx twice in a row of one group is ADH_ERR_INVALID_ARGUMENT ("precursor_idx must be unique
+ * within a score group").  With reference_channel >= 0 the rows of groups without a row of that channel get
+ * ADH_FLAG_SKIP.  One gather kernel writes the candidate columns of adh_upload_candidates into the handle's candidate
+ * slab.  n_selected: rows with score > 0; n_kept: rows of the assembled table; was_sorted: 1 when no sort ran.  May be
+ * called again on the same selection (another cutoff).  ADH_ERR_NOT_STAGED without a resident selection.
+ */
+int adh_assemble_selected(adh_handle_t *handle, int32_t apply_cutoff, double score_cutoff, int32_t score_grouped,
+                          int32_t reference_channel, int64_t *n_selected, int64_t *n_kept, int32_t *was_sorted);
+
+/* What the last adh_assemble_selected did: stats[4] = was_sorted, radix passes, score-group scans, rows flagged
+ * ADH_FLAG_SKIP; assemble_ms (may be NULL): HIP-event time from its first kernel to its last. */
+int adh_select_handover_stats(adh_handle_t *handle, int32_t *stats, double *assemble_ms);
+
+/*
+ * adh_score_candidates_resident on the table adh_assemble_selected left in the candidate slab: the same plan build,
+ * kernel classes and device tables, nothing uploaded and nothing copied back.  ADH_ERR_NOT_STAGED when that table is
+ * gone (another scoring or staging call since), ADH_ERR_UNSUPPORTED with a communicator attached.
+ */
+int adh_score_selected_resident(adh_handle_t *handle, const adh_scoring_config_t *config);
+
+/* Per row of the assembled table, in its order: the row in the selection table (precursor row = table_row /
+ * candidate_count) and the rank.  n must be n_kept.  5 bytes per row cross PCIe. */
+int adh_selected_ids(adh_handle_t *handle, uint32_t *table_row, uint8_t *rank, int64_t n);
+
+/*
+ * The nine candidate columns of the listed rows of the assembled table (out->n == n), in list order, and - where
+ * selected_pos is not NULL - the position of each among the rows with score > 0 (the index label the host's frame
+ * gives it).  Errors as adh_take_rows: a row outside the table is ADH_ERR_INVALID_ARGUMENT, no assembled table
+ * ADH_ERR_NOT_STAGED.
+ */
+int adh_take_selected(adh_handle_t *handle, const int64_t *rows, int64_t n, adh_candidate_table_t *out,
+                      uint32_t *selected_pos);
+
 /* ------------------------------------------------------------------------------------------
  * FDR stage: alphadia/fdr/fdr.py + alphadia/fdr/classifiers.py.
  * ------------------------------------------------------------------------------------------ */
