@@ -810,6 +810,59 @@ STAGE_LIB_PROTOTYPES = {
 }
 
 
+# ... and of the candidate library of transfer-library requantification built in HBM (adh_candidate_library.hip)
+CANDIDATE_LIBRARY_MAX_SERIES = 64
+CANDIDATE_LIBRARY_MAX_NAA = 255
+
+
+class CandidateLibrary(C.Structure):
+    _fields_ = [
+        ("n", C.c_int64),
+        ("seq_offset", _i64p),
+        ("residues", _u8p),
+        ("mod_offset", _i64p),
+        ("mod_site", C.POINTER(C.c_int32)),
+        ("mod_mass", C.POINTER(C.c_double)),
+        ("aa_mass", C.POINTER(C.c_double)),
+        ("mass_proton", C.c_double),
+        ("mass_h2o", C.c_double),
+        ("n_series", C.c_int32),
+        ("series_type", _u8p),
+        ("series_from_nterm", _u8p),
+        ("series_charge", _u8p),
+    ]
+
+
+def pack_candidate_library(seq_offset, residues, mod_offset, mod_site, mod_mass, aa_mass, mass_proton, mass_h2o,
+                           series_type, series_from_nterm, series_charge) -> Marshalled:
+    """``adh_candidate_library_t`` from the arrays of ``transfer_requantification.candidate_library_tables``.  Only the
+    shapes are checked here: what the values may be is the C side's to say."""
+    so, mo = as_c(seq_offset, np.int64), as_c(mod_offset, np.int64)
+    res, site, mass = as_c(residues, np.uint8), as_c(mod_site, np.int32), as_c(mod_mass, np.float64)
+    aa = as_c(aa_mass, np.float64)
+    series = [as_c(a, np.uint8) for a in (series_type, series_from_nterm, series_charge)]
+    if so.ndim != 1 or so.shape[0] < 1 or mo.shape != so.shape:
+        raise ValueError("seq_offset and mod_offset must have one entry per precursor and one more")
+    if aa.shape != (128,):
+        raise ValueError("aa_mass must have 128 entries")
+    if site.shape != mass.shape or site.ndim != 1:
+        raise ValueError("mod_site and mod_mass differ in length")
+    if res.shape[0] < int(so[-1]) or site.shape[0] < int(mo[-1]):
+        raise ValueError("offsets point past the end of residues / mod_site")
+    if any(a.shape != series[0].shape or a.ndim != 1 for a in series):
+        raise ValueError("series columns differ in length")
+    s = CandidateLibrary(so.shape[0] - 1, _ptr(so, C.c_int64), _ptr(res, C.c_uint8), _ptr(mo, C.c_int64),
+                         _ptr(site, C.c_int32), _ptr(mass, C.c_double), _ptr(aa, C.c_double), float(mass_proton),
+                         float(mass_h2o), series[0].shape[0], *[_ptr(a, C.c_uint8) for a in series])
+    return Marshalled(s, [so, res, mo, site, mass, aa, *series])
+
+
+CANDIDATE_LIBRARY_PROTOTYPES = {
+    "adh_stage_candidate_library": [C.c_void_p, C.POINTER(CandidateLibrary), C.POINTER(LoessModel), _u32p, _u32p, _f32p,
+                                    C.POINTER(C.c_double)],
+}
+
+
 # ... and of the per-class candidate counts of the launched plans (the class table in include/alphadia_hip.h)
 N_PLAN_CLASSES = 37
 # launch groups of the generic class (small layouts, layouts up to the LDS of a CU, the spill path): adh_generic_launch_stats
@@ -825,9 +878,11 @@ PLAN_PROTOTYPES = {
 
 def declare(lib) -> None:
     """Argument types of the entries listed in RESIDENT_PROTOTYPES, HANDOVER_PROTOTYPES, STAGE_PART_PROTOTYPES, APPEND_PROTOTYPES,
-    QUANT_PROTOTYPES, PG_PROTOTYPES, PFDR_PROTOTYPES, TL_PROTOTYPES, MBR_PROTOTYPES, STAGE_LIB_PROTOTYPES and PLAN_PROTOTYPES (the others are called with explicit casts)."""
+    QUANT_PROTOTYPES, PG_PROTOTYPES, PFDR_PROTOTYPES, TL_PROTOTYPES, MBR_PROTOTYPES, STAGE_LIB_PROTOTYPES,
+    CANDIDATE_LIBRARY_PROTOTYPES and PLAN_PROTOTYPES (the others are called with explicit casts)."""
     for name, argtypes in {**RESIDENT_PROTOTYPES, **HANDOVER_PROTOTYPES, **STAGE_PART_PROTOTYPES, **APPEND_PROTOTYPES, **QUANT_PROTOTYPES,
-                           **PG_PROTOTYPES, **PFDR_PROTOTYPES, **TL_PROTOTYPES, **MBR_PROTOTYPES, **STAGE_LIB_PROTOTYPES, **PLAN_PROTOTYPES}.items():
+                           **PG_PROTOTYPES, **PFDR_PROTOTYPES, **TL_PROTOTYPES, **MBR_PROTOTYPES, **STAGE_LIB_PROTOTYPES,
+                           **CANDIDATE_LIBRARY_PROTOTYPES, **PLAN_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = C.c_int

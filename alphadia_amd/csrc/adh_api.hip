@@ -2098,6 +2098,7 @@ int adh_fragcomp_stats(adh_handle_t *h, double *kernel_ms, int64_t *pairs, int64
 #include "adh_fdr_device.hip"
 #include "adh_calibration.hip"
 #include "adh_stage_lib.hip"
+#include "adh_candidate_library.hip"
 #include "adh_take_rows.hip"
 #include "adh_resident_append.hip"
 #include "adh_session.h"  // behind fail, HIP_TRY and the hipMalloc / hipFree macros: its allocations go through the block cache

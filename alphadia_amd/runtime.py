@@ -140,6 +140,7 @@ EXPORTED_SYMBOLS = [
     "adh_score_selected_resident",
     "adh_selected_ids",
     "adh_take_selected",
+    "adh_stage_candidate_library",
 ]
 
 
@@ -827,6 +828,36 @@ class Context:
                "adh_stage_fragments_columns")
         self._staged_library(columns, m.struct.n, None)
         return y
+
+    def stage_candidate_library(self, tables, model=None):
+        """``adh_stage_candidate_library``: build and stage the library of all fragment series of the precursors in
+        ``tables`` (a ``Marshalled`` ``adh_candidate_library_t``, ``_abi.pack_candidate_library``) in HBM, with ``mz``
+        = float32 of the fitted ``model`` over ``mz_library`` when one is given.  Returns ``(flat_frag_start_idx,
+        flat_frag_stop_idx, mz_library, mz_calibrated)``: uint32 per precursor, float32 and float64 (None without a
+        model) per row.  The staged library then equals no host column set: ``adopt_fragment_columns`` names one.  A
+        refused table leaves the staged library and its bookkeeping as they were."""
+        packed = _abi.pack_loess_model(model.scale_mean, model.scale_max, model.beta) if model is not None else None
+        st = tables.struct
+        n = int(st.n)
+        offsets = np.ctypeslib.as_array(st.seq_offset, shape=(n + 1,))
+        # (the row count the C side will arrive at, for the output columns; a table it refuses writes nothing)
+        total = int((np.diff(offsets) - 1).sum()) * int(st.n_series) if n else 0
+        if not 0 <= total < 0xFFFFFFFF or (n and int(np.diff(offsets).min()) < 2):
+            total = 0
+        start, stop = np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.uint32)
+        mz_library = np.empty(total, dtype=np.float32)
+        y = np.empty(total, dtype=np.float64) if packed is not None else None
+        rc = lib.adh_stage_candidate_library(
+            self._h, tables.ref(), C.byref(packed) if packed is not None else None, start.ctypes.data_as(_abi._u32p),
+            stop.ctypes.data_as(_abi._u32p), mz_library.ctypes.data_as(_abi._f32p),
+            y.ctypes.data_as(C.POINTER(C.c_double)) if y is not None else None)
+        if rc in (-1, -4):  # ADH_ERR_INVALID_ARGUMENT, ADH_ERR_UNSUPPORTED: refused before anything was touched
+            _check(rc, "adh_stage_candidate_library")
+        self._lib_key = None
+        self.select_serial += 1
+        _check(rc, "adh_stage_candidate_library")
+        self._staged_library((mz_library,), total, None)
+        return start, stop, mz_library, y
 
     def calibrate_staged_fragments(self, model) -> np.ndarray:
         """``adh_calibrate_staged_fragments``: rewrite ``mz`` of the staged library, in HBM, as float32 of the fitted

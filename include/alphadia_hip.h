@@ -865,8 +865,8 @@ typedef struct adh_loess_model {
  */
 int adh_calibration_predict(adh_handle_t *handle, const adh_loess_model_t *model, const void *x, int32_t x_is_f64,
                             int64_t n, double *y);
-/* Summed HIP-event duration (ms) of the kernels of the last adh_calibration_predict, adh_calibrate_staged_fragments
- * or adh_stage_fragments_columns call. */
+/* Summed HIP-event duration (ms) of the kernels of the last adh_calibration_predict, adh_calibrate_staged_fragments,
+ * adh_stage_fragments_columns or adh_stage_candidate_library call. */
 int adh_calibration_time_ms(adh_handle_t *handle, double *kernel_ms);
 
 /*
@@ -892,6 +892,48 @@ int adh_calibrate_staged_fragments(adh_handle_t *handle, const adh_loess_model_t
  */
 int adh_stage_fragments_columns(adh_handle_t *handle, const adh_fragments_t *fragments, const adh_loess_model_t *model,
                                 double *mz_out);
+
+/*
+ * The candidate library of transfer-library requantification (_build_candidate_speclib_flat,
+ * workflow/peptidecentric/transfer_library_requantification_handler.py:140-240), built in HBM from the identified
+ * precursors themselves: sequence bytes, modification lists and the mass tables go up (a few dozen bytes per
+ * precursor), a kernel writes the records of all fragment series at every position.  Strings stay with the caller.
+ */
+#define ADH_CANDIDATE_LIBRARY_MAX_SERIES 64
+typedef struct adh_candidate_library {
+    int64_t n;                        /* precursors */
+    const int64_t *seq_offset;        /* [n + 1] into residues; L = nAA = the difference */
+    const uint8_t *residues;          /* ASCII, every byte < 128 */
+    const int64_t *mod_offset;        /* [n + 1] into mod_site / mod_mass, in list order */
+    const int32_t *mod_site;          /* 0: residue 0 (N-terminal), -1: residue L-1 (C-terminal), s >= 1: residue s-1 */
+    const double *mod_mass;
+    const double *aa_mass;            /* [128] mass of a residue byte */
+    double mass_proton;
+    double mass_h2o;
+    int32_t n_series;                 /* 1 .. ADH_CANDIDATE_LIBRARY_MAX_SERIES charged fragment types, in column order */
+    const uint8_t *series_type;       /* [n_series] code point of the letter: 98 'b', 121 'y' */
+    const uint8_t *series_from_nterm; /* [n_series] 1: the ion holds the N-terminus (a, b, c), 0: the C-terminus (x, y, z) */
+    const uint8_t *series_charge;     /* [n_series] */
+} adh_candidate_library_t;
+
+/*
+ * Precursor p with L residues: m[j] = aa_mass[residue j] plus the masses of its modifications in list order;
+ * B[i] = m[0] + ... + m[i] in float64, summed left to right (np.cumsum); pep = B[L-1] + mass_h2o; Y[i] = pep - B[i].
+ * It owns (L-1) * n_series consecutive rows, position-major: row i * n_series + s has
+ * mz_library = float32((from_nterm ? B[i] : Y[i]) / charge_s + mass_proton), intensity 1, type series_type[s],
+ * loss_type 0, charge series_charge[s], number = from_nterm ? i+1 : L-1-i, position i, cardinality 0.
+ * flat_frag_start_idx / flat_frag_stop_idx [n]: the exclusive scan of the row counts in input order.  model != NULL:
+ * mz = float32 of the model over mz_library, the row evaluation of adh_calibrate_staged_fragments, and mz_out (may be
+ * NULL) receives the float64 predictions; model == NULL: mz = mz_library and mz_out is not written.  mz_library_out
+ * (may be NULL) receives the float32 column.  Both have one entry per row.
+ * ADH_ERR_INVALID_ARGUMENT, before anything is staged or written: L < 2, L > 255 (number and position are uint8), a
+ * residue byte >= 128, a modification site outside [-1, L], n_series = 0, 2^32 - 1 rows or more.  n = 0 stages an
+ * empty library.  Effects on the handle as adh_stage_fragments; the host copy of the records is rebuilt by the host
+ * team (adh_host_threads) from the same sums in the same order.  adh_calibration_time_ms covers the call's kernels.
+ */
+int adh_stage_candidate_library(adh_handle_t *handle, const adh_candidate_library_t *library,
+                                const adh_loess_model_t *model, uint32_t *flat_frag_start_idx,
+                                uint32_t *flat_frag_stop_idx, float *mz_library_out, double *mz_out);
 
 /*
  * For tests and tools: the raw 32-byte records of the staged library, from HBM (host_mirror = 0) or from the
