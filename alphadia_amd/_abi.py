@@ -1,6 +1,7 @@
-"""ctypes mirror of ``include/alphadia_hip.h`` (struct layouts + array marshalling).
+"""ctypes mirror of ``include/alphadia_hip.h``: the struct layouts, the array marshalling and ``PROTOTYPES``, the one
+table of every export's ``restype`` and ``argtypes`` that ``declare`` applies to a loaded library.
 
-Pure data-layout code: no compute happens here.
+Pure data-layout code: no compute happens here, and the library is not loaded here.
 """
 
 from __future__ import annotations
@@ -14,9 +15,13 @@ FLAG_SKIP = 1
 
 _f32p = C.POINTER(C.c_float)
 _f64p = C.POINTER(C.c_double)
+_i32p = C.POINTER(C.c_int32)
 _i64p = C.POINTER(C.c_int64)
+_u64p = C.POINTER(C.c_uint64)
 _u32p = C.POINTER(C.c_uint32)
+_u16p = C.POINTER(C.c_uint16)
 _u8p = C.POINTER(C.c_uint8)
+_f32pp = C.POINTER(_f32p)
 
 
 class AlphaRaw(C.Structure):
@@ -202,8 +207,11 @@ OUTPUT_FIELDS = [
 ]
 
 
-def _ptr(a: np.ndarray, ctype):
-    return a.ctypes.data_as(C.POINTER(ctype))
+def ptr(a, ctype=None):
+    """The data of array ``a`` as a ``POINTER(ctype)`` argument (``void *`` without a ctype); None stays NULL."""
+    if a is None:
+        return None
+    return a.ctypes.data_as(C.POINTER(ctype) if ctype is not None else C.c_void_p)
 
 
 _CT = {
@@ -251,17 +259,17 @@ def pack_alpharaw(dia) -> Marshalled:
     if mz.shape != it.shape:
         raise ValueError("mz_values and intensity_values differ in length")
     s = AlphaRaw(
-        _ptr(cycle, C.c_double),
+        ptr(cycle, C.c_double),
         cycle.shape[1],
         cycle.shape[2],
-        _ptr(rt, C.c_float),
+        ptr(rt, C.c_float),
         rt.shape[0],
-        _ptr(mob, C.c_float),
+        ptr(mob, C.c_float),
         mob.shape[0],
-        _ptr(ps, C.c_int64),
-        _ptr(pe, C.c_int64),
-        _ptr(mz, C.c_float),
-        _ptr(it, C.c_float),
+        ptr(ps, C.c_int64),
+        ptr(pe, C.c_int64),
+        ptr(mz, C.c_float),
+        ptr(it, C.c_float),
         mz.shape[0],
     )
     return Marshalled(s, [cycle, rt, mob, ps, pe, mz, it])
@@ -278,20 +286,20 @@ def pack_timstof(dia) -> Marshalled:
     rt = as_c(dia.rt_values, np.float64)
     mob = as_c(dia.mobility_values, np.float64)
     mz = as_c(dia.mz_values, np.float64)
-    ptr = as_c(dia.tof_indptr, np.int64)
+    indptr = as_c(dia.tof_indptr, np.int64)
     push = as_c(dia.push_indices, np.uint32)
     inten = np.ascontiguousarray(dia.intensity_values, dtype=np.uint16)
     if dpc.shape[0] != cycle.shape[1] * cycle.shape[2]:
         raise ValueError("dia_precursor_cycle must have one entry per (frame, scan) of the cycle")
-    if ptr.shape[0] != mz.shape[0] + 1 or push.shape != inten.shape:
+    if indptr.shape[0] != mz.shape[0] + 1 or push.shape != inten.shape:
         raise ValueError("inconsistent TOF index arrays")
     s = TimsTOF(
-        _ptr(cycle, C.c_double), cycle.shape[1], cycle.shape[2], _ptr(dpc, C.c_int64),
-        _ptr(rt, C.c_double), rt.shape[0], _ptr(mob, C.c_double), _ptr(mz, C.c_double), mz.shape[0],
-        _ptr(ptr, C.c_int64), _ptr(push, C.c_uint32), inten.ctypes.data_as(C.POINTER(C.c_uint16)),
+        ptr(cycle, C.c_double), cycle.shape[1], cycle.shape[2], ptr(dpc, C.c_int64),
+        ptr(rt, C.c_double), rt.shape[0], ptr(mob, C.c_double), ptr(mz, C.c_double), mz.shape[0],
+        ptr(indptr, C.c_int64), ptr(push, C.c_uint32), ptr(inten, C.c_uint16),
         push.shape[0], int(bool(dia.zeroth_frame)),
     )
-    return Marshalled(s, [cycle, dpc, rt, mob, mz, ptr, push, inten])
+    return Marshalled(s, [cycle, dpc, rt, mob, mz, indptr, push, inten])
 
 
 def pack_fragments(mz_library, mz, intensity, type_, loss_type, charge, number, position, cardinality):
@@ -302,8 +310,8 @@ def pack_fragments(mz_library, mz, intensity, type_, loss_type, charge, number, 
         raise ValueError("fragment columns differ in length")
     s = Fragments(
         n,
-        *[_ptr(a, C.c_float) for a in arrs[:3]],
-        *[_ptr(a, C.c_uint8) for a in arrs[3:]],
+        *[ptr(a, C.c_float) for a in arrs[:3]],
+        *[ptr(a, C.c_uint8) for a in arrs[3:]],
     )
     return Marshalled(s, arrs)
 
@@ -327,7 +335,7 @@ def pack_fragments_calibrated(mz_library, intensity, type_, loss_type, charge, n
     n = arrs[0].shape[0]
     if any(a.shape != (n,) for a in arrs):
         raise ValueError("fragment columns differ in length")
-    s = Fragments(n, _ptr(arrs[0], C.c_float), None, _ptr(arrs[1], C.c_float), *[_ptr(a, C.c_uint8) for a in arrs[2:]])
+    s = Fragments(n, ptr(arrs[0], C.c_float), None, ptr(arrs[1], C.c_float), *[ptr(a, C.c_uint8) for a in arrs[2:]])
     return Marshalled(s, arrs)
 
 
@@ -369,15 +377,15 @@ def pack_candidates(
             raise ValueError("candidate columns differ in length")
     s = Candidates(
         n,
-        _ptr(pi, C.c_uint32),
-        _ptr(rk, C.c_uint8),
-        _ptr(fl, C.c_uint8) if fl is not None else None,
-        _ptr(fs, C.c_uint32),
-        _ptr(fe, C.c_uint32),
-        *[_ptr(a, C.c_int64) for a in i64],
-        _ptr(ch, C.c_uint8),
-        _ptr(pm, C.c_float),
-        _ptr(iso, C.c_float),
+        ptr(pi, C.c_uint32),
+        ptr(rk, C.c_uint8),
+        ptr(fl, C.c_uint8),
+        ptr(fs, C.c_uint32),
+        ptr(fe, C.c_uint32),
+        *[ptr(a, C.c_int64) for a in i64],
+        ptr(ch, C.c_uint8),
+        ptr(pm, C.c_float),
+        ptr(iso, C.c_float),
         iso.shape[1],
     )
     return Marshalled(s, [pi, rk, fl, fs, fe, *i64, ch, pm, iso])
@@ -438,9 +446,9 @@ def alloc_output(n: int, top_k: int, with_stats: bool = False, zero: bool = True
     s = Output(
         n,
         top_k,
-        *[_ptr(arrays[name], _CT[np.dtype(dt)]) for name, dt, _ in OUTPUT_FIELDS],
-        _ptr(stats, C.c_uint32) if stats is not None else None,
-        _ptr(slots, C.c_uint16) if slots is not None else None,
+        *[ptr(arrays[name], _CT[np.dtype(dt)]) for name, dt, _ in OUTPUT_FIELDS],
+        ptr(stats, C.c_uint32),
+        ptr(slots, C.c_uint16),
     )
     if stats is not None:
         arrays["stat_matched_peaks"] = stats
@@ -565,8 +573,8 @@ def pack_precursors(precursor_idx, frag_start_idx, frag_stop_idx, charge, rt, mo
     n = u32[0].shape[0]
     if any(a.shape != (n,) for a in u32 + [ch] + f32) or iso.shape[0] != n:
         raise ValueError("precursor columns differ in length")
-    s = Precursors(n, *[_ptr(a, C.c_uint32) for a in u32], _ptr(ch, C.c_uint8),
-                   *[_ptr(a, C.c_float) for a in f32], _ptr(iso, C.c_float), iso.shape[1])
+    s = Precursors(n, *[ptr(a, C.c_uint32) for a in u32], ptr(ch, C.c_uint8),
+                   *[ptr(a, C.c_float) for a in f32], ptr(iso, C.c_float), iso.shape[1])
     return Marshalled(s, u32 + [ch] + f32 + [iso])
 
 
@@ -594,7 +602,7 @@ def pack_selection_config(cfg) -> SelectionConfig:
 
 def alloc_candidate_table(n_rows: int):
     arrays = {name: np.zeros(n_rows, dtype=dt) for name, dt in CANDIDATE_TABLE_FIELDS}
-    s = CandidateTable(n_rows, *[_ptr(arrays[name], _CT[np.dtype(dt)]) for name, dt in CANDIDATE_TABLE_FIELDS])
+    s = CandidateTable(n_rows, *[ptr(arrays[name], _CT[np.dtype(dt)]) for name, dt in CANDIDATE_TABLE_FIELDS])
     return Marshalled(s, arrays), arrays
 
 
@@ -680,141 +688,20 @@ def pack_loess_model(scale_mean, scale_max, beta) -> LoessModel:
     return m
 
 
-# ctypes prototypes of the resident-extraction entries (include/alphadia_hip.h); tests/ compares them with the header
-RESIDENT_PROTOTYPES = {
-    "adh_score_candidates_resident": [C.c_void_p, C.c_void_p, C.c_void_p],
-    "adh_take_rows": [C.c_void_p, C.POINTER(C.c_int64), C.c_int64, C.POINTER(CompactOutput)],
-}
-
-
-# ... of the selection -> scoring hand-over in HBM (adh_select_handover.hip)
-HANDOVER_PROTOTYPES = {
-    "adh_select_candidates_resident": [C.c_void_p, C.POINTER(Precursors), C.POINTER(SelectionConfig), C.POINTER(C.c_float),
-                                       C.c_int32, C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8),
-                                       C.POINTER(C.c_uint8)],
-    "adh_assemble_selected": [C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.POINTER(C.c_int64),
-                              C.POINTER(C.c_int64), C.POINTER(C.c_int32)],
-    "adh_select_handover_stats": [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)],
-    "adh_score_selected_resident": [C.c_void_p, C.c_void_p],
-    "adh_selected_ids": [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.c_int64],
-    "adh_take_selected": [C.c_void_p, C.POINTER(C.c_int64), C.c_int64, C.POINTER(CandidateTable), C.POINTER(C.c_uint32)],
-}
-
-
-# ... of the staging of one part of a channel-wise decoy strategy
-_f32pp = C.POINTER(C.POINTER(C.c_float))
-STAGE_PART_PROTOTYPES = {
-    "adh_mlp_stage_rows_device_part": [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, _f32pp, C.c_int32,
-                                       C.POINTER(C.c_uint8), C.c_int64, C.POINTER(C.c_int64), C.c_int64, C.c_int64,
-                                       C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
-}
-
-
-# ... and of the accumulated resident tables (the optimisation loop)
-APPEND_PROTOTYPES = {
-    "adh_score_candidates_resident_append": [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)],
-    "adh_resident_reset": [C.c_void_p],
-    "adh_resident_counts": [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
-}
-
-
-# ... and of the cross-run fragment quantity matrices (adh_quant_*)
+# limits the header states as #defines (tests/ compares them with the header)
 QUANT_MAX_COLUMNS = 16
-_u8p, _u32p, _f32p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_float)
-QUANT_PROTOTYPES = {
-    "adh_quant_create": [C.c_void_p, C.c_int32, _u32p, C.c_int64, C.POINTER(C.c_void_p)],
-    "adh_quant_destroy": [C.c_void_p],
-    "adh_quant_add_run": [C.c_void_p, C.c_int64, _u32p, _u8p, _u8p, _u8p, _u8p, C.POINTER(_f32p),
-                          C.POINTER(C.c_int64)],
-    "adh_quant_build": [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)],
-    "adh_quant_keys": [C.c_void_p, _i64p, _u32p],
-    "adh_quant_matrix": [C.c_void_p, C.c_int32, _f32p],
-    "adh_quant_rows": [C.c_void_p, _i64p, _u32p, _u32p, C.POINTER(_f32p)],
-    "adh_quant_set_matrix": [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(_f32p)],
-    "adh_quant_filter": [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_double, C.c_double, _f32p,
-                         C.POINTER(C.c_double), _u8p],
-    "adh_quant_time_ms": [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)],
-}
-
-
-# ... and of protein inference (adh_pg_*, adh_grouping.hip)
-_i32p = C.POINTER(C.c_int32)
-PG_PROTOTYPES = {
-    "adh_pg_create": [C.c_void_p, C.POINTER(C.c_void_p)],
-    "adh_pg_destroy": [C.c_void_p],
-    "adh_pg_solve": [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, _i32p, _i32p, _i32p, _i32p, _i32p],
-    "adh_pg_filter": [C.c_void_p, C.c_int32, _i32p, _i32p, _i32p, _i32p, C.POINTER(C.c_int64)],
-    "adh_pg_stats": [C.c_void_p, _i32p, _i32p, _i32p],
-    "adh_pg_time_ms": [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)],
-}
-
-
-# ... and of the protein-group FDR (adh_pfdr_*, adh_protein_fdr.hip)
-_f64p = C.POINTER(C.c_double)
-PFDR_PROTOTYPES = {
-    "adh_pfdr_create": [C.c_void_p, C.POINTER(C.c_void_p)],
-    "adh_pfdr_destroy": [C.c_void_p],
-    "adh_pfdr_features": [C.c_void_p, C.c_int64, _i32p, C.POINTER(C.c_uint8), C.POINTER(C.c_int64), _i32p, _i32p,
-                          C.c_void_p, C.c_int32, C.POINTER(C.c_int64)],
-    "adh_pfdr_read_features": [C.c_void_p, _i32p, C.POINTER(C.c_uint8), _f64p, _i32p],
-    "adh_pfdr_fit_begin": [C.c_void_p, C.c_int64, _f64p, C.POINTER(C.c_uint8), _f64p],
-    "adh_pfdr_epoch": [C.c_void_p, _i32p, C.c_int32, _f64p, _f64p],
-    "adh_pfdr_predict": [C.c_void_p, C.c_int64, _f64p, _f64p],
-    "adh_pfdr_gather": [C.c_void_p, C.c_int64, _f64p, _f64p],
-    "adh_pfdr_time_ms": [C.c_void_p, _f64p, _f64p, _f64p, _f64p],
-}
-
-
-# ... and of the transfer-learning library (adh_tl_*, adh_transfer_library.hip)
 TL_MAX_MATRICES = 4
 TL_QC_SLICE = 512
-TL_PROTOTYPES = {
-    "adh_tl_create": [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)],
-    "adh_tl_destroy": [C.c_void_p],
-    "adh_tl_scatter": [C.c_void_p, C.c_int64, C.c_int64, _i64p, _i32p, _f32p, _f32p, _f32p, _i32p],
-    "adh_tl_update": [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, _i64p, _i64p, _i64p,
-                      C.c_int64, C.POINTER(_f32p), _i64p, _i64p],
-    "adh_tl_read_kept": [C.c_void_p, _i64p, _i64p, _i64p],
-    "adh_tl_read_matrix": [C.c_void_p, C.c_int32, _f32p],
-    "adh_tl_time_ms": [C.c_void_p, _f64p, _f64p, _f64p],
-    "adh_tl_qc": [C.c_void_p, C.c_int64, _i64p, _i64p, C.c_int64, C.c_int32, _f32p, _f32p, C.c_float, C.c_float, C.c_int32,
-                  C.POINTER(C.c_uint8), _i64p, _f64p],
-    "adh_tl_rt_norm": [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
-                       C.c_void_p, _f64p],
-}
-
-# ... and of the match-between-runs library (adh_mbr_*, adh_mbr_library.hip)
-_u64p = C.POINTER(C.c_uint64)
-MBR_PROTOTYPES = {
-    "adh_mbr_create": [C.c_void_p, C.POINTER(C.c_void_p)],
-    "adh_mbr_destroy": [C.c_void_p],
-    "adh_mbr_aggregate": [C.c_void_p, C.c_int64, _f64p, _u8p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
-                          C.c_int32, _u8p, C.c_double, C.c_int32, _i64p, _i64p, _i64p, _i64p],
-    "adh_mbr_read_table": [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, _i64p],
-    "adh_mbr_filter": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, _i64p, _i64p, C.c_int64, C.c_int32, C.c_int32,
-                       C.POINTER(_f32p), _i64p, _i64p],
-    "adh_mbr_read_filter": [C.c_void_p, _i64p, _i64p, _i64p, _i64p],
-    "adh_mbr_read_matrix": [C.c_void_p, C.c_int32, _f32p],
-    "adh_mbr_assign": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, _i64p, _i64p],
-    "adh_mbr_index": [C.c_void_p, C.c_int64, _u64p, C.c_int64, _u64p, _i64p, C.POINTER(C.c_int32)],
-    "adh_mbr_notnull_objects": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint8), _i64p],
-    "adh_mbr_stats": [C.c_void_p, _f64p, _f64p, _f64p, _f64p, _u64p, _u64p],
-}
-
-
-# ... and of the library staged from its columns and calibrated in HBM (adh_stage_lib.hip, adh_calibration.hip)
-STAGE_LIB_PROTOTYPES = {
-    "adh_calibrate_staged_fragments": [C.c_void_p, C.POINTER(LoessModel), C.POINTER(C.c_double)],
-    "adh_stage_fragments_columns": [C.c_void_p, C.POINTER(Fragments), C.POINTER(LoessModel), C.POINTER(C.c_double)],
-    "adh_staged_fragments_read": [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64],
-}
-
-
-# ... and of the candidate library of transfer-library requantification built in HBM (adh_candidate_library.hip)
 CANDIDATE_LIBRARY_MAX_SERIES = 64
 CANDIDATE_LIBRARY_MAX_NAA = 255
+N_PLAN_CLASSES = 37  # the class table in include/alphadia_hip.h: adh_plan_class_counts
+# launch groups of the generic class (small layouts, layouts up to the LDS of a CU, the spill path): adh_generic_launch_stats
+N_GENERIC_GROUPS = 3
+# ... and of the dynamic route of the ion-mobility feature kernel: adh_im_launch_stats
+N_IM_GROUPS = 3
 
 
+# the candidate library of transfer-library requantification built in HBM (adh_candidate_library.hip)
 class CandidateLibrary(C.Structure):
     _fields_ = [
         ("n", C.c_int64),
@@ -851,38 +738,193 @@ def pack_candidate_library(seq_offset, residues, mod_offset, mod_site, mod_mass,
         raise ValueError("offsets point past the end of residues / mod_site")
     if any(a.shape != series[0].shape or a.ndim != 1 for a in series):
         raise ValueError("series columns differ in length")
-    s = CandidateLibrary(so.shape[0] - 1, _ptr(so, C.c_int64), _ptr(res, C.c_uint8), _ptr(mo, C.c_int64),
-                         _ptr(site, C.c_int32), _ptr(mass, C.c_double), _ptr(aa, C.c_double), float(mass_proton),
-                         float(mass_h2o), series[0].shape[0], *[_ptr(a, C.c_uint8) for a in series])
+    s = CandidateLibrary(so.shape[0] - 1, ptr(so, C.c_int64), ptr(res, C.c_uint8), ptr(mo, C.c_int64),
+                         ptr(site, C.c_int32), ptr(mass, C.c_double), ptr(aa, C.c_double), float(mass_proton),
+                         float(mass_h2o), series[0].shape[0], *[ptr(a, C.c_uint8) for a in series])
     return Marshalled(s, [so, res, mo, site, mass, aa, *series])
 
 
-CANDIDATE_LIBRARY_PROTOTYPES = {
-    "adh_stage_candidate_library": [C.c_void_p, C.POINTER(CandidateLibrary), C.POINTER(LoessModel), _u32p, _u32p, _f32p,
-                                    C.POINTER(C.c_double)],
+class TableField(C.Structure):
+    """adh_table_field_t: one column of the packed device buffer (adh_table_layout)."""
+
+    _fields_ = [("name", C.c_char * 40), ("offset", C.c_uint64), ("row_elems", C.c_uint32), ("elem_bytes", C.c_uint32),
+                ("wire", C.c_int32), ("reserved", C.c_int32)]
+
+
+# the header's name of every public struct that an export takes by pointer
+STRUCTS = {
+    "adh_alpharaw_t": AlphaRaw, "adh_timstof_t": TimsTOF, "adh_fragments_t": Fragments, "adh_candidates_t": Candidates,
+    "adh_scoring_config_t": ScoringConfig, "adh_output_t": Output, "adh_compact_output_t": CompactOutput,
+    "adh_table_field_t": TableField, "adh_precursors_t": Precursors, "adh_selection_config_t": SelectionConfig,
+    "adh_candidate_table_t": CandidateTable, "adh_mlp_arch_t": MlpArch, "adh_mlp_fit_t": MlpFit,
+    "adh_loess_model_t": LoessModel, "adh_candidate_library_t": CandidateLibrary,
 }
 
-
-# ... and of the per-class candidate counts of the launched plans (the class table in include/alphadia_hip.h)
-N_PLAN_CLASSES = 37
-# launch groups of the generic class (small layouts, layouts up to the LDS of a CU, the spill path): adh_generic_launch_stats
-N_GENERIC_GROUPS = 3
-# ... and of the dynamic route of the ion-mobility feature kernel: adh_im_launch_stats
-N_IM_GROUPS = 3
-PLAN_PROTOTYPES = {
-    "adh_plan_class_counts": [C.c_void_p, C.POINTER(C.c_int64), C.c_int32],
-    "adh_generic_launch_stats": [C.c_void_p, C.POINTER(C.c_int64), C.c_int32],
-    "adh_im_launch_stats": [C.c_void_p, C.POINTER(C.c_int64), C.c_int32],
+# Every export of include/alphadia_hip.h, in the header's order: name -> (restype, argtypes).  The header is the
+# authority: int / int32_t -> c_int32; int64_t, uint64_t, float, double -> the ctypes type of that name; a pointer to a
+# scalar -> POINTER of it; void * and the opaque handles (adh_handle_t *, adh_mlp_t *, ...) -> c_void_p, a pointer to
+# one of those -> POINTER(c_void_p); a pointer to a public struct -> POINTER of its class in STRUCTS.
+# tests/test_abi.py derives every entry from the header's text and compares type by type.
+_i32, _i64, _u64, _f32, _f64 = C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_double
+_vp, _vpp = C.c_void_p, C.POINTER(C.c_void_p)
+PROTOTYPES = {
+    # errors, devices, the per-GPU context
+    "adh_last_error": (C.c_char_p, []),
+    "adh_device_count": (_i32, [_i32p]),
+    "adh_create": (_i32, [_vpp, _i32]),
+    "adh_destroy": (_i32, [_vp]),
+    # staging of a run and of the fragment library
+    "adh_stage_alpharaw": (_i32, [_vp, C.POINTER(AlphaRaw)]),
+    "adh_stage_timstof": (_i32, [_vp, C.POINTER(TimsTOF)]),
+    "adh_stage_fragments": (_i32, [_vp, C.POINTER(Fragments)]),
+    # scoring: host to host, uploaded tables, resident and accumulated resident tables
+    "adh_score_candidates": (_i32, [_vp, C.POINTER(Candidates), C.POINTER(ScoringConfig), C.POINTER(Output)]),
+    "adh_score_candidates_compact": (_i32, [_vp, C.POINTER(Candidates), C.POINTER(ScoringConfig),
+                                            C.POINTER(CompactOutput)]),
+    "adh_upload_candidates": (_i32, [_vp, C.POINTER(Candidates)]),
+    "adh_score_uploaded": (_i32, [_vp, C.POINTER(ScoringConfig), C.POINTER(Output), _vp]),
+    "adh_get_device_tables": (_i32, [_vp, C.POINTER(Output)]),
+    "adh_score_candidates_resident": (_i32, [_vp, C.POINTER(Candidates), C.POINTER(ScoringConfig)]),
+    "adh_take_rows": (_i32, [_vp, _i64p, _i64, C.POINTER(CompactOutput)]),
+    "adh_score_candidates_resident_append": (_i32, [_vp, C.POINTER(Candidates), C.POINTER(ScoringConfig), _i64p]),
+    "adh_resident_reset": (_i32, [_vp]),
+    "adh_resident_counts": (_i32, [_vp, _i64p, _i64p]),
+    # table layout, page-locked host memory, the device cache
+    "adh_table_layout": (_i32, [_i64, _i32, _i32, C.POINTER(TableField), _i32p, _u64p, _u64p]),
+    "adh_zero_device_tables": (_i32, [_vp, _vp]),
+    "adh_host_alloc": (_i32, [_vpp, _u64]),
+    "adh_copy_to_host": (_i32, [_vp, _vp, _vp, _u64]),
+    "adh_host_free": (_i32, [_vp]),
+    "adh_trim_device_cache": (_i32, []),
+    # host helpers: thread budget, chunk boundaries, the object gather
+    "adh_host_threads": (_i32, [_i64, _i32p, _i32p]),
+    "adh_chunk_cuts": (_i32, [_i64, _i32, _i64, _i32, _i64p, _i64, _i64p]),
+    "adh_host_take_objects": (_i32, [_vpp, _vpp, _i64p, _i64, _i64, _vp, _i32]),
+    # test entry, stream, timers and launch counters
+    "adh_debug_get_dense": (_i32, [_vp, _i64, _i64, _i64, _i64, _f32p, _i32, _f32, _f32, _f32, _f32p, _i64, _i32p,
+                                   _i32p, _i32p, _i32p]),
+    "adh_get_stream": (_i32, [_vp, _vpp]),
+    "adh_synchronize": (_i32, [_vp]),
+    "adh_kernel_time_ms": (_i32, [_vp, _f64p, _f64p, _i64p, _i32]),
+    "adh_plan_class_counts": (_i32, [_vp, _i64p, _i32]),
+    "adh_generic_launch_stats": (_i32, [_vp, _i64p, _i32]),
+    "adh_im_launch_stats": (_i32, [_vp, _i64p, _i32]),
+    # multi-GPU (RCCL behind the ABI)
+    "adh_comm_unique_id": (_i32, [_vp]),
+    "adh_comm_init": (_i32, [_vp, _i32, _i32, _vp, _i64]),
+    "adh_comm_destroy": (_i32, [_vp]),
+    "adh_comm_wait": (_i32, [_vp]),
+    "adh_comm_gathered": (_i32, [_vp, _i32, C.POINTER(Output), _i64p]),
+    "adh_comm_all_reduce_max": (_i32, [_vp, _f64p]),
+    "adh_comm_barrier": (_i32, [_vp]),
+    "adh_comm_all_gather_host": (_i32, [_vp, _vp, _u64, _vp]),
+    "adh_comm_info": (_i32, [_vp, _i32p, _i32p]),
+    "adh_device_synchronize": (_i32, [_vp]),
+    # fragment competition
+    "adh_fragcomp": (_i32, [_vp, _i64, _i64p, _i64p, _i64, _f32p, _i64p, _i64p, _i64, _f32p, _f64, _f64, _u8p]),
+    "adh_fragcomp_frames": (_i32, [_vp, _i64, _u32p, _u8p, _f32p, _f32p, _f32p, _i64, _u32p, _u8p, _f32p, _i32, _f64p,
+                                   _f64p, _f64, _f64, _i64p, _u8p, _i64p, _i32p]),
+    "adh_fragcomp_stats": (_i32, [_vp, _f64p, _i64p, _i64p, _i32p, _i32p]),
+    # candidate selection, the timsTOF transpose
+    "adh_select_candidates": (_i32, [_vp, C.POINTER(Precursors), C.POINTER(SelectionConfig), _f32p, _i32, _i32,
+                                     C.POINTER(CandidateTable)]),
+    "adh_transpose_timstof": (_i32, [_vp, _u32p, _i64p, _i64, _i64, _u16p, _i64, _u32p, _i64p, _u16p]),
+    "adh_select_time_ms": (_i32, [_vp, _f64p]),
+    # selection -> scoring hand-over in HBM (adh_select_handover.hip)
+    "adh_select_candidates_resident": (_i32, [_vp, C.POINTER(Precursors), C.POINTER(SelectionConfig), _f32p, _i32, _i32,
+                                              _u32p, _u8p, _u8p]),
+    "adh_assemble_selected": (_i32, [_vp, _i32, _f64, _i32, _i32, _i64p, _i64p, _i32p]),
+    "adh_select_handover_stats": (_i32, [_vp, _i32p, _f64p]),
+    "adh_score_selected_resident": (_i32, [_vp, C.POINTER(ScoringConfig)]),
+    "adh_selected_ids": (_i32, [_vp, _u32p, _u8p, _i64]),
+    "adh_take_selected": (_i32, [_vp, _i64p, _i64, C.POINTER(CandidateTable), _u32p]),
+    # FDR stage: q-values, keep-best, the classifier (adh_mlp_*)
+    "adh_fdr_q_values": (_i32, [_vp, _i64, _f64p, _u8p, _i64p, _i64p, _f64p]),
+    "adh_fdr_keep_best": (_i32, [_vp, _i64, _f64p, _i64p, _i64p, _u8p]),
+    "adh_mlp_create": (_i32, [_vp, C.POINTER(MlpArch), _vpp]),
+    "adh_mlp_destroy": (_i32, [_vp]),
+    "adh_mlp_param_count": (_i32, [C.POINTER(MlpArch), _i64p]),
+    "adh_mlp_set_state": (_i32, [_vp, _f32p, _f32p, _f32p, _i64]),
+    "adh_mlp_get_state": (_i32, [_vp, _f32p, _f32p, _f32p, _i64p]),
+    "adh_mlp_stage_rows": (_i32, [_vp, _f32p, _i64, _i32, _f32p]),
+    "adh_mlp_fit": (_i32, [_vp, C.POINTER(MlpFit), _f32p]),
+    "adh_mlp_predict": (_i32, [_vp, _i64p, _i64, _f32p]),
+    "adh_mlp_time_ms": (_i32, [_vp, _f64p, _f64p]),
+    # FDR stage fed from the resident scoring tables
+    "adh_mlp_stage_rows_device": (_i32, [_vp, _i32p, _i32, _f32pp, _i32, _u8p, _i64, _i64p, _i64p]),
+    "adh_mlp_stage_rows_device_part": (_i32, [_vp, _i32p, _i32, _f32pp, _i32, _u8p, _i64, _i64p, _i64, _i64, _i32,
+                                              _i64p, _i64p]),
+    "adh_mlp_staged_rows": (_i32, [_vp, _i64p, _i64]),
+    "adh_mlp_predict_resident": (_i32, [_vp]),
+    "adh_fdr_resident": (_i32, [_vp, _vp, _i64p, _i64p, _i64p, _f64p, _i32, _i32, _f64, _f64, _f64, _i64p, _i64p, _f32p,
+                                _f64p]),
+    "adh_transfer_counters": (_i32, [_vp, _u64p, _i32]),
+    # library calibration, the library staged from its columns, the candidate library
+    "adh_calibration_predict": (_i32, [_vp, C.POINTER(LoessModel), _vp, _i32, _i64, _f64p]),
+    "adh_calibration_time_ms": (_i32, [_vp, _f64p]),
+    "adh_calibrate_staged_fragments": (_i32, [_vp, C.POINTER(LoessModel), _f64p]),
+    "adh_stage_fragments_columns": (_i32, [_vp, C.POINTER(Fragments), C.POINTER(LoessModel), _f64p]),
+    "adh_stage_candidate_library": (_i32, [_vp, C.POINTER(CandidateLibrary), C.POINTER(LoessModel), _u32p, _u32p, _f32p,
+                                           _f64p]),
+    "adh_staged_fragments_read": (_i32, [_vp, _i32, _vp, _i64]),
+    # cross-run fragment quantity matrices (adh_quant_*)
+    "adh_quant_create": (_i32, [_vp, _i32, _u32p, _i64, _vpp]),
+    "adh_quant_destroy": (_i32, [_vp]),
+    "adh_quant_add_run": (_i32, [_vp, _i64, _u32p, _u8p, _u8p, _u8p, _u8p, _f32pp, _i64p]),
+    "adh_quant_build": (_i32, [_vp, _i64p, _i32p]),
+    "adh_quant_keys": (_i32, [_vp, _i64p, _u32p]),
+    "adh_quant_matrix": (_i32, [_vp, _i32, _f32p]),
+    "adh_quant_rows": (_i32, [_vp, _i64p, _u32p, _u32p, _f32pp]),
+    "adh_quant_set_matrix": (_i32, [_vp, _i64, _i32, _f32pp]),
+    "adh_quant_filter": (_i32, [_vp, _i32, _i32p, _i32, _f64, _f64, _f32p, _f64p, _u8p]),
+    "adh_quant_time_ms": (_i32, [_vp, _f64p, _f64p]),
+    # protein inference (adh_pg_*)
+    "adh_pg_create": (_i32, [_vp, _vpp]),
+    "adh_pg_destroy": (_i32, [_vp]),
+    "adh_pg_solve": (_i32, [_vp, _i32, _i32, _i64, _i32p, _i32p, _i32p, _i32p, _i32p]),
+    "adh_pg_filter": (_i32, [_vp, _i32, _i32p, _i32p, _i32p, _i32p, _i64p]),
+    "adh_pg_stats": (_i32, [_vp, _i32p, _i32p, _i32p]),
+    "adh_pg_time_ms": (_i32, [_vp, _f64p, _f64p, _f64p]),
+    # protein-group FDR (adh_pfdr_*)
+    "adh_pfdr_create": (_i32, [_vp, _vpp]),
+    "adh_pfdr_destroy": (_i32, [_vp]),
+    "adh_pfdr_features": (_i32, [_vp, _i64, _i32p, _u8p, _i64p, _i32p, _i32p, _vp, _i32, _i64p]),
+    "adh_pfdr_read_features": (_i32, [_vp, _i32p, _u8p, _f64p, _i32p]),
+    "adh_pfdr_fit_begin": (_i32, [_vp, _i64, _f64p, _u8p, _f64p]),
+    "adh_pfdr_epoch": (_i32, [_vp, _i32p, _i32, _f64p, _f64p]),
+    "adh_pfdr_predict": (_i32, [_vp, _i64, _f64p, _f64p]),
+    "adh_pfdr_gather": (_i32, [_vp, _i64, _f64p, _f64p]),
+    "adh_pfdr_time_ms": (_i32, [_vp, _f64p, _f64p, _f64p, _f64p]),
+    # transfer-learning library (adh_tl_*)
+    "adh_tl_create": (_i32, [_vp, _i32, _i32, _vpp]),
+    "adh_tl_destroy": (_i32, [_vp]),
+    "adh_tl_scatter": (_i32, [_vp, _i64, _i64, _i64p, _i32p, _f32p, _f32p, _f32p, _i32p]),
+    "adh_tl_update": (_i32, [_vp, _i32, _i64, _vp, _i32, _vp, _i32, _i64p, _i64p, _i64p, _i64, _f32pp, _i64p, _i64p]),
+    "adh_tl_read_kept": (_i32, [_vp, _i64p, _i64p, _i64p]),
+    "adh_tl_read_matrix": (_i32, [_vp, _i32, _f32p]),
+    "adh_tl_time_ms": (_i32, [_vp, _f64p, _f64p, _f64p]),
+    "adh_tl_qc": (_i32, [_vp, _i64, _i64p, _i64p, _i64, _i32, _f32p, _f32p, _f32, _f32, _i32, _u8p, _i64p, _f64p]),
+    "adh_tl_rt_norm": (_i32, [_vp, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _f64p]),
+    # match-between-runs library (adh_mbr_*)
+    "adh_mbr_create": (_i32, [_vp, _vpp]),
+    "adh_mbr_destroy": (_i32, [_vp]),
+    "adh_mbr_aggregate": (_i32, [_vp, _i64, _f64p, _u8p, _vp, _i32, _vp, _i32, _vp, _i32, _u8p, _f64, _i32, _i64p,
+                                 _i64p, _i64p, _i64p]),
+    "adh_mbr_read_table": (_i32, [_vp, _i32, _vp, _vp, _i64p]),
+    "adh_mbr_filter": (_i32, [_vp, _i64, _vp, _i32, _i64p, _i64p, _i64, _i32, _i32, _f32pp, _i64p, _i64p]),
+    "adh_mbr_read_filter": (_i32, [_vp, _i64p, _i64p, _i64p, _i64p]),
+    "adh_mbr_read_matrix": (_i32, [_vp, _i32, _f32p]),
+    "adh_mbr_assign": (_i32, [_vp, _i64, _vp, _i32, _vp, _i32, _vp, _i64p, _i64p]),
+    "adh_mbr_index": (_i32, [_vp, _i64, _u64p, _i64, _u64p, _i64p, _i32p]),
+    "adh_mbr_notnull_objects": (_i32, [_vpp, _i64, _vp, _vp, _u8p, _i64p]),
+    "adh_mbr_stats": (_i32, [_vp, _f64p, _f64p, _f64p, _f64p, _u64p, _u64p]),
 }
 
 
 def declare(lib) -> None:
-    """Argument types of the entries listed in RESIDENT_PROTOTYPES, HANDOVER_PROTOTYPES, STAGE_PART_PROTOTYPES, APPEND_PROTOTYPES,
-    QUANT_PROTOTYPES, PG_PROTOTYPES, PFDR_PROTOTYPES, TL_PROTOTYPES, MBR_PROTOTYPES, STAGE_LIB_PROTOTYPES,
-    CANDIDATE_LIBRARY_PROTOTYPES and PLAN_PROTOTYPES (the others are called with explicit casts)."""
-    for name, argtypes in {**RESIDENT_PROTOTYPES, **HANDOVER_PROTOTYPES, **STAGE_PART_PROTOTYPES, **APPEND_PROTOTYPES, **QUANT_PROTOTYPES,
-                           **PG_PROTOTYPES, **PFDR_PROTOTYPES, **TL_PROTOTYPES, **MBR_PROTOTYPES, **STAGE_LIB_PROTOTYPES,
-                           **CANDIDATE_LIBRARY_PROTOTYPES, **PLAN_PROTOTYPES}.items():
+    """Set ``restype`` and ``argtypes`` of every export on ``lib`` (a ``CDLL`` or ``PyDLL`` of the library) from
+    PROTOTYPES.  Nothing else assigns them: a call that disagrees with the header raises ``ctypes.ArgumentError``."""
+    for name, (restype, argtypes) in PROTOTYPES.items():
         fn = getattr(lib, name)
+        fn.restype = restype
         fn.argtypes = argtypes
-        fn.restype = C.c_int

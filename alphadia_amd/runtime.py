@@ -1,5 +1,8 @@
 """ctypes binding of ``libalphadia_hip.so`` (the C ABI in include/alphadia_hip.h).
 
+Every export is declared once, by ``_abi.declare`` from ``_abi.PROTOTYPES``; the calls below pass plain Python
+numbers, ``_p(array, ctype)`` pointers and ``C.byref`` out-parameters, and ctypes converts and checks them.
+
 There is deliberately no fallback: importing this module without the built
 library, or creating a context without a GPU, raises.
 """
@@ -17,131 +20,7 @@ from alphadia_amd import _abi
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ADH_LIB_PATH") or os.path.join(_HERE, "libalphadia_hip.so")  # (developer switch: an experimental build)
 
-EXPORTED_SYMBOLS = [
-    "adh_last_error",
-    "adh_device_count",
-    "adh_create",
-    "adh_destroy",
-    "adh_stage_alpharaw",
-    "adh_stage_timstof",
-    "adh_stage_fragments",
-    "adh_score_candidates",
-    "adh_score_candidates_compact",
-    "adh_host_take_objects",
-    "adh_trim_device_cache",
-    "adh_host_threads",
-    "adh_chunk_cuts",
-    "adh_upload_candidates",
-    "adh_score_uploaded",
-    "adh_get_stream",
-    "adh_synchronize",
-    "adh_kernel_time_ms",
-    "adh_fragcomp",
-    "adh_fragcomp_stats",
-    "adh_fragcomp_frames",
-    "adh_select_candidates",
-    "adh_select_time_ms",
-    "adh_transpose_timstof",
-    "adh_fdr_q_values",
-    "adh_fdr_keep_best",
-    "adh_mlp_create",
-    "adh_mlp_destroy",
-    "adh_mlp_param_count",
-    "adh_mlp_set_state",
-    "adh_mlp_get_state",
-    "adh_mlp_stage_rows",
-    "adh_mlp_fit",
-    "adh_mlp_predict",
-    "adh_mlp_time_ms",
-    "adh_get_device_tables",
-    "adh_zero_device_tables",
-    "adh_debug_get_dense",
-    "adh_mlp_stage_rows_device",
-    "adh_mlp_stage_rows_device_part",
-    "adh_mlp_staged_rows",
-    "adh_mlp_predict_resident",
-    "adh_fdr_resident",
-    "adh_transfer_counters",
-    "adh_host_alloc",
-    "adh_host_free",
-    "adh_copy_to_host",
-    "adh_comm_unique_id",
-    "adh_comm_init",
-    "adh_comm_destroy",
-    "adh_comm_wait",
-    "adh_comm_gathered",
-    "adh_comm_all_reduce_max",
-    "adh_comm_barrier",
-    "adh_comm_all_gather_host",
-    "adh_comm_info",
-    "adh_table_layout",
-    "adh_device_synchronize",
-    "adh_calibration_predict",
-    "adh_calibration_time_ms",
-    "adh_score_candidates_resident",
-    "adh_take_rows",
-    "adh_score_candidates_resident_append",
-    "adh_resident_reset",
-    "adh_resident_counts",
-    "adh_quant_create",
-    "adh_quant_destroy",
-    "adh_quant_add_run",
-    "adh_quant_build",
-    "adh_quant_keys",
-    "adh_quant_matrix",
-    "adh_quant_rows",
-    "adh_quant_set_matrix",
-    "adh_quant_filter",
-    "adh_quant_time_ms",
-    "adh_calibrate_staged_fragments",
-    "adh_stage_fragments_columns",
-    "adh_staged_fragments_read",
-    "adh_plan_class_counts",
-    "adh_generic_launch_stats",
-    "adh_im_launch_stats",
-    "adh_pg_create",
-    "adh_pg_destroy",
-    "adh_pg_solve",
-    "adh_pg_filter",
-    "adh_pg_stats",
-    "adh_pg_time_ms",
-    "adh_pfdr_create",
-    "adh_pfdr_destroy",
-    "adh_pfdr_features",
-    "adh_pfdr_read_features",
-    "adh_pfdr_fit_begin",
-    "adh_pfdr_epoch",
-    "adh_pfdr_predict",
-    "adh_pfdr_gather",
-    "adh_pfdr_time_ms",
-    "adh_tl_create",
-    "adh_tl_destroy",
-    "adh_tl_scatter",
-    "adh_tl_update",
-    "adh_tl_read_kept",
-    "adh_tl_read_matrix",
-    "adh_tl_time_ms",
-    "adh_tl_qc",
-    "adh_tl_rt_norm",
-    "adh_mbr_create",
-    "adh_mbr_destroy",
-    "adh_mbr_aggregate",
-    "adh_mbr_read_table",
-    "adh_mbr_filter",
-    "adh_mbr_read_filter",
-    "adh_mbr_read_matrix",
-    "adh_mbr_assign",
-    "adh_mbr_index",
-    "adh_mbr_notnull_objects",
-    "adh_mbr_stats",
-    "adh_select_candidates_resident",
-    "adh_assemble_selected",
-    "adh_select_handover_stats",
-    "adh_score_selected_resident",
-    "adh_selected_ids",
-    "adh_take_selected",
-    "adh_stage_candidate_library",
-]
+EXPORTED_SYMBOLS = list(_abi.PROTOTYPES)  # every export of include/alphadia_hip.h, in the header's order
 
 
 def _process_start_time(pid: str | int = "self") -> float:
@@ -189,23 +68,19 @@ def _load():
             "g.build()'` (hipcc --offload-arch=gfx950). There is no CPU fallback."
         )
     lib = C.CDLL(LIB_PATH)
-    lib.adh_last_error.restype = C.c_char_p
-    for name in EXPORTED_SYMBOLS[1:]:
-        getattr(lib, name).restype = C.c_int
     _abi.declare(lib)
     return lib
 
 
 lib = _load()
+_p = _abi.ptr  # (array, ctype) -> the POINTER(ctype) argument of a native call; None stays NULL
 
 
 def host_threads(n_rows: int) -> tuple[int, int]:
     """(threads a scoring call over ``n_rows`` candidates starts on the host, CPU budget of this process): the
     library's ``adh_host_threads`` - cgroup quota, affinity mask, hardware threads; the rank's share of them."""
     t, b = C.c_int32(0), C.c_int32(0)
-    fn = lib.adh_host_threads
-    fn.argtypes = [C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-    _check(fn(int(n_rows), C.byref(t), C.byref(b)), "adh_host_threads")
+    _check(lib.adh_host_threads(int(n_rows), C.byref(t), C.byref(b)), "adh_host_threads")
     return int(t.value), int(b.value)
 
 
@@ -213,12 +88,11 @@ def chunk_cuts(n_rows: int, ion_mobility: bool = False, max_rows: int = 0, packe
     """Chunk boundaries of a host -> host scoring call over ``n_rows`` candidates (the library's ``adh_chunk_cuts``):
     chunk i is rows [cuts[i], cuts[i + 1]).  ``max_rows``: the call's bound on a chunk's rows (0: none); ``packed``:
     the compacted copy-out of the padded tables is in use.  Reads the ``ADH_CHUNK*`` switches; needs no GPU."""
-    fn = lib.adh_chunk_cuts
-    fn.argtypes = [C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64)]
+    args = (int(n_rows), int(ion_mobility), int(max_rows), int(packed))
     count = C.c_int64(0)
-    fn(int(n_rows), int(ion_mobility), int(max_rows), int(packed), None, 0, C.byref(count))  # (the size query)
+    lib.adh_chunk_cuts(*args, None, 0, C.byref(count))  # (the size query)
     cuts = (C.c_int64 * max(count.value, 1))()
-    _check(fn(int(n_rows), int(ion_mobility), int(max_rows), int(packed), cuts, len(cuts), C.byref(count)), "adh_chunk_cuts")
+    _check(lib.adh_chunk_cuts(*args, cuts, len(cuts), C.byref(count)), "adh_chunk_cuts")
     return list(cuts[: count.value])
 
 
@@ -244,16 +118,14 @@ def _probe_take_objects() -> bool:
         return False
     try:
         _pylib = C.PyDLL(LIB_PATH)
-        fn = _pylib.adh_host_take_objects
-        fn.restype = C.c_int
-        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32]
+        _abi.declare(_pylib)
         probe = object()
         src = np.empty(1, dtype=object)
         src[0] = probe
         idx = np.zeros(5, dtype=np.int64)
         dst = np.empty(5, dtype=object)
         before = sys.getrefcount(probe)
-        rc = fn(dst.ctypes.data, src.ctypes.data, idx.ctypes.data, 5, 1, id(None), 1)
+        rc = _pylib.adh_host_take_objects(_p(dst, C.c_void_p), _p(src, C.c_void_p), _p(idx, C.c_int64), 5, 1, id(None), 1)
         after = sys.getrefcount(probe)
         return rc == 0 and after - before == 5 and all(o is probe for o in dst)
     except Exception:
@@ -278,8 +150,8 @@ def take_objects(src: np.ndarray, idx: np.ndarray, threads: int = 8) -> np.ndarr
         return src[idx]
     idx64 = np.ascontiguousarray(idx, dtype=np.int64)
     dst = np.empty(len(idx64), dtype=object)
-    rc = _pylib.adh_host_take_objects(dst.ctypes.data, src.ctypes.data, idx64.ctypes.data, len(idx64), len(src), id(None),
-                                      int(threads))
+    rc = _pylib.adh_host_take_objects(_p(dst, C.c_void_p), _p(src, C.c_void_p), _p(idx64, C.c_int64), len(idx64), len(src),
+                                      id(None), int(threads))
     if rc != 0:  # (an index NumPy would wrap or reject: let NumPy decide; entries written so far are dropped with dst)
         return src[idx]
     return dst
@@ -300,7 +172,7 @@ def notnull_objects(a) -> np.ndarray:
     if not _OBJ_TAKE:
         return np.asarray(pd.notna(a))
     out, other = np.empty(len(a), np.uint8), C.c_int64(0)
-    _check(lib.adh_mbr_notnull_objects(a.ctypes.data, len(a), id(None), id(str), out.ctypes.data_as(C.POINTER(C.c_uint8)),
+    _check(lib.adh_mbr_notnull_objects(_p(a, C.c_void_p), len(a), id(None), id(str), _p(out, C.c_uint8),
                                        C.byref(other)), "adh_mbr_notnull_objects")
     if other.value:
         rest = np.flatnonzero(out == 2)
@@ -314,24 +186,24 @@ def _check(rc: int, what: str):
         raise HipBackendError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
 
 
-class _TableField(C.Structure):
-    _fields_ = [("name", C.c_char * 40), ("offset", C.c_uint64), ("row_elems", C.c_uint32), ("elem_bytes", C.c_uint32),
-                ("wire", C.c_int32), ("reserved", C.c_int32)]
-
-
 def table_layout(rows: int, top_k: int) -> tuple[list[dict], int, int]:
     """``adh_table_layout``: the packed device buffer of ``rows`` candidates as the library lays it out -
     (fields in buffer order, total bytes, bytes of the wire prefix).  Needs no GPU."""
     n = C.c_int32(0)
     total, wire = C.c_uint64(0), C.c_uint64(0)
-    _check(lib.adh_table_layout(C.c_int64(int(rows)), C.c_int32(int(top_k)), C.c_int32(0), None, C.byref(n),
-                                C.byref(total), C.byref(wire)), "adh_table_layout")
-    arr = (_TableField * n.value)()
-    _check(lib.adh_table_layout(C.c_int64(int(rows)), C.c_int32(int(top_k)), C.c_int32(n.value), arr, C.byref(n),
-                                C.byref(total), C.byref(wire)), "adh_table_layout")
+    _check(lib.adh_table_layout(int(rows), int(top_k), 0, None, C.byref(n), C.byref(total), C.byref(wire)),
+           "adh_table_layout")
+    arr = (_abi.TableField * n.value)()
+    _check(lib.adh_table_layout(int(rows), int(top_k), n.value, arr, C.byref(n), C.byref(total), C.byref(wire)),
+           "adh_table_layout")
     fields = [dict(name=f.name.decode(), offset=int(f.offset), row_elems=int(f.row_elems), elem_bytes=int(f.elem_bytes),
                    wire=bool(f.wire)) for f in arr]
     return fields, int(total.value), int(wire.value)
+
+
+def trim_device_cache() -> None:
+    """``adh_trim_device_cache``: give the device buffers the library keeps parked back to the runtime."""
+    _check(lib.adh_trim_device_cache(), "adh_trim_device_cache")
 
 
 def device_count() -> int:
@@ -357,11 +229,11 @@ class PinnedPool:
         ptr, cap = self._bufs.get(tag, (0, 0))
         if cap < nbytes or ptr == 0:
             if ptr:
-                lib.adh_host_free(C.c_void_p(ptr))
+                lib.adh_host_free(ptr)
                 self._bufs.pop(tag, None)
             want = max(nbytes + nbytes // 8, 64)
             p = C.c_void_p()
-            _check(lib.adh_host_alloc(C.byref(p), C.c_uint64(want)), "adh_host_alloc")
+            _check(lib.adh_host_alloc(C.byref(p), want), "adh_host_alloc")
             ptr, cap = int(p.value), want
             self._bufs[tag] = (ptr, cap)
         if nbytes == 0:
@@ -386,7 +258,7 @@ class PinnedPool:
 
     def close(self):
         for ptr, _ in self._bufs.values():
-            lib.adh_host_free(C.c_void_p(ptr))
+            lib.adh_host_free(ptr)
         self._bufs.clear()
 
 
@@ -530,7 +402,7 @@ class Context:
 
     def __init__(self, device: int = 0):
         self._h = C.c_void_p()
-        _check(lib.adh_create(C.byref(self._h), C.c_int(device)), "adh_create")
+        _check(lib.adh_create(C.byref(self._h), device), "adh_create")
         self.device = device
         self._run_key = None
         self._lib_key = None
@@ -570,7 +442,7 @@ class Context:
         result: list = []
 
         def call():
-            result.append(lib.adh_comm_init(self._h, C.c_int(rank), C.c_int(world), buf, C.c_int64(int(max_rows_per_rank))))
+            result.append(lib.adh_comm_init(self._h, rank, world, buf, int(max_rows_per_rank)))
             msg = lib.adh_last_error()  # (thread-local: fetched on the thread that made the call)
             result.append(msg.decode() if msg else "")
 
@@ -619,8 +491,7 @@ class Context:
         send = np.zeros((cap,) + local.shape[1:], dtype=local.dtype)
         send[: local.shape[0]] = local
         recv = np.empty((world, cap) + local.shape[1:], dtype=local.dtype)
-        _check(lib.adh_comm_all_gather_host(self._h, send.ctypes.data_as(C.c_void_p), C.c_uint64(cap * row_bytes),
-                                            recv.ctypes.data_as(C.c_void_p)), "adh_comm_all_gather_host")
+        _check(lib.adh_comm_all_gather_host(self._h, _p(send), cap * row_bytes, _p(recv)), "adh_comm_all_gather_host")
         return np.concatenate([recv[r, : int(rows_per_rank[r])] for r in range(world)], axis=0)
 
     def all_reduce_max(self, value: float) -> float:
@@ -646,8 +517,7 @@ class Context:
             if not ptr:
                 continue
             a = np.empty(shape, dtype=dt)
-            _check(lib.adh_copy_to_host(self._h, a.ctypes.data_as(C.c_void_p), C.c_void_p(ptr), C.c_uint64(a.nbytes)),
-                   "adh_copy_to_host")
+            _check(lib.adh_copy_to_host(self._h, _p(a), ptr, a.nbytes), "adh_copy_to_host")
             out[name] = a
         return out
 
@@ -668,11 +538,9 @@ class Context:
         n_obs, n_s, n_f = C.c_int32(0), C.c_int32(0), C.c_int32(0)
         _check(
             lib.adh_debug_get_dense(
-                self._h, C.c_int64(int(frame_start)), C.c_int64(int(frame_stop)), C.c_int64(int(scan_start)),
-                C.c_int64(int(scan_stop)), q.ctypes.data_as(C.POINTER(C.c_float)), C.c_int32(q.shape[0]),
-                C.c_float(float(mass_tolerance)), C.c_float(float(quad_lo)), C.c_float(float(quad_hi)),
-                buf.ctypes.data_as(C.POINTER(C.c_float)), C.c_int64(buf.shape[0]),
-                obs.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(n_obs), C.byref(n_s), C.byref(n_f)),
+                self._h, int(frame_start), int(frame_stop), int(scan_start), int(scan_stop), _p(q, C.c_float), q.shape[0],
+                mass_tolerance, quad_lo, quad_hi, _p(buf, C.c_float), buf.shape[0], _p(obs, C.c_int32), C.byref(n_obs),
+                C.byref(n_s), C.byref(n_f)),
             "adh_debug_get_dense",
         )
         K, O, S, F = q.shape[0], n_obs.value, n_s.value, n_f.value
@@ -681,7 +549,7 @@ class Context:
     def d2h_bytes(self, reset: bool = False) -> int:
         """Bytes the library copied device -> host on this GPU since the last reset."""
         v = C.c_uint64(0)
-        _check(lib.adh_transfer_counters(self._h, C.byref(v), C.c_int(int(reset))), "adh_transfer_counters")
+        _check(lib.adh_transfer_counters(self._h, C.byref(v), int(reset)), "adh_transfer_counters")
         return int(v.value)
 
     def fdr_resident(self, mlp: "DeviceMlp", group_a, group_b=None, tiebreak=None, cycle=None,
@@ -697,20 +565,18 @@ class Context:
         m = mlp.n_rows
         rows, proba, qval = np.zeros(m, np.int64), np.zeros(m, np.float32), np.zeros(m, np.float64)
         n_out = C.c_int64(0)
-        p = lambda a, t: a.ctypes.data_as(C.POINTER(t)) if a is not None else None  # noqa: E731
         _check(
             lib.adh_fdr_resident(
-                self._h, mlp._s, p(ga, C.c_int64), p(gb, C.c_int64), p(tb, C.c_int64), p(cyc, C.c_double),
-                C.c_int32(cyc.shape[1] if cyc is not None else 0), C.c_int32(cyc.shape[2] if cyc is not None else 0),
-                C.c_double(float(rt_tol_seconds)), C.c_double(float(mass_tol_ppm)), C.c_double(float(fdr_heuristic)),
-                C.byref(n_out), p(rows, C.c_int64), p(proba, C.c_float), p(qval, C.c_double)),
+                self._h, mlp._s, _p(ga, C.c_int64), _p(gb, C.c_int64), _p(tb, C.c_int64), _p(cyc, C.c_double),
+                cyc.shape[1] if cyc is not None else 0, cyc.shape[2] if cyc is not None else 0, rt_tol_seconds,
+                mass_tol_ppm, fdr_heuristic, C.byref(n_out), _p(rows, C.c_int64), _p(proba, C.c_float), _p(qval, C.c_double)),
             "adh_fdr_resident",
         )
         k = int(n_out.value)
         return rows[:k], proba[:k], qval[:k]
 
     def zero_device_tables(self, stream: int = 0) -> None:
-        _check(lib.adh_zero_device_tables(self._h, C.c_void_p(stream)), "adh_zero_device_tables")
+        _check(lib.adh_zero_device_tables(self._h, stream), "adh_zero_device_tables")
 
     def table_rows_to_host(self, name: str, start: int, stop: int) -> np.ndarray:
         """Rows [start, stop) of the device table ``name`` (of the current tables), copied to the host."""
@@ -723,8 +589,7 @@ class Context:
         ptr = C.cast(getattr(view, name), C.c_void_p).value
         if a.nbytes:
             row_bytes = int(np.prod(row_shape, dtype=np.int64)) * np.dtype(dt).itemsize
-            _check(lib.adh_copy_to_host(self._h, a.ctypes.data_as(C.c_void_p), C.c_void_p(ptr + start * row_bytes),
-                                        C.c_uint64(a.nbytes)), "adh_copy_to_host")
+            _check(lib.adh_copy_to_host(self._h, _p(a), ptr + start * row_bytes, a.nbytes), "adh_copy_to_host")
         return a
 
     def device_tables_to_host(self, names=None) -> dict:
@@ -735,7 +600,7 @@ class Context:
         """Host copy of the computed ("wire") tables rank ``rank`` contributed to the last all-gather."""
         view = _abi.Output()
         n = C.c_int64(0)
-        _check(lib.adh_comm_gathered(self._h, C.c_int(rank), C.byref(view), C.byref(n)), "adh_comm_gathered")
+        _check(lib.adh_comm_gathered(self._h, rank, C.byref(view), C.byref(n)), "adh_comm_gathered")
         return self._view_to_host(view, int(n.value) if rows is None else int(rows))
 
     def __del__(self):
@@ -824,7 +689,7 @@ class Context:
         y = np.empty(int(m.struct.n), dtype=np.float64)
         self._lib_key = None
         self.select_serial += 1
-        _check(lib.adh_stage_fragments_columns(self._h, m.ref(), C.byref(packed), y.ctypes.data_as(C.POINTER(C.c_double))),
+        _check(lib.adh_stage_fragments_columns(self._h, m.ref(), C.byref(packed), _p(y, C.c_double)),
                "adh_stage_fragments_columns")
         self._staged_library(columns, m.struct.n, None)
         return y
@@ -848,9 +713,8 @@ class Context:
         mz_library = np.empty(total, dtype=np.float32)
         y = np.empty(total, dtype=np.float64) if packed is not None else None
         rc = lib.adh_stage_candidate_library(
-            self._h, tables.ref(), C.byref(packed) if packed is not None else None, start.ctypes.data_as(_abi._u32p),
-            stop.ctypes.data_as(_abi._u32p), mz_library.ctypes.data_as(_abi._f32p),
-            y.ctypes.data_as(C.POINTER(C.c_double)) if y is not None else None)
+            self._h, tables.ref(), C.byref(packed) if packed is not None else None, _p(start, C.c_uint32),
+            _p(stop, C.c_uint32), _p(mz_library, C.c_float), _p(y, C.c_double))
         if rc in (-1, -4):  # ADH_ERR_INVALID_ARGUMENT, ADH_ERR_UNSUPPORTED: refused before anything was touched
             _check(rc, "adh_stage_candidate_library")
         self._lib_key = None
@@ -868,7 +732,7 @@ class Context:
         y = np.empty(getattr(self, "_n_lib", 0), dtype=np.float64)  # (no library: the call says so)
         self._lib_key = None
         self.select_serial += 1
-        _check(lib.adh_calibrate_staged_fragments(self._h, C.byref(packed), y.ctypes.data_as(C.POINTER(C.c_double))),
+        _check(lib.adh_calibrate_staged_fragments(self._h, C.byref(packed), _p(y, C.c_double)),
                "adh_calibrate_staged_fragments")
         return y
 
@@ -895,8 +759,8 @@ class Context:
     def staged_fragment_records(self, host_mirror: bool = False) -> np.ndarray:
         """The raw records of the staged library (``_abi.LIB_RECORD_DTYPE``), from HBM or from the host mirror."""
         out = np.empty(getattr(self, "_n_lib", 0), dtype=_abi.LIB_RECORD_DTYPE)
-        _check(lib.adh_staged_fragments_read(self._h, C.c_int32(int(bool(host_mirror))), C.c_void_p(out.ctypes.data),
-                                             C.c_int64(out.shape[0])), "adh_staged_fragments_read")
+        _check(lib.adh_staged_fragments_read(self._h, int(bool(host_mirror)), _p(out), out.shape[0]),
+               "adh_staged_fragments_read")
         return out
 
     # -- scoring ---------------------------------------------------------
@@ -1031,7 +895,7 @@ class Context:
             arrays.update({name: np.empty(slots_cap, dtype=dt) for name, dt in _abi.COMPACT_SLOT_FIELDS})
             for name, a in arrays.items():
                 setattr(out, name, a.ctypes.data_as(dict(out._fields_)[name]))
-            rc = lib.adh_take_rows(self._h, r.ctypes.data_as(C.POINTER(C.c_int64)), C.c_int64(n), C.byref(out))
+            rc = lib.adh_take_rows(self._h, _p(r, C.c_int64), n, C.byref(out))
             if rc != 0 and (int(out.n_rows) > rows_cap or int(out.n_slots) > slots_cap):
                 rows_cap, slots_cap = max(rows_cap, int(out.n_rows)), max(slots_cap, int(out.n_slots))
                 continue  # (cannot happen: every listed row and slot fits)
@@ -1060,7 +924,7 @@ class Context:
         zeroed the buffers on the same stream."""
         cfg = _abi.pack_config(cfg_jit)
         _check(
-            lib.adh_score_uploaded(self._h, C.byref(cfg), C.byref(out_struct), C.c_void_p(stream)),
+            lib.adh_score_uploaded(self._h, C.byref(cfg), C.byref(out_struct), stream),
             "adh_score_uploaded",
         )
 
@@ -1073,7 +937,7 @@ class Context:
         f = C.c_double(0)
         n = C.c_int64(0)
         _check(
-            lib.adh_kernel_time_ms(self._h, C.byref(g), C.byref(f), C.byref(n), C.c_int(int(reset))),
+            lib.adh_kernel_time_ms(self._h, C.byref(g), C.byref(f), C.byref(n), int(reset)),
             "adh_kernel_time_ms",
         )
         return g.value, f.value, n.value
@@ -1083,7 +947,7 @@ class Context:
         since the last reset, over all chunks and scoring entry points."""
         counts = np.zeros(_abi.N_PLAN_CLASSES, dtype=np.int64)
         _check(
-            lib.adh_plan_class_counts(self._h, counts.ctypes.data_as(C.POINTER(C.c_int64)), C.c_int32(int(reset))),
+            lib.adh_plan_class_counts(self._h, _p(counts, C.c_int64), int(reset)),
             "adh_plan_class_counts",
         )
         return counts
@@ -1094,7 +958,7 @@ class Context:
         ``lds_bytes`` a launch of the group asked for."""
         stats = np.zeros(2 * _abi.N_GENERIC_GROUPS, dtype=np.int64)
         _check(
-            lib.adh_generic_launch_stats(self._h, stats.ctypes.data_as(C.POINTER(C.c_int64)), C.c_int32(int(reset))),
+            lib.adh_generic_launch_stats(self._h, _p(stats, C.c_int64), int(reset)),
             "adh_generic_launch_stats",
         )
         return {"candidates": stats[: _abi.N_GENERIC_GROUPS].copy(), "lds_bytes": stats[_abi.N_GENERIC_GROUPS :].copy()}
@@ -1105,7 +969,7 @@ class Context:
         the largest dynamic ``lds_bytes`` a launch of the group asked for."""
         stats = np.zeros(2 * _abi.N_IM_GROUPS, dtype=np.int64)
         _check(
-            lib.adh_im_launch_stats(self._h, stats.ctypes.data_as(C.POINTER(C.c_int64)), C.c_int32(int(reset))),
+            lib.adh_im_launch_stats(self._h, _p(stats, C.c_int64), int(reset)),
             "adh_im_launch_stats",
         )
         return {"candidates": stats[: _abi.N_IM_GROUPS].copy(), "lds_bytes": stats[_abi.N_IM_GROUPS :].copy()}
@@ -1123,8 +987,7 @@ class Context:
         self.select_serial += 1
         _check(
             lib.adh_select_candidates(
-                self._h, precursors.ref(), C.byref(c), k.ctypes.data_as(C.POINTER(C.c_float)),
-                C.c_int32(k.shape[0]), C.c_int32(k.shape[1]), m_out.ref(),
+                self._h, precursors.ref(), C.byref(c), _p(k, C.c_float), k.shape[0], k.shape[1], m_out.ref(),
             ),
             "adh_select_candidates",
         )
@@ -1145,9 +1008,8 @@ class Context:
         self.select_serial += 1
         _check(
             lib.adh_select_candidates_resident(
-                self._h, precursors.ref(), C.byref(c), k.ctypes.data_as(C.POINTER(C.c_float)), C.c_int32(k.shape[0]),
-                C.c_int32(k.shape[1]), eg.ctypes.data_as(C.POINTER(C.c_uint32)), dc.ctypes.data_as(C.POINTER(C.c_uint8)),
-                ch.ctypes.data_as(C.POINTER(C.c_uint8))),
+                self._h, precursors.ref(), C.byref(c), _p(k, C.c_float), k.shape[0], k.shape[1], _p(eg, C.c_uint32),
+                _p(dc, C.c_uint8), _p(ch, C.c_uint8)),
             "adh_select_candidates_resident",
         )
         return n * int(c.candidate_count)
@@ -1158,9 +1020,9 @@ class Context:
         cutoff is rounded to the dtype NumPy compares a float32 column with it in (the device compares in float64)."""
         cutoff = float(np.asarray(score_cutoff).astype(np.result_type(np.float32, score_cutoff)))
         n_sel, n_kept, was_sorted = C.c_int64(0), C.c_int64(0), C.c_int32(0)
-        _check(lib.adh_assemble_selected(self._h, C.c_int32(int(bool(apply_cutoff))), C.c_double(cutoff),
-                                         C.c_int32(int(bool(score_grouped))), C.c_int32(int(reference_channel)),
-                                         C.byref(n_sel), C.byref(n_kept), C.byref(was_sorted)), "adh_assemble_selected")
+        _check(lib.adh_assemble_selected(self._h, int(bool(apply_cutoff)), cutoff, int(bool(score_grouped)),
+                                         int(reference_channel), C.byref(n_sel), C.byref(n_kept), C.byref(was_sorted)),
+               "adh_assemble_selected")
         return int(n_sel.value), int(n_kept.value), bool(was_sorted.value)
 
     def select_handover_stats(self) -> dict:
@@ -1183,8 +1045,7 @@ class Context:
     def selected_ids(self, n: int) -> tuple[np.ndarray, np.ndarray]:
         """``adh_selected_ids``: (row in the selection table, rank) of the ``n`` rows of the assembled table."""
         rows, rank = np.empty(n, np.uint32), np.empty(n, np.uint8)
-        _check(lib.adh_selected_ids(self._h, rows.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                    rank.ctypes.data_as(C.POINTER(C.c_uint8)), C.c_int64(n)), "adh_selected_ids")
+        _check(lib.adh_selected_ids(self._h, _p(rows, C.c_uint32), _p(rank, C.c_uint8), n), "adh_selected_ids")
         return rows, rank
 
     def take_selected(self, rows) -> tuple[dict, np.ndarray]:
@@ -1195,8 +1056,8 @@ class Context:
             raise ValueError("rows must be one-dimensional")
         m_out, arrays = _abi.alloc_candidate_table(r.shape[0])
         pos = np.zeros(r.shape[0], np.uint32)
-        _check(lib.adh_take_selected(self._h, r.ctypes.data_as(C.POINTER(C.c_int64)), C.c_int64(r.shape[0]), m_out.ref(),
-                                     pos.ctypes.data_as(C.POINTER(C.c_uint32))), "adh_take_selected")
+        _check(lib.adh_take_selected(self._h, _p(r, C.c_int64), r.shape[0], m_out.ref(),
+                                     _p(pos, C.c_uint32)), "adh_take_selected")
         return arrays, pos
 
     def select_time_ms(self) -> float:
@@ -1216,12 +1077,10 @@ class Context:
         push_out = np.zeros(n, dtype=np.uint32)
         val_out = np.zeros(n, dtype=np.uint16)
         indptr_out = np.zeros(int(n_tof_indices) + 1, dtype=np.int64)
-        p = lambda a, t: a.ctypes.data_as(C.POINTER(t))  # noqa: E731
         _check(
             lib.adh_transpose_timstof(
-                self._h, p(tof, C.c_uint32), p(ptr, C.c_int64), C.c_int64(ptr.shape[0] - 1),
-                C.c_int64(int(n_tof_indices)), p(val, C.c_uint16), C.c_int64(n),
-                p(push_out, C.c_uint32), p(indptr_out, C.c_int64), p(val_out, C.c_uint16),
+                self._h, _p(tof, C.c_uint32), _p(ptr, C.c_int64), ptr.shape[0] - 1, int(n_tof_indices), _p(val, C.c_uint16),
+                n, _p(push_out, C.c_uint32), _p(indptr_out, C.c_int64), _p(val_out, C.c_uint16),
             ),
             "adh_transpose_timstof",
         )
@@ -1240,22 +1099,11 @@ class Context:
                  else np.array(valid, dtype=bool).astype(np.uint8))
         if valid.shape[0] != rtv.shape[0] or fs.shape[0] != rtv.shape[0] or fe.shape[0] != rtv.shape[0]:
             raise ValueError("rt / fragment ranges / valid must have one entry per PSM")
-        p = lambda a, t: a.ctypes.data_as(C.POINTER(t))  # noqa: E731
         _check(
             lib.adh_fragcomp(
-                self._h,
-                C.c_int64(ws.shape[0]),
-                p(ws, C.c_int64),
-                p(we, C.c_int64),
-                C.c_int64(rtv.shape[0]),
-                p(rtv, C.c_float),
-                p(fs, C.c_int64),
-                p(fe, C.c_int64),
-                C.c_int64(fm.shape[0]),
-                p(fm, C.c_float),
-                C.c_double(float(rt_tol_seconds)),
-                C.c_double(float(mass_tol_ppm)),
-                p(valid, C.c_uint8),
+                self._h, ws.shape[0], _p(ws, C.c_int64), _p(we, C.c_int64), rtv.shape[0], _p(rtv, C.c_float),
+                _p(fs, C.c_int64), _p(fe, C.c_int64), fm.shape[0], _p(fm, C.c_float), rt_tol_seconds, mass_tol_ppm,
+                _p(valid, C.c_uint8),
             ),
             "adh_fragcomp",
         )
@@ -1279,13 +1127,12 @@ class Context:
             raise ValueError("columns of one frame differ in length")
         rows, valid = np.empty(n, dtype=np.int64), np.empty(n, dtype=np.uint8)
         n_rows, grouped = C.c_int64(0), C.c_int32(1)
-        p = lambda a, t: a.ctypes.data_as(C.POINTER(t))  # noqa: E731
         _check(
             lib.adh_fragcomp_frames(
-                self._h, C.c_int64(n), p(pp, C.c_uint32), p(pr, C.c_uint8), p(pmz, C.c_float), p(prt, C.c_float),
-                p(ppb, C.c_float), C.c_int64(fp.shape[0]), p(fp, C.c_uint32), p(fr, C.c_uint8), p(fmz, C.c_float),
-                C.c_int32(lower.shape[0]), p(lower, C.c_double), p(upper, C.c_double), C.c_double(float(rt_tol_seconds)),
-                C.c_double(float(mass_tol_ppm)), p(rows, C.c_int64), p(valid, C.c_uint8), C.byref(n_rows), C.byref(grouped)),
+                self._h, n, _p(pp, C.c_uint32), _p(pr, C.c_uint8), _p(pmz, C.c_float), _p(prt, C.c_float),
+                _p(ppb, C.c_float), fp.shape[0], _p(fp, C.c_uint32), _p(fr, C.c_uint8), _p(fmz, C.c_float),
+                lower.shape[0], _p(lower, C.c_double), _p(upper, C.c_double), rt_tol_seconds, mass_tol_ppm,
+                _p(rows, C.c_int64), _p(valid, C.c_uint8), C.byref(n_rows), C.byref(grouped)),
             "adh_fragcomp_frames",
         )
         if not grouped.value:
@@ -1313,7 +1160,6 @@ class Context:
         n = sc.shape[0]
         if de.shape[0] != n:
             raise ValueError("score and decoy differ in length")
-        p = lambda a, t: a.ctypes.data_as(C.POINTER(t))  # noqa: E731
         tb = None
         if tiebreak is not None:
             tb = _abi.as_c(tiebreak, np.int64)
@@ -1322,9 +1168,8 @@ class Context:
         order = np.zeros(n, dtype=np.int64)
         qval = np.zeros(n, dtype=np.float64)
         _check(
-            lib.adh_fdr_q_values(self._h, C.c_int64(n), p(sc, C.c_double), p(de, C.c_uint8),
-                                 p(tb, C.c_int64) if tb is not None else None, p(order, C.c_int64),
-                                 p(qval, C.c_double)),
+            lib.adh_fdr_q_values(self._h, n, _p(sc, C.c_double), _p(de, C.c_uint8), _p(tb, C.c_int64), _p(order, C.c_int64),
+                                 _p(qval, C.c_double)),
             "adh_fdr_q_values",
         )
         return order, qval
@@ -1338,10 +1183,8 @@ class Context:
         if ga.shape[0] != n or (gb is not None and gb.shape[0] != n):
             raise ValueError("score and group columns differ in length")
         keep = np.zeros(n, dtype=np.uint8)
-        p = lambda a, t: a.ctypes.data_as(C.POINTER(t))  # noqa: E731
         _check(
-            lib.adh_fdr_keep_best(self._h, C.c_int64(n), p(sc, C.c_double), p(ga, C.c_int64),
-                                  p(gb, C.c_int64) if gb is not None else None, p(keep, C.c_uint8)),
+            lib.adh_fdr_keep_best(self._h, n, _p(sc, C.c_double), _p(ga, C.c_int64), _p(gb, C.c_int64), _p(keep, C.c_uint8)),
             "adh_fdr_keep_best",
         )
         return keep.view(np.bool_)
@@ -1359,10 +1202,8 @@ class Context:
             raise ValueError("calibration_predict takes one input column")
         xa = np.ascontiguousarray(xa, dtype=np.float32 if xa.dtype == np.float32 else np.float64)
         y = np.empty(xa.shape[0], dtype=np.float64)
-        _check(lib.adh_calibration_predict(self._h, C.byref(packed), C.c_void_p(xa.ctypes.data),
-                                           C.c_int32(int(xa.dtype == np.float64)), C.c_int64(xa.shape[0]),
-                                           y.ctypes.data_as(C.POINTER(C.c_double))),
-               "adh_calibration_predict")
+        _check(lib.adh_calibration_predict(self._h, C.byref(packed), _p(xa), int(xa.dtype == np.float64), xa.shape[0],
+                                           _p(y, C.c_double)), "adh_calibration_predict")
         return y
 
     def calibration_time_ms(self) -> float:
@@ -1403,10 +1244,9 @@ class Context:
             raise ValueError("tl_qc: intensity and correlation of one shape, one start and stop per precursor")
         use = np.zeros(fs.shape[0], np.uint8)
         large, ms = C.c_int64(0), C.c_double(0.0)
-        p = lambda a, t: a.ctypes.data_as(C.POINTER(t))  # noqa: E731
-        _check(lib.adh_tl_qc(self._h, fs.shape[0], p(fs, C.c_int64), p(fe, C.c_int64), inten.shape[0], inten.shape[1],
-                             p(inten, C.c_float), p(corr, C.c_float), float(cutoff), float(ratio), int(bool(empty_passes)),
-                             p(use, C.c_uint8), C.byref(large), C.byref(ms)), "adh_tl_qc")
+        _check(lib.adh_tl_qc(self._h, fs.shape[0], _p(fs, C.c_int64), _p(fe, C.c_int64), inten.shape[0], inten.shape[1],
+                             _p(inten, C.c_float), _p(corr, C.c_float), cutoff, ratio, int(bool(empty_passes)),
+                             _p(use, C.c_uint8), C.byref(large), C.byref(ms)), "adh_tl_qc")
         return use.astype(bool), inten, int(large.value), float(ms.value)
 
     def tl_rt_norm(self, rt_observed, rt_calibrated=None, rt_library=None):
@@ -1423,9 +1263,8 @@ class Context:
         out = np.empty(obs.shape[0], np.result_type(obs, cal, lb) if delta else obs.dtype)
         ms = C.c_double(0.0)
         f64 = lambda a: int(a is not None and a.dtype == np.float64)  # noqa: E731
-        ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None  # noqa: E731
-        _check(lib.adh_tl_rt_norm(self._h, obs.shape[0], int(delta), ptr(obs), f64(obs), ptr(cal), f64(cal), ptr(lb),
-                                  f64(lb), ptr(out), C.byref(ms)), "adh_tl_rt_norm")
+        _check(lib.adh_tl_rt_norm(self._h, obs.shape[0], int(delta), _p(obs), f64(obs), _p(cal), f64(cal), _p(lb),
+                                  f64(lb), _p(out), C.byref(ms)), "adh_tl_rt_norm")
         return out, float(ms.value)
 
     # -- match-between-runs library ---------------------------------------
@@ -1438,8 +1277,8 @@ class _DeviceSession:
     """A native object that lives on a ``Context``'s handle (``adh_mlp_t``, ``adh_quant_t``, ...).  The subclass
     fills ``self._s`` with its create call.  The context closes its live sessions before it destroys the handle, so
     the native destroy always finds the handle it reads, and a session closed that way makes no native call later.
-    (The subclass makes its own two calls by name, ``lib.adh_x_destroy(s)`` and ``lib.adh_x_time_ms(...)``: the ABI
-    tests read the wrapper classes for the exports they call.)"""
+    (The subclass makes its own destroy and ``time_ms`` calls by name, as every native call in this module is spelled
+    ``lib.adh_<name>(...)``: the ABI tests read the module and the wrapper classes for the exports they call.)"""
 
     def __init__(self, ctx: Context):
         self._ctx = ctx  # keeps the handle alive
@@ -1461,10 +1300,6 @@ class _DeviceSession:
             self.close()
         except Exception:
             pass
-
-    @staticmethod
-    def _p(a, t):
-        return a.ctypes.data_as(C.POINTER(t))
 
     @staticmethod
     def _times(n: int, call) -> tuple:
@@ -1498,15 +1333,15 @@ class DeviceMlp(_DeviceSession):
         rv = _abi.as_c(running_var, np.float32)
         if pa.shape != (self.n_params,) or rm.shape != (self.input_dim,) or rv.shape != (self.input_dim,):
             raise ValueError("state arrays do not match the architecture")
-        _check(lib.adh_mlp_set_state(self._s, self._p(pa, C.c_float), self._p(rm, C.c_float), self._p(rv, C.c_float),
-                                     C.c_int64(int(num_batches_tracked))), "adh_mlp_set_state")
+        _check(lib.adh_mlp_set_state(self._s, _p(pa, C.c_float), _p(rm, C.c_float), _p(rv, C.c_float),
+                                     int(num_batches_tracked)), "adh_mlp_set_state")
 
     def get_state(self):
         pa = np.zeros(self.n_params, dtype=np.float32)
         rm = np.zeros(self.input_dim, dtype=np.float32)
         rv = np.zeros(self.input_dim, dtype=np.float32)
         nbt = C.c_int64(0)
-        _check(lib.adh_mlp_get_state(self._s, self._p(pa, C.c_float), self._p(rm, C.c_float), self._p(rv, C.c_float),
+        _check(lib.adh_mlp_get_state(self._s, _p(pa, C.c_float), _p(rm, C.c_float), _p(rv, C.c_float),
                                      C.byref(nbt)), "adh_mlp_get_state")
         return pa, rm, rv, int(nbt.value)
 
@@ -1519,8 +1354,8 @@ class DeviceMlp(_DeviceSession):
             ya = _abi.as_c(y, np.float32)
             if ya.shape != (xa.shape[0],):
                 raise ValueError("y must hold one target per row")
-        _check(lib.adh_mlp_stage_rows(self._s, self._p(xa, C.c_float), C.c_int64(xa.shape[0]), C.c_int32(xa.shape[1]),
-                                      self._p(ya, C.c_float) if ya is not None else None), "adh_mlp_stage_rows")
+        _check(lib.adh_mlp_stage_rows(self._s, _p(xa, C.c_float), xa.shape[0], xa.shape[1], _p(ya, C.c_float)),
+               "adh_mlp_stage_rows")
         self.n_rows = xa.shape[0]
 
     def stage_rows_device(self, src_cols, decoy, extra_cols=(), channel=None, part=None):
@@ -1535,12 +1370,11 @@ class DeviceMlp(_DeviceSession):
         extras = [_abi.as_c(e, np.float32) for e in extra_cols]
         if any(e.shape != de.shape for e in extras):
             raise ValueError("extra columns must have one value per candidate row")
-        arr = (C.POINTER(C.c_float) * max(len(extras), 1))(*[self._p(e, C.c_float) for e in extras])
+        arr = (C.POINTER(C.c_float) * max(len(extras), 1))(*[_p(e, C.c_float) for e in extras])
         nt, nd = C.c_int64(0), C.c_int64(0)
         if part is None:
-            _check(lib.adh_mlp_stage_rows_device(self._s, self._p(sc, C.c_int32), C.c_int32(sc.shape[0]), arr,
-                                                 C.c_int32(len(extras)), self._p(de, C.c_uint8), C.c_int64(de.shape[0]),
-                                                 C.byref(nt), C.byref(nd)), "adh_mlp_stage_rows_device")
+            _check(lib.adh_mlp_stage_rows_device(self._s, _p(sc, C.c_int32), sc.shape[0], arr, len(extras), _p(de, C.c_uint8),
+                                                 de.shape[0], C.byref(nt), C.byref(nd)), "adh_mlp_stage_rows_device")
         else:
             if channel is None:
                 raise ValueError("a part needs the channel column")
@@ -1550,16 +1384,15 @@ class DeviceMlp(_DeviceSession):
                                       f"{de.shape[0]}: one per row of the device tables is needed")
             target, decoy_channel, by_channel = part
             _check(lib.adh_mlp_stage_rows_device_part(
-                self._s, self._p(sc, C.c_int32), C.c_int32(sc.shape[0]), arr, C.c_int32(len(extras)),
-                self._p(de, C.c_uint8), C.c_int64(de.shape[0]), self._p(ch, C.c_int64), C.c_int64(int(target)),
-                C.c_int64(int(decoy_channel)), C.c_int32(int(bool(by_channel))), C.byref(nt), C.byref(nd)),
+                self._s, _p(sc, C.c_int32), sc.shape[0], arr, len(extras), _p(de, C.c_uint8), de.shape[0], _p(ch, C.c_int64),
+                int(target), int(decoy_channel), int(bool(by_channel)), C.byref(nt), C.byref(nd)),
                 "adh_mlp_stage_rows_device_part")
         self.n_rows = int(nt.value) + int(nd.value)
         return int(nt.value), int(nd.value)
 
     def staged_rows(self) -> np.ndarray:
         rows = np.zeros(self.n_rows, dtype=np.int64)
-        _check(lib.adh_mlp_staged_rows(self._s, self._p(rows, C.c_int64), C.c_int64(rows.shape[0])), "adh_mlp_staged_rows")
+        _check(lib.adh_mlp_staged_rows(self._s, _p(rows, C.c_int64), rows.shape[0]), "adh_mlp_staged_rows")
         return rows
 
     def predict_resident(self) -> None:
@@ -1570,14 +1403,14 @@ class DeviceMlp(_DeviceSession):
         tr = _abi.as_c(train_rows, np.int64)
         bs = _abi.as_c(batch_start, np.int64)
         f = _abi.MlpFit()
-        f.train_rows, f.n_train = self._p(tr, C.c_int64), tr.shape[0]
-        f.batch_start, f.n_steps = self._p(bs, C.c_int64), bs.shape[0]
+        f.train_rows, f.n_train = _p(tr, C.c_int64), tr.shape[0]
+        f.batch_start, f.n_steps = _p(bs, C.c_int64), bs.shape[0]
         f.batch_size = int(batch_size)
         f.learning_rate, f.weight_decay, f.dropout = float(learning_rate), float(weight_decay), float(dropout)
         f.beta1, f.beta2, f.eps = float(betas[0]), float(betas[1]), float(eps)
         f.seed, f.first_step = int(seed) & (2**64 - 1), int(first_step)
         loss = np.zeros(bs.shape[0], dtype=np.float32)
-        _check(lib.adh_mlp_fit(self._s, C.byref(f), self._p(loss, C.c_float)), "adh_mlp_fit")
+        _check(lib.adh_mlp_fit(self._s, C.byref(f), _p(loss, C.c_float)), "adh_mlp_fit")
         return loss
 
     def predict(self, rows=None) -> np.ndarray:
@@ -1585,9 +1418,9 @@ class DeviceMlp(_DeviceSession):
             n, rp = self.n_rows, None
         else:
             ra = _abi.as_c(rows, np.int64)
-            n, rp = ra.shape[0], self._p(ra, C.c_int64)
+            n, rp = ra.shape[0], _p(ra, C.c_int64)
         out = np.zeros((n, self.output_dim), dtype=np.float32)
-        _check(lib.adh_mlp_predict(self._s, rp, C.c_int64(n), self._p(out, C.c_float)), "adh_mlp_predict")
+        _check(lib.adh_mlp_predict(self._s, rp, n, _p(out, C.c_float)), "adh_mlp_predict")
         return out
 
     def time_ms(self):
@@ -1602,7 +1435,7 @@ class DeviceQuant(_DeviceSession):
         super().__init__(ctx)
         self.n_columns = int(n_columns)
         psm = np.ascontiguousarray(psm_precursor_idx, dtype=np.uint32)
-        _check(lib.adh_quant_create(ctx._h, self.n_columns, psm.ctypes.data_as(C.POINTER(C.c_uint32)), psm.shape[0],
+        _check(lib.adh_quant_create(ctx._h, self.n_columns, _p(psm, C.c_uint32), psm.shape[0],
                                     C.byref(self._s)), "adh_quant_create")
         self.n_runs = 0
         self.n_rows = 0
@@ -1614,7 +1447,7 @@ class DeviceQuant(_DeviceSession):
 
     @staticmethod
     def _cols(arrays):
-        return (C.POINTER(C.c_float) * max(len(arrays), 1))(*[a.ctypes.data_as(C.POINTER(C.c_float)) for a in arrays])
+        return (C.POINTER(C.c_float) * max(len(arrays), 1))(*[_p(a, C.c_float) for a in arrays])
 
     def add_run(self, precursor_idx, number, type_, charge, loss_type, columns) -> int:
         """Append one run (uint32 precursor_idx, four uint8 columns, ``n_columns`` float32 columns); returns the rows
@@ -1626,8 +1459,7 @@ class DeviceQuant(_DeviceSession):
         if len(cols) != self.n_columns or any(x.shape != (n,) for x in [*b, *cols]):
             raise ValueError("add_run: every column must hold one value per row, one array per quantity column")
         kept = C.c_int64(0)
-        u8 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint8))  # noqa: E731
-        _check(lib.adh_quant_add_run(self._s, n, p.ctypes.data_as(C.POINTER(C.c_uint32)), *[u8(x) for x in b],
+        _check(lib.adh_quant_add_run(self._s, n, _p(p, C.c_uint32), *[_p(x, C.c_uint8) for x in b],
                                      self._cols(cols), C.byref(kept)), "adh_quant_add_run")
         self.n_runs += 1
         self.n_rows += int(kept.value)
@@ -1643,14 +1475,13 @@ class DeviceQuant(_DeviceSession):
     def keys(self):
         ion = np.empty(self.n_keys, dtype=np.int64)
         pidx = np.empty(self.n_keys, dtype=np.uint32)
-        _check(lib.adh_quant_keys(self._s, ion.ctypes.data_as(C.POINTER(C.c_int64)),
-                                  pidx.ctypes.data_as(C.POINTER(C.c_uint32))), "adh_quant_keys")
+        _check(lib.adh_quant_keys(self._s, _p(ion, C.c_int64), _p(pidx, C.c_uint32)), "adh_quant_keys")
         return ion, pidx
 
     def matrix(self, column: int) -> np.ndarray:
         """Quantity column ``column`` as a C-ordered ``(n_runs, n_keys)`` float32 array (one row per run)."""
         out = np.empty((self.n_runs, self.n_keys), dtype=np.float32)
-        _check(lib.adh_quant_matrix(self._s, int(column), out.ctypes.data_as(C.POINTER(C.c_float))), "adh_quant_matrix")
+        _check(lib.adh_quant_matrix(self._s, int(column), _p(out, C.c_float)), "adh_quant_matrix")
         return out
 
     def rows(self):
@@ -1658,9 +1489,8 @@ class DeviceQuant(_DeviceSession):
         n = self.n_rows
         ion, pidx, run = np.empty(n, np.int64), np.empty(n, np.uint32), np.empty(n, np.uint32)
         cols = [np.empty(n, np.float32) for _ in range(self.n_columns)]
-        _check(lib.adh_quant_rows(self._s, ion.ctypes.data_as(C.POINTER(C.c_int64)),
-                                  pidx.ctypes.data_as(C.POINTER(C.c_uint32)), run.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                  self._cols(cols)), "adh_quant_rows")
+        _check(lib.adh_quant_rows(self._s, _p(ion, C.c_int64), _p(pidx, C.c_uint32), _p(run, C.c_uint32), self._cols(cols)),
+               "adh_quant_rows")
         return ion, pidx, run, cols
 
     def set_matrix(self, run_columns) -> None:
@@ -1680,10 +1510,8 @@ class DeviceQuant(_DeviceSession):
         total = np.empty(self.n_keys, np.float32)
         rank = np.empty(self.n_keys, np.float64)
         mask = np.empty(self.n_keys, np.uint8)
-        _check(lib.adh_quant_filter(self._s, int(column), g.ctypes.data_as(C.POINTER(C.c_int32)), int(n_groups),
-                                    float(top_n), float(threshold), total.ctypes.data_as(C.POINTER(C.c_float)),
-                                    rank.ctypes.data_as(C.POINTER(C.c_double)), mask.ctypes.data_as(C.POINTER(C.c_uint8))),
-               "adh_quant_filter")
+        _check(lib.adh_quant_filter(self._s, int(column), _p(g, C.c_int32), int(n_groups), top_n, threshold,
+                                    _p(total, C.c_float), _p(rank, C.c_double), _p(mask, C.c_uint8)), "adh_quant_filter")
         return total, rank, mask.view(np.bool_)
 
     def time_ms(self):
@@ -1703,10 +1531,6 @@ class DeviceProteinGroups(_DeviceSession):
     def _native_destroy(self, s):
         lib.adh_pg_destroy(s)
 
-    @staticmethod
-    def _i32(a):
-        return a.ctypes.data_as(C.POINTER(C.c_int32))
-
     def solve(self, edge_pattern, edge_id, weight, n_ids: int):
         """``(pattern_master, id_emptied_by)`` of ``adh_pg_solve``: one weight per pattern, ``n_ids`` id codes."""
         ep, ei, w = (_abi.as_c(x, np.int32) for x in (edge_pattern, edge_id, weight))
@@ -1714,8 +1538,8 @@ class DeviceProteinGroups(_DeviceSession):
             raise ValueError("solve: one pattern and one id per edge, one weight per pattern")
         master = np.empty(w.shape[0], np.int32)
         emptied = np.empty(max(int(n_ids), 0), np.int32)
-        _check(lib.adh_pg_solve(self._s, w.shape[0], int(n_ids), ep.shape[0], self._i32(ep), self._i32(ei), self._i32(w),
-                                self._i32(master), self._i32(emptied)), "adh_pg_solve")
+        _check(lib.adh_pg_solve(self._s, w.shape[0], int(n_ids), ep.shape[0], _p(ep, C.c_int32), _p(ei, C.c_int32),
+                                _p(w, C.c_int32), _p(master, C.c_int32), _p(emptied, C.c_int32)), "adh_pg_solve")
         self.n_patterns, self.n_ids, self.n_edges = w.shape[0], int(n_ids), ep.shape[0]
         return master, emptied
 
@@ -1727,8 +1551,8 @@ class DeviceProteinGroups(_DeviceSession):
         off = np.empty(self.n_patterns + 1, np.int32)
         ids = np.empty(max(self.n_edges, 1), np.int32)
         kept = C.c_int64(0)
-        _check(lib.adh_pg_filter(self._s, int(n_strings), self._i32(s), self._i32(r), self._i32(off), self._i32(ids),
-                                 C.byref(kept)), "adh_pg_filter")
+        _check(lib.adh_pg_filter(self._s, int(n_strings), _p(s, C.c_int32), _p(r, C.c_int32), _p(off, C.c_int32),
+                                 _p(ids, C.c_int32), C.byref(kept)), "adh_pg_filter")
         return off, ids[: int(kept.value)]
 
     def stats(self) -> tuple[int, int, int]:
@@ -1769,16 +1593,16 @@ class DeviceProteinFdr(_DeviceSession):
         if pg.ndim != 1 or any(a.shape != (n,) for a in (seq, rn, de, pi, pr)):
             raise ValueError("features: one value of every column per row")
         groups = C.c_int64(0)
-        _check(lib.adh_pfdr_features(self._s, n, self._p(pg, C.c_int32), self._p(de, C.c_uint8), self._p(pi, C.c_int64),
-                                     self._p(seq, C.c_int32), self._p(rn, C.c_int32), C.c_void_p(pr.ctypes.data),
+        _check(lib.adh_pfdr_features(self._s, n, _p(pg, C.c_int32), _p(de, C.c_uint8), _p(pi, C.c_int64),
+                                     _p(seq, C.c_int32), _p(rn, C.c_int32), _p(pr),
                                      int(pr.dtype == np.float64), C.byref(groups)), "adh_pfdr_features")
         self.n_rows, self.n_groups = n, int(groups.value)
         gpg = np.empty(self.n_groups, np.int32)
         gde = np.empty(self.n_groups, np.uint8)
         x = np.empty((self.n_groups, self.N_FEATURES), np.float64)
         row_group = np.empty(n, np.int32) if with_row_group else None
-        _check(lib.adh_pfdr_read_features(self._s, self._p(gpg, C.c_int32), self._p(gde, C.c_uint8), self._p(x, C.c_double),
-                                          self._p(row_group, C.c_int32) if with_row_group else None),
+        _check(lib.adh_pfdr_read_features(self._s, _p(gpg, C.c_int32), _p(gde, C.c_uint8), _p(x, C.c_double),
+                                          _p(row_group, C.c_int32)),
                "adh_pfdr_read_features")
         return (gpg, gde, x, row_group) if with_row_group else (gpg, gde, x)
 
@@ -1789,8 +1613,8 @@ class DeviceProteinFdr(_DeviceSession):
         p = _abi.as_c(params, np.float64)
         if x.ndim != 2 or x.shape[1] != self.N_FEATURES or y.shape != (x.shape[0],) or p.shape != (self.N_PARAMS,):
             raise ValueError("fit_begin: x [rows, 7], one label per row, 901 parameters")
-        _check(lib.adh_pfdr_fit_begin(self._s, x.shape[0], self._p(x, C.c_double), self._p(y, C.c_uint8),
-                                      self._p(p, C.c_double)), "adh_pfdr_fit_begin")
+        _check(lib.adh_pfdr_fit_begin(self._s, x.shape[0], _p(x, C.c_double), _p(y, C.c_uint8),
+                                      _p(p, C.c_double)), "adh_pfdr_fit_begin")
         self.n_train = x.shape[0]
 
     def epoch(self, order, step_size) -> float:
@@ -1800,7 +1624,7 @@ class DeviceProteinFdr(_DeviceSession):
         if o.shape != (self.n_train,) or lr.ndim != 1:
             raise ValueError("epoch: one position per training row, one step size per batch")
         loss = C.c_double(0.0)
-        _check(lib.adh_pfdr_epoch(self._s, self._p(o, C.c_int32), lr.shape[0], self._p(lr, C.c_double), C.byref(loss)),
+        _check(lib.adh_pfdr_epoch(self._s, _p(o, C.c_int32), lr.shape[0], _p(lr, C.c_double), C.byref(loss)),
                "adh_pfdr_epoch")
         return float(loss.value)
 
@@ -1809,7 +1633,7 @@ class DeviceProteinFdr(_DeviceSession):
         if x.ndim != 2 or x.shape[1] != self.N_FEATURES:
             raise ValueError("predict: x [rows, 7]")
         out = np.empty(x.shape[0], np.float64)
-        _check(lib.adh_pfdr_predict(self._s, x.shape[0], self._p(x, C.c_double), self._p(out, C.c_double)),
+        _check(lib.adh_pfdr_predict(self._s, x.shape[0], _p(x, C.c_double), _p(out, C.c_double)),
                "adh_pfdr_predict")
         return out
 
@@ -1819,7 +1643,7 @@ class DeviceProteinFdr(_DeviceSession):
         if v.shape != (self.n_groups,):
             raise ValueError("gather: one value per group of the last features call")
         out = np.empty(self.n_rows, np.float64)
-        _check(lib.adh_pfdr_gather(self._s, v.shape[0], self._p(v, C.c_double), self._p(out, C.c_double)), "adh_pfdr_gather")
+        _check(lib.adh_pfdr_gather(self._s, v.shape[0], _p(v, C.c_double), _p(out, C.c_double)), "adh_pfdr_gather")
         return out
 
     def time_ms(self) -> tuple[float, float, float, float]:
@@ -1847,8 +1671,8 @@ class DeviceTransferLibrary(_DeviceSession):
         if r.ndim != 1 or any(a.shape != r.shape for a in (c, *v)):
             raise ValueError("scatter: one value of every column per flat row")
         dup = C.c_int32(0)
-        _check(lib.adh_tl_scatter(self._s, int(n_rows), r.shape[0], self._p(r, C.c_int64), self._p(c, C.c_int32),
-                                  *(self._p(a, C.c_float) for a in v), C.byref(dup)), "adh_tl_scatter")
+        _check(lib.adh_tl_scatter(self._s, int(n_rows), r.shape[0], _p(r, C.c_int64), _p(c, C.c_int32),
+                                  *(_p(a, C.c_float) for a in v), C.byref(dup)), "adh_tl_scatter")
         return bool(dup.value)
 
     def update(self, keep_top: int, mod_seq_hash, proba, precursor_idx, frag_start, frag_stop, n_new_rows: int,
@@ -1869,22 +1693,21 @@ class DeviceTransferLibrary(_DeviceSession):
             held = [_abi.as_c(m, np.float32) for m in matrices]
             if len(held) != self.n_matrices or any(m.shape != (n_new_rows, self.n_columns) for m in held):
                 raise ValueError("update: every dense matrix is [n_new_rows, n_columns]")
-            mats = (C.POINTER(C.c_float) * len(held))(*(self._p(m, C.c_float) for m in held))
+            mats = (C.POINTER(C.c_float) * len(held))(*(_p(m, C.c_float) for m in held))
         kept_n, rows_n = C.c_int64(0), C.c_int64(0)
-        _check(lib.adh_tl_update(self._s, int(keep_top), n, C.c_void_p(h.ctypes.data), int(h.dtype == np.int64),
-                                 C.c_void_p(pr.ctypes.data), int(pr.dtype == np.float64), self._p(pi, C.c_int64),
-                                 self._p(fs, C.c_int64), self._p(fe, C.c_int64), int(n_new_rows), mats, C.byref(kept_n),
+        _check(lib.adh_tl_update(self._s, int(keep_top), n, _p(h), int(h.dtype == np.int64), _p(pr), int(pr.dtype == np.float64),
+                                 _p(pi, C.c_int64), _p(fs, C.c_int64), _p(fe, C.c_int64), int(n_new_rows), mats, C.byref(kept_n),
                                  C.byref(rows_n)), "adh_tl_update")
         self.n_kept, self.n_rows = int(kept_n.value), int(rows_n.value)
         kept, start, stop = (np.empty(self.n_kept, np.int64) for _ in range(3))
-        _check(lib.adh_tl_read_kept(self._s, self._p(kept, C.c_int64), self._p(start, C.c_int64), self._p(stop, C.c_int64)),
+        _check(lib.adh_tl_read_kept(self._s, _p(kept, C.c_int64), _p(start, C.c_int64), _p(stop, C.c_int64)),
                "adh_tl_read_kept")
         return kept, start, stop
 
     def matrix(self, m: int) -> np.ndarray:
         """``adh_tl_read_matrix``: dense matrix ``m`` of the consensus."""
         out = np.empty((self.n_rows, self.n_columns), np.float32)
-        _check(lib.adh_tl_read_matrix(self._s, int(m), self._p(out, C.c_float)), "adh_tl_read_matrix")
+        _check(lib.adh_tl_read_matrix(self._s, int(m), _p(out, C.c_float)), "adh_tl_read_matrix")
         return out
 
     def time_ms(self) -> tuple[float, float, float]:
@@ -1938,10 +1761,9 @@ class DeviceMbr(_DeviceSession):
         if q.ndim != 1 or any(a.shape != (n,) for a in (d, eg, h, rt, pg)):
             raise ValueError("aggregate: one value of every column per PSM row")
         out = [C.c_int64(0) for _ in range(4)]
-        _check(lib.adh_mbr_aggregate(self._s, n, self._p(q, C.c_double), self._p(d, C.c_uint8), C.c_void_p(eg.ctypes.data),
-                                     int(eg.dtype == np.uint32), C.c_void_p(h.ctypes.data), int(h.dtype == np.int64),
-                                     C.c_void_p(rt.ctypes.data), int(rt.dtype == np.float64), self._p(pg, C.c_uint8),
-                                     float(fdr), int(bool(keep_decoys)), *(C.byref(x) for x in out)), "adh_mbr_aggregate")
+        _check(lib.adh_mbr_aggregate(self._s, n, _p(q, C.c_double), _p(d, C.c_uint8), _p(eg), int(eg.dtype == np.uint32), _p(h),
+                                     int(h.dtype == np.int64), _p(rt), int(rt.dtype == np.float64), _p(pg, C.c_uint8),
+                                     fdr, int(bool(keep_decoys)), *(C.byref(x) for x in out)), "adh_mbr_aggregate")
         self.n_passed, self.n_by_group, self.n_by_hash, self.n_groups = (int(x.value) for x in out)
         self._rt_dtype, self._hash_dtype = rt.dtype, h.dtype
         self._group_dtype = np.asarray(elution_group_idx).dtype
@@ -1954,14 +1776,13 @@ class DeviceMbr(_DeviceSession):
         n = (self.n_by_group, self.n_by_hash)[which]
         keys = np.empty(n, np.int64 if which == 0 else self._hash_dtype)
         med, first = np.empty(n, self._rt_dtype), np.empty(n, np.int64)
-        _check(lib.adh_mbr_read_table(self._s, int(which), C.c_void_p(keys.ctypes.data), C.c_void_p(med.ctypes.data),
-                                      self._p(first, C.c_int64)), "adh_mbr_read_table")
+        _check(lib.adh_mbr_read_table(self._s, int(which), _p(keys), _p(med), _p(first, C.c_int64)), "adh_mbr_read_table")
         return (keys.astype(self._group_dtype) if which == 0 else keys), med, first
 
     def groups(self) -> np.ndarray:
         """The elution groups that passed, ascending."""
         keys = np.empty(self.n_groups, np.int64)
-        _check(lib.adh_mbr_read_table(self._s, 2, C.c_void_p(keys.ctypes.data), None, None), "adh_mbr_read_table")
+        _check(lib.adh_mbr_read_table(self._s, 2, _p(keys), None, None), "adh_mbr_read_table")
         return keys.astype(self._group_dtype)
 
     def filter(self, elution_group_idx, frag_start, frag_stop, n_rows: int, matrices=None, source_rows: bool = False):
@@ -1981,17 +1802,16 @@ class DeviceMbr(_DeviceSession):
             if any(m.ndim != 2 or m.shape != held[0].shape or m.shape[0] != n_rows for m in held):
                 raise ValueError("filter: every dense matrix is [n_rows, n_columns]")
             n_cols = held[0].shape[1]
-            mats = (C.POINTER(C.c_float) * len(held))(*(self._p(m, C.c_float) for m in held))
+            mats = (C.POINTER(C.c_float) * len(held))(*(_p(m, C.c_float) for m in held))
         kept_n, rows_n = C.c_int64(0), C.c_int64(0)
-        _check(lib.adh_mbr_filter(self._s, n, C.c_void_p(eg.ctypes.data), int(eg.dtype == np.uint32), self._p(fs, C.c_int64),
-                                  self._p(fe, C.c_int64), int(n_rows), int(n_cols), len(held), mats, C.byref(kept_n),
-                                  C.byref(rows_n)), "adh_mbr_filter")
+        _check(lib.adh_mbr_filter(self._s, n, _p(eg), int(eg.dtype == np.uint32), _p(fs, C.c_int64), _p(fe, C.c_int64),
+                                  int(n_rows), int(n_cols), len(held), mats, C.byref(kept_n), C.byref(rows_n)), "adh_mbr_filter")
         self.n_kept, self.n_rows, self.n_columns = int(kept_n.value), int(rows_n.value), int(n_cols)
         kept, start, stop = (np.empty(self.n_kept, np.int64) for _ in range(3))
         src = np.empty(self.n_rows, np.int64) if source_rows else None
         if self.n_kept:
-            _check(lib.adh_mbr_read_filter(self._s, self._p(kept, C.c_int64), self._p(start, C.c_int64),
-                                           self._p(stop, C.c_int64), self._p(src, C.c_int64) if source_rows else None),
+            _check(lib.adh_mbr_read_filter(self._s, _p(kept, C.c_int64), _p(start, C.c_int64),
+                                           _p(stop, C.c_int64), _p(src, C.c_int64)),
                    "adh_mbr_read_filter")
         return kept, start, stop, src
 
@@ -1999,7 +1819,7 @@ class DeviceMbr(_DeviceSession):
         """``adh_mbr_read_matrix``: gathered dense matrix ``m`` of the last filter."""
         out = np.empty((self.n_rows, self.n_columns), np.float32)
         if self.n_kept:
-            _check(lib.adh_mbr_read_matrix(self._s, int(m), self._p(out, C.c_float)), "adh_mbr_read_matrix")
+            _check(lib.adh_mbr_read_matrix(self._s, int(m), _p(out, C.c_float)), "adh_mbr_read_matrix")
         return out
 
     def assign(self, elution_group_idx, mod_seq_charge_hash):
@@ -2011,9 +1831,8 @@ class DeviceMbr(_DeviceSession):
         if eg.ndim != 1 or h.shape != (n,):
             raise ValueError("assign: one value of every column per precursor")
         rt, row, missing = np.empty(n, self._rt_dtype), np.empty(n, np.int64), C.c_int64(0)
-        _check(lib.adh_mbr_assign(self._s, n, C.c_void_p(eg.ctypes.data), int(eg.dtype == np.uint32), C.c_void_p(h.ctypes.data),
-                                  int(h.dtype == np.int64), C.c_void_p(rt.ctypes.data), self._p(row, C.c_int64),
-                                  C.byref(missing)), "adh_mbr_assign")
+        _check(lib.adh_mbr_assign(self._s, n, _p(eg), int(eg.dtype == np.uint32), _p(h), int(h.dtype == np.int64), _p(rt),
+                                  _p(row, C.c_int64), C.byref(missing)), "adh_mbr_assign")
         return rt, row, int(missing.value)
 
     def index(self, target_keys, lookup_keys):
@@ -2021,8 +1840,8 @@ class DeviceMbr(_DeviceSession):
         columns in an order-preserving uint64 form."""
         t, k = _abi.as_c(target_keys, np.uint64), _abi.as_c(lookup_keys, np.uint64)
         out, dup = np.empty(t.shape[0], np.int64), C.c_int32(0)
-        _check(lib.adh_mbr_index(self._s, t.shape[0], self._p(t, C.c_uint64), k.shape[0], self._p(k, C.c_uint64),
-                                 self._p(out, C.c_int64), C.byref(dup)), "adh_mbr_index")
+        _check(lib.adh_mbr_index(self._s, t.shape[0], _p(t, C.c_uint64), k.shape[0], _p(k, C.c_uint64),
+                                 _p(out, C.c_int64), C.byref(dup)), "adh_mbr_index")
         return out, bool(dup.value)
 
     def stats(self) -> dict:

@@ -1,5 +1,5 @@
-"""Resident extraction, host side (no GPU): the C prototypes of the two new entries against their ctypes
-declarations, the frames ResidentScores builds from a compact copy-out, and HipExtractionHandler.extract's
+"""Resident extraction, host side (no GPU): the ctypes declarations of the two entries and the compact
+output against the header, the frames ResidentScores builds from a compact copy-out, and HipExtractionHandler.extract's
 fallback decision and frame assembly, with stand-ins for the device."""
 
 import ctypes as C
@@ -19,24 +19,16 @@ from alphadia_amd.scoring import (DEFAULT_FEATURE_COLUMNS, FRAGMENT_DF_COLUMNS, 
                                   collect_candidates, collect_fragments_compact)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CTYPE_OF = {
-    "adh_handle_t *": C.c_void_p,
-    "const adh_candidates_t *": C.c_void_p,
-    "const adh_scoring_config_t *": C.c_void_p,
-    "const int64_t *": C.POINTER(C.c_int64),
-    "int64_t": C.c_int64,
-    "adh_compact_output_t *": C.POINTER(_abi.CompactOutput),
-}
 
 
 def test_resident_entries_match_the_header():
+    """The two entries take the structs themselves (tests/test_abi.py holds every prototype against the header), and
+    the compact output has the header's fields."""
     header = open(os.path.join(ROOT, "include", "alphadia_hip.h")).read()
-    for name, argtypes in _abi.RESIDENT_PROTOTYPES.items():
-        m = re.search(rf"\bint\s+{name}\s*\(([^)]*)\)\s*;", header)
-        assert m, name
-        params = [re.sub(r"\s+", " ", p).strip() for p in m.group(1).split(",")]
-        types = [re.sub(r"\s*\w+$", "", p).strip() for p in params]
-        assert [CTYPE_OF[t] for t in types] == argtypes, (name, types)
+    handle, table, config = C.c_void_p, C.POINTER(_abi.Candidates), C.POINTER(_abi.ScoringConfig)
+    assert _abi.PROTOTYPES["adh_score_candidates_resident"] == (C.c_int32, [handle, table, config])
+    assert _abi.PROTOTYPES["adh_take_rows"] == (C.c_int32, [handle, C.POINTER(C.c_int64), C.c_int64,
+                                                            C.POINTER(_abi.CompactOutput)])
     body = re.search(r"typedef struct adh_compact_output \{(.*?)\} adh_compact_output_t;", header, re.S).group(1)
     fields = re.findall(r"^\s*[\w ]+?\**\s*\**(\w+);", body, re.M)
     assert fields == [f for f, _ in _abi.CompactOutput._fields_]

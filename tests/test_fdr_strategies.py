@@ -2,7 +2,6 @@
 entry against its ctypes declaration, the NumPy restatement of the staging against the host manager's slicing
 (fdr_manager.py:178-223) on the golden's input table, and the golden's generator against the committed fixture."""
 
-import ctypes as C
 import os
 import re
 import subprocess
@@ -20,17 +19,6 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 sys.path.insert(0, GOLDEN)
 import make_golden_fdr_strategies as gen  # noqa: E402  (importing it runs nothing of the reference)
 
-CTYPE_OF = {
-    "adh_mlp_t *": C.c_void_p,
-    "const int32_t *": C.POINTER(C.c_int32),
-    "int32_t": C.c_int32,
-    "const float *const *": C.POINTER(C.POINTER(C.c_float)),
-    "const uint8_t *": C.POINTER(C.c_uint8),
-    "const int64_t *": C.POINTER(C.c_int64),
-    "int64_t": C.c_int64,
-    "int64_t *": C.POINTER(C.c_int64),
-}
-
 
 def _header_types(name):
     header = open(os.path.join(ROOT, "include", "alphadia_hip.h")).read()
@@ -41,12 +29,13 @@ def _header_types(name):
 
 
 def test_part_staging_entry_matches_the_header():
-    assert list(_abi.STAGE_PART_PROTOTYPES) == ["adh_mlp_stage_rows_device_part"]
-    for name, argtypes in _abi.STAGE_PART_PROTOTYPES.items():
-        types = _header_types(name)
-        assert [CTYPE_OF[t] for t in types] == argtypes, (name, types)
+    """tests/test_abi.py holds every prototype against the header; here, what the loaded library got and how the
+    part entry extends the whole-table one."""
+    for name in ("adh_mlp_stage_rows_device", "adh_mlp_stage_rows_device_part"):
+        restype, argtypes = _abi.PROTOTYPES[name]
+        assert len(_header_types(name)) == len(argtypes)
         assert name in runtime.EXPORTED_SYMBOLS
-        assert getattr(runtime.lib, name).argtypes == argtypes
+        assert getattr(runtime.lib, name).argtypes == argtypes and getattr(runtime.lib, name).restype is restype
     # the arguments of the existing entry plus channel, target_channel, decoy_channel, label_by_channel
     old, new = _header_types("adh_mlp_stage_rows_device"), _header_types("adh_mlp_stage_rows_device_part")
     assert new[: len(old) - 2] == old[:-2] and new[-2:] == old[-2:]

@@ -1,11 +1,10 @@
 """Host side of protein inference (alphadia_amd/grouping.py): the host restatement against the reference's goldens,
-the string plumbing on hand-made inputs, the error cases, the dispatch of apply_protein_inference and the C-ABI
-declarations of adh_pg_*.  No GPU needed."""
+the string plumbing on hand-made inputs, the error cases, and the dispatch of apply_protein_inference.
+No GPU needed."""
 
 from __future__ import annotations
 
 import os
-import re
 import subprocess
 import sys
 
@@ -14,7 +13,6 @@ import pandas as pd
 import pytest
 
 import grouping_golden as G
-from alphadia_amd import _abi
 from alphadia_amd import grouping as PG
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -109,19 +107,6 @@ def test_apply_protein_inference_dispatch(monkeypatch):
     assert out["pg"].equals(df["genes"]) and out["pg_master"].equals(df["genes"])
     with pytest.raises(ValueError, match="Unknown inference strategy"):
         PG.apply_protein_inference(G.table("genes"), "parsimony", "genes")
-
-
-def test_pg_abi_declarations_agree():
-    """Every adh_pg_* entry is declared in the header, prototyped in _abi with the header's parameter count, and
-    listed in runtime.EXPORTED_SYMBOLS (checked without loading the library)."""
-    header = open(os.path.join(ROOT, "include", "alphadia_hip.h")).read()
-    decl = {m.group(1): m.group(2) for m in re.finditer(r"\bint (adh_pg_[a-z_]+)\s*\(([^)]*)\)", header)}
-    assert set(decl) == set(_abi.PG_PROTOTYPES) and len(decl) == 6
-    for name, params in decl.items():
-        assert len(params.split(",")) == len(_abi.PG_PROTOTYPES[name]), name
-    src = open(os.path.join(ROOT, "alphadia_amd", "runtime.py")).read()
-    exported = re.search(r"EXPORTED_SYMBOLS = \[(.*?)\]", src, re.S).group(1)
-    assert set(decl) <= set(re.findall(r'"(adh_[a-z_0-9]+)"', exported))
 
 
 def _graph_of(case, k=0):

@@ -502,7 +502,6 @@ def test_chunk_cuts_report_the_count_they_need():
     from alphadia_amd import runtime
 
     fn = runtime.lib.adh_chunk_cuts
-    fn.argtypes = [C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64)]
     few, count = (C.c_int64 * 2)(-1, -1), C.c_int64(0)
     assert fn(375_000, 0, 0, 0, few, 2, C.byref(count)) == -1  # ADH_ERR_INVALID_ARGUMENT
     assert count.value == len(runtime.chunk_cuts(375_000)) and list(few) == [-1, -1]

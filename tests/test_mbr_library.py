@@ -122,16 +122,10 @@ def test_argument_validation():
 
 
 def test_mbr_abi_declarations_agree():
-    """Every adh_mbr_* entry is declared in the header, prototyped in _abi with the header's parameter count, and
-    listed in runtime.EXPORTED_SYMBOLS (checked without loading the library)."""
-    header = open(os.path.join(ROOT, "include", "alphadia_hip.h")).read()
-    decl = {m.group(1): m.group(2) for m in re.finditer(r"\bint (adh_mbr_[a-z_0-9]+)\s*\(([^)]*)\)", header)}
-    assert set(decl) == set(_abi.MBR_PROTOTYPES) and len(decl) == 11
-    for name, params in decl.items():
-        assert len(params.split(",")) == len(_abi.MBR_PROTOTYPES[name]), name
-    src = open(os.path.join(ROOT, "alphadia_amd", "runtime.py")).read()
-    exported = re.search(r"EXPORTED_SYMBOLS = \[(.*?)\]", src, re.S).group(1)
-    assert all(f'"{name}"' in exported for name in decl)
+    """Every adh_mbr_* entry of the prototype table (tests/test_abi.py holds it against the header) is defined in
+    adh_mbr_library.hip, which adh_api.hip includes (checked without loading the library)."""
+    decl = [name for name in _abi.PROTOTYPES if name.startswith("adh_mbr_")]
+    assert len(decl) == 11
     csrc = open(os.path.join(ROOT, "alphadia_amd", "csrc", "adh_mbr_library.hip")).read()
     assert all(re.search(rf"\bint {name}\(", csrc) for name in decl)
     assert '#include "adh_mbr_library.hip"' in open(os.path.join(ROOT, "alphadia_amd", "csrc", "adh_api.hip")).read()

@@ -1,38 +1,15 @@
-"""Resident optimisation steps, host side (no GPU): the C prototypes of the append entries against their ctypes
-declarations, HipOptimizationLock's batch plan, elution-group order and batch library, the accumulated tables'
-growth rule and relayout arithmetic against the table layout of the library, and the fallback of
-HipExtractionHandler.process_optimization_batch to the chained calls."""
+"""Resident optimisation steps, host side (no GPU): HipOptimizationLock's batch plan, elution-group order and batch
+library, the accumulated tables' growth rule and relayout arithmetic against the table layout of the library, and the
+fallback of HipExtractionHandler.process_optimization_batch to the chained calls."""
 
-import ctypes as C
-import os
-import re
 from types import SimpleNamespace
 
 import numpy as np
 import pandas as pd
 import pytest
 
-from alphadia_amd import _abi
 from alphadia_amd.optimization import (HipOptimizationLock, append_geometry, filter_fragments_for_calibration,
                                        relayout_rows, remove_unused_fragments)
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CTYPE_OF = {
-    "adh_handle_t *": C.c_void_p,
-    "const adh_candidates_t *": C.c_void_p,
-    "const adh_scoring_config_t *": C.c_void_p,
-    "int64_t *": C.POINTER(C.c_int64),
-}
-
-
-def test_append_entries_match_the_header():
-    header = open(os.path.join(ROOT, "include", "alphadia_hip.h")).read()
-    for name, argtypes in _abi.APPEND_PROTOTYPES.items():
-        m = re.search(rf"\bint\s+{name}\s*\(([^)]*)\)\s*;", header)
-        assert m, name
-        params = [re.sub(r"\s+", " ", p).strip() for p in m.group(1).split(",")]
-        types = [re.sub(r"\s*\w+$", "", p).strip() for p in params]
-        assert [CTYPE_OF[t] for t in types] == argtypes, (name, types)
 
 
 def _library(eg):

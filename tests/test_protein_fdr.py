@@ -169,16 +169,11 @@ def test_build_precursor_table_chain(monkeypatch):
 
 
 def test_pfdr_abi_declarations_agree():
-    """Every adh_pfdr_* entry is declared in the header, prototyped in _abi with the header's parameter count, listed
-    in runtime.EXPORTED_SYMBOLS and called by the wrapper class (checked without loading the library)."""
-    header = open(os.path.join(ROOT, "include", "alphadia_hip.h")).read()
-    decl = {m.group(1): m.group(2) for m in re.finditer(r"\bint (adh_pfdr_[a-z_]+)\s*\(([^)]*)\)", header)}
-    assert set(decl) == set(_abi.PFDR_PROTOTYPES) and len(decl) == 9
-    for name, params in decl.items():
-        assert len(params.split(",")) == len(_abi.PFDR_PROTOTYPES[name]), name
+    """Every adh_pfdr_* entry of the prototype table (tests/test_abi.py holds it against the header) is called by the
+    wrapper class and defined in adh_protein_fdr.hip, which adh_api.hip includes (checked without loading the library)."""
+    decl = [name for name in _abi.PROTOTYPES if name.startswith("adh_pfdr_")]
+    assert len(decl) == 9
     src = open(os.path.join(ROOT, "alphadia_amd", "runtime.py")).read()
-    exported = re.search(r"EXPORTED_SYMBOLS = \[(.*?)\]", src, re.S).group(1)
-    assert set(decl) <= set(re.findall(r'"(adh_[a-z_0-9]+)"', exported))
     wrapper = src[src.index("class DeviceProteinFdr"):]
     assert set(decl) == set(re.findall(r"lib\.(adh_pfdr_[a-z_]+)\(", wrapper))
     source = open(os.path.join(ROOT, "alphadia_amd", "csrc", "adh_protein_fdr.hip")).read()

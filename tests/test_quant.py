@@ -1,22 +1,17 @@
 """Host side of the cross-run fragment quantity matrices (alphadia_amd/quant.py): the host restatement of the
-reference's merges against the goldens, the duplicate-key path, the folder reader, the threshold rounding and the
-C-ABI declarations of adh_quant_*.  No GPU needed."""
+reference's merges against the goldens, the duplicate-key path, the folder reader and the threshold rounding.
+No GPU needed."""
 
 from __future__ import annotations
 
 import logging
-import os
-import re
 
 import numpy as np
 import pandas as pd
 import pytest
 
 import quant_golden as G
-from alphadia_amd import _abi
 from alphadia_amd import quant as Q
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.parametrize("case", G.cases())
@@ -111,17 +106,3 @@ def test_frag_reader_skips_missing_and_unreadable(tmp_path, caplog):
         pd.testing.assert_frame_equal(a, b)
     assert any("no frag file found for missing_run" in r.getMessage() for r in caplog.records)
     assert any("Error reading frag file for broken_run" in r.getMessage() for r in caplog.records)
-
-
-def test_quant_abi_declarations_agree():
-    """Every adh_quant_* entry is declared in the header, prototyped in _abi with the header's parameter count, and
-    listed in runtime.EXPORTED_SYMBOLS (checked without loading the library)."""
-    header = open(os.path.join(ROOT, "include", "alphadia_hip.h")).read()
-    decl = {m.group(1): m.group(2) for m in re.finditer(r"\bint (adh_quant_[a-z_]+)\s*\(([^)]*)\)", header)}
-    assert set(decl) == set(_abi.QUANT_PROTOTYPES)
-    for name, params in decl.items():
-        assert len(params.split(",")) == len(_abi.QUANT_PROTOTYPES[name]), name
-    src = open(os.path.join(ROOT, "alphadia_amd", "runtime.py")).read()
-    exported = re.search(r"EXPORTED_SYMBOLS = \[(.*?)\]", src, re.S).group(1)
-    assert set(decl) <= set(re.findall(r'"(adh_[a-z_0-9]+)"', exported))
-    assert "#define ADH_QUANT_MAX_COLUMNS 16" in header and _abi.QUANT_MAX_COLUMNS == 16

@@ -160,19 +160,13 @@ def test_empty_tables():
 
 
 def test_handover_abi_declarations_agree():
-    """Every hand-over entry is declared in the header, prototyped in _abi with the header's parameter count, listed
-    in runtime.EXPORTED_SYMBOLS and defined in adh_select_handover.hip, which adh_api.hip includes (no library loaded)."""
-    header = open(os.path.join(ROOT, "include", "alphadia_hip.h")).read()
+    """Every hand-over entry is in the prototype table (tests/test_abi.py holds it against the header), one after the
+    other as in the header, and defined in adh_select_handover.hip, which adh_api.hip includes (no library loaded)."""
     names = ["adh_select_candidates_resident", "adh_assemble_selected", "adh_select_handover_stats",
              "adh_score_selected_resident", "adh_selected_ids", "adh_take_selected"]
-    assert set(_abi.HANDOVER_PROTOTYPES) == set(names)
-    decl = {m.group(1): m.group(2) for m in re.finditer(r"\bint (adh_[a-z_0-9]+)\s*\(([^)]*)\)", header)}
-    src = open(os.path.join(ROOT, "alphadia_amd", "runtime.py")).read()
-    exported = re.search(r"EXPORTED_SYMBOLS = \[(.*?)\]", src, re.S).group(1)
+    table = list(_abi.PROTOTYPES)
+    assert table[table.index(names[0]):][: len(names)] == names
     csrc = open(os.path.join(ROOT, "alphadia_amd", "csrc", "adh_select_handover.hip")).read()
     for name in names:
-        assert name in decl, name
-        assert len(decl[name].split(",")) == len(_abi.HANDOVER_PROTOTYPES[name]), name
-        assert f'"{name}"' in exported, name
         assert re.search(rf"\bint {name}\(", csrc), name
     assert '#include "adh_select_handover.hip"' in open(os.path.join(ROOT, "alphadia_amd", "csrc", "adh_api.hip")).read()

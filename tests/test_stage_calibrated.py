@@ -1,5 +1,5 @@
-"""The library staged from its columns and calibrated in HBM, host side: the record dtype against the header, the
-prototypes, and the path ``HipCalibrationManager.predict_staged`` takes, against a context that only records calls.
+"""The library staged from its columns and calibrated in HBM, host side: the record dtype against the header
+and the path ``HipCalibrationManager.predict_staged`` takes, against a context that only records calls.
 The device side is in tests/test_stage_calibrated_gpu.py."""
 
 from __future__ import annotations
@@ -53,14 +53,6 @@ def test_record_dtype_matches_the_device_struct():
     for name, (_, at) in ((k, v[:2]) for k, v in _abi.LIB_RECORD_DTYPE.fields.items() if k != "pad"):
         assert offsets[name] == at, name
     assert offsets["pad0"] == _abi.LIB_RECORD_DTYPE.fields["pad"][1]
-
-
-def test_prototypes_are_declared_and_exported():
-    header = _header()
-    for name, argtypes in _abi.STAGE_LIB_PROTOTYPES.items():
-        params = re.search(rf"\bint {name}\(([^;]*?)\);", header, re.S).group(1)
-        assert len(params.split(",")) == len(argtypes), name
-        assert name in runtime.EXPORTED_SYMBOLS
 
 
 @pytest.mark.parametrize("name", [n for n in FITTED if CASES[n]["meta"]["dtype"] == "float32"])

@@ -5,7 +5,6 @@ the reference's own known answer of the MS2 quality control.  No GPU needed."""
 from __future__ import annotations
 
 import os
-import re
 
 import numpy as np
 import pandas as pd
@@ -153,15 +152,9 @@ def test_quality_control_refuses_overlapping_blocks():
 
 
 def test_tl_abi_declarations_agree():
-    """Every adh_tl_* entry is declared in the header, prototyped in _abi with the header's parameter count, and
-    listed in runtime.EXPORTED_SYMBOLS (checked without loading the library)."""
+    """The nine adh_tl_* entries of the prototype table (tests/test_abi.py holds it against the header) and the two
+    limits this module and the header share."""
     header = open(os.path.join(ROOT, "include", "alphadia_hip.h")).read()
-    decl = {m.group(1): m.group(2) for m in re.finditer(r"\bint (adh_tl_[a-z_0-9]+)\s*\(([^)]*)\)", header)}
-    assert set(decl) == set(_abi.TL_PROTOTYPES) and len(decl) == 9
-    for name, params in decl.items():
-        assert len(params.split(",")) == len(_abi.TL_PROTOTYPES[name]), name
-    src = open(os.path.join(ROOT, "alphadia_amd", "runtime.py")).read()
-    exported = re.search(r"EXPORTED_SYMBOLS = \[(.*?)\]", src, re.S).group(1)
-    assert set(decl) <= set(re.findall(r'"(adh_[a-z_0-9]+)"', exported))
+    assert len([name for name in _abi.PROTOTYPES if name.startswith("adh_tl_")]) == 9
     assert f"#define ADH_TL_QC_SLICE {_abi.TL_QC_SLICE}" in header and T.QC_LDS_SLICE == _abi.TL_QC_SLICE
     assert f"#define ADH_TL_MAX_MATRICES {_abi.TL_MAX_MATRICES}" in header
