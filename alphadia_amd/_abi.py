@@ -699,6 +699,9 @@ N_PLAN_CLASSES = 37  # the class table in include/alphadia_hip.h: adh_plan_class
 N_GENERIC_GROUPS = 3
 # ... and of the dynamic route of the ion-mobility feature kernel: adh_im_launch_stats
 N_IM_GROUPS = 3
+# ... and the values of adh_im_launch_routes, by their ADH_IM_LAYOUT_* / ADH_IM_LAUNCH_* numbers (0: the class is empty)
+IM_LAYOUTS = (None, "small", "common", "common2", "dynamic")
+IM_LAUNCHES = (None, "fused4", "tile4", "split1", "one")
 
 
 # the candidate library of transfer-library requantification built in HBM (adh_candidate_library.hip)
@@ -809,6 +812,7 @@ PROTOTYPES = {
     "adh_plan_class_counts": (_i32, [_vp, _i64p, _i32]),
     "adh_generic_launch_stats": (_i32, [_vp, _i64p, _i32]),
     "adh_im_launch_stats": (_i32, [_vp, _i64p, _i32]),
+    "adh_im_launch_routes": (_i32, [_i32, _i32, _i32, _i32, _i32, _i64p, C.POINTER(ScoringConfig), _i32p, _i32p]),
     # multi-GPU (RCCL behind the ABI)
     "adh_comm_unique_id": (_i32, [_vp]),
     "adh_comm_init": (_i32, [_vp, _i32, _i32, _vp, _i64]),

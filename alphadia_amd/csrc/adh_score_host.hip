@@ -529,9 +529,38 @@ void fold_timed(adh_handle *h, bool wait) {
     h->timed.resize(keep);
 }
 
+// The developer switches of an ion-mobility launch (ADH_DEBUG_IM*), read from the environment here and nowhere else,
+// once per call of launch_scoring: the tests flip them between calls on one handle.  (plan_key reads the plan's own.)
+struct ImSwitches {
+    int32_t stop_phase, drop_dense, stop4;
+    size_t gather_pad, feature_pad, tile4_two_pad;
+    bool dynamic_layout, no_split, no_split2, tile1, tile1_two, no_fuse4, no_tiles;
+};
+
+ImSwitches im_switches_from_env() {
+    auto number = [](const char *name) { const char *v = getenv(name); return v ? atoi(v) : 0; };
+    auto is_set = [](const char *name) { return getenv(name) != nullptr; };
+    ImSwitches sw{};
+    sw.stop_phase = number("ADH_DEBUG_IM");  // ablation stops of the gather and the one-kernel path (8: dense tiles only)
+    sw.drop_dense = number("ADH_DEBUG_IM_DROP_DENSE");
+    // extra LDS per block, to see what occupancy is worth: the gather, every feature launch, the two-observation tile4 launch alone
+    sw.gather_pad = (size_t)number("ADH_DEBUG_IM_GATHER_LDS_PAD");
+    sw.feature_pad = (size_t)number("ADH_DEBUG_IM_FEATURE_LDS_PAD");
+    sw.tile4_two_pad = (size_t)number("ADH_DEBUG_IM_TILE4_TWO_LDS_PAD");
+    sw.dynamic_layout = is_set("ADH_DEBUG_IM_DYNAMIC_LAYOUT");  // no fixed layout
+    sw.no_split = is_set("ADH_DEBUG_IM_NO_SPLIT");              // the one-kernel path for everything
+    sw.no_split2 = is_set("ADH_DEBUG_IM_NO_SPLIT2");            // ... for the two-observation class
+    sw.tile1 = is_set("ADH_DEBUG_IM_TILE1");                    // the one-candidate-per-wavefront tile kernel everywhere
+    sw.tile1_two = is_set("ADH_DEBUG_IM_TILE1_TWO");            // ... for the two-observation class
+    sw.no_fuse4 = is_set("ADH_DEBUG_IM_NO_FUSE4");              // tile and profile phase in two kernels
+    sw.stop4 = number("ADH_DEBUG_IM4");                         // ablation stops of the tile4 kernel (tile4_phase); not fused then
+    sw.no_tiles = is_set("ADH_DEBUG_IM_NO_TILES");  // A/B: the gather without the (window, TOF bin) ranges of the TOF-major events
+    return sw;
+}
+
 // What an ion-mobility plan is still refused for, before anything is launched or counted.  No candidate is refused for
 // the product of the call's maxima: every block of the dynamic route asks for its candidate's own layout.
-int refuse_im(const Plan &p) {
+int refuse_im(const Plan &p, const ImSwitches &sw) {
     char buf[256];
     if (p.im_over != 0) {
         // even the spill path keeps everything indexed by K * O and K, the template and the scan tables in LDS
@@ -543,9 +572,7 @@ int refuse_im(const Plan &p) {
                  (long long)p.im_over_shape[2], (long long)p.im_over_shape[3], (int)ADH_IM_LDS_LIMIT);
         return fail(ADH_ERR_UNSUPPORTED, buf);
     }
-    size_t g_pad = 0;
-    if (const char *dbg = getenv("ADH_DEBUG_IM_GATHER_LDS_PAD")) g_pad = (size_t)atoi(dbg);
-    const size_t g_lds = adh_gather_im_lds_bytes(p.caps_all) + g_pad;
+    const size_t g_lds = adh_gather_im_lds_bytes(p.caps_all) + sw.gather_pad;
     if (g_lds > 160 * 1024) {
         snprintf(buf, sizeof(buf),
                  "library slice of %d fragments needs %zu bytes of LDS in the ion-mobility gather kernel: exceeds 160 KiB",
@@ -555,61 +582,158 @@ int refuse_im(const Plan &p) {
     return ADH_OK;
 }
 
-int launch_scoring_im(adh_handle *h, Plan &p, const adh_scoring_config_t *cfg, adh_output_t *out, hipStream_t st) {
+// ---- the route of every plan class of an ion-mobility launch: im_launch_routes decides, launch_scoring_im follows
+struct ImRoute {
+    int32_t layout, launch;  // ADH_IM_LAYOUT_*, ADH_IM_LAUNCH_* (include/alphadia_hip.h: adh_im_launch_routes); 0: the class is empty
+    uint64_t prof_off;  // split launches: the class's profile records (ImProfRec) in the scratch slab
+    uint64_t side_off;  // fused4 / tile4: its side list (featim4::side_bytes: a counter and the plan positions)
+};
+struct ImRoutes {
+    ImRoute of[ADH_N_CLASSES];
+    uint64_t scratch_bytes;  // the plan's blocks, the profile records and the side lists behind them
+};
+
+// the maxima of the launch of plan class `c` (one launch per observation class: 1, 2, more; adh_plan_rec_im_kernel)
+Caps im_class_caps(Caps cc, int c) {
+    if (c == 0 || c == ADH_CLASS_IM_SMALL) cc.o = 1;
+    if (c == 1) cc.o = std::min(cc.o, 2);
+    if (c == ADH_CLASS_IM_SMALL) {  // (what the plan admitted to the class)
+        cc.k = std::min(cc.k, ADH_IM_SMALL_K);
+        cc.s = std::min(cc.s, ADH_IM_SMALL_S);
+        cc.f = std::min(cc.f, ADH_IM_SMALL_F);
+    }
+    return cc;
+}
+
+// The rule, and nothing else: no HIP call, no handle.  `caps`: the launch maxima (k, o, s, f and the isotopes i of the
+// call); `scratch_bytes`: the plan's blocks in the scratch slab.
+//  * Split feature path (adh_features_im2.hip): a one- or two-observation class whose maxima a fixed layout holds leaves
+//    a profile record per candidate behind the scratch blocks, and a second kernel with four candidates per wavefront
+//    finishes them.  Not with four isotopes, without experimental_xic or under a stop of the one-kernel path (8 is the
+//    gather's dense-tiles switch, no feature-kernel stop): the one-kernel path then, on a fixed layout where one holds
+//    the class (capacities fixed at compile time: adh_features_im.hip, DimsFix).
+//  * The tile part of a split class takes four candidates per wavefront (tile4, adh_features_im4.hip); the candidates
+//    it leaves aside (materialised tiles) are on the class's side list and taken by the first blocks of the same grid
+//    with the one-candidate body.  With one observation the profile phase runs in the same kernel (fused4).
+//    split1: the one-candidate-per-wavefront tile kernel, then the profile kernel.
+//  * Everything else: the dynamic route, every block with its candidate's own layout.
+ImRoutes im_launch_routes(const Caps &caps, const int64_t *n_class, const adh_scoring_config_t *cfg, const ImSwitches &sw,
+                          uint64_t scratch_bytes) {
+    using namespace featim;
+    const bool fixed = !sw.dynamic_layout;
+    const bool split_cfg = fixed && cfg->experimental_xic && (sw.stop_phase == 0 || sw.stop_phase == 8) && !sw.no_split && caps.i <= 3;
+    const bool tile4 = !sw.tile1;
+    const bool fuse4 = tile4 && !sw.no_fuse4 && sw.stop4 == 0;
+    const int32_t one_obs = fuse4 ? ADH_IM_LAUNCH_FUSED4 : tile4 ? ADH_IM_LAUNCH_TILE4 : ADH_IM_LAUNCH_SPLIT1;
+    const int32_t two_obs = tile4 && !sw.tile1_two ? ADH_IM_LAUNCH_TILE4 : ADH_IM_LAUNCH_SPLIT1;
+    ImRoutes r{};
+    for (int c = 0; c < ADH_N_CLASSES; ++c) {
+        if (n_class[c] <= 0) continue;
+        const Caps cc = im_class_caps(caps, c);
+        // (the small class was admitted candidate by candidate, plane size included: its axes alone are asked, and
+        // not the f >= 3 of the split path of the common shapes)
+        if (c == ADH_CLASS_IM_SMALL && fixed && DimsSmall::holds_axes(cc))
+            r.of[c] = {ADH_IM_LAYOUT_SMALL, split_cfg ? one_obs : ADH_IM_LAUNCH_ONE};
+        else if (c == 1 && split_cfg && DimsCommon2::holds(cc) && cc.f >= 3 && !sw.no_split2)
+            r.of[c] = {ADH_IM_LAYOUT_COMMON2, two_obs};
+        else if (fixed && DimsCommon::holds(cc))
+            r.of[c] = {ADH_IM_LAYOUT_COMMON, c == 0 && split_cfg && cc.f >= 3 ? one_obs : ADH_IM_LAUNCH_ONE};
+        else
+            r.of[c] = {ADH_IM_LAYOUT_DYNAMIC, ADH_IM_LAUNCH_ONE};
+    }
+    // behind the plan's blocks: the profile records of the split classes, then the side lists
+    static const int split_classes[3] = {0, ADH_CLASS_IM_SMALL, 1};
+    uint64_t at = (scratch_bytes + 255) / 256 * 256;
+    for (int c : split_classes) {
+        ImRoute &rt = r.of[c];
+        if (rt.launch == ADH_IM_LAUNCH_NONE || rt.launch == ADH_IM_LAUNCH_ONE) continue;
+        rt.prof_off = at;
+        at += (uint64_t)n_class[c] * (rt.layout == ADH_IM_LAYOUT_SMALL    ? sizeof(ImProfRec<DimsSmall::Fc, DimsSmall::Sc, 1>)
+                                      : rt.layout == ADH_IM_LAYOUT_COMMON ? sizeof(ImProfRec<DimsCommon::Fc, DimsCommon::Sc, 1>)
+                                                                          : sizeof(ImProfRec<DimsCommon2::Fc, DimsCommon2::Sc, 2>));
+    }
+    at = (at + 255) / 256 * 256;
+    for (int c : split_classes) {
+        ImRoute &rt = r.of[c];
+        if (rt.launch != ADH_IM_LAUNCH_FUSED4 && rt.launch != ADH_IM_LAUNCH_TILE4) continue;
+        rt.side_off = at;
+        at += featim4::side_bytes(n_class[c]);
+    }
+    r.scratch_bytes = at;
+    return r;
+}
+
+// The launches of `cnt` candidates of one plan class, from plan position `first`, on a fixed layout with NO observations.
+extern "C++" template <class Dims, class Layout, int NO>
+int launch_im_fixed(adh_handle *h, const Plan &p, const adh_scoring_config_t *cfg, adh_output_t *out, hipStream_t st,
+                    const ImSwitches &sw, const ImRoute &rt, const Caps &cc, int64_t first, int64_t cnt) {
+    constexpr int Fc = Dims::Fc, Sc = Dims::Sc;
+    const int32_t n_iso = h->cs.n_iso_cols;
+    const CandRecIM *recs = p.d_recs_im + first;
+    unsigned char *d_scratch = static_cast<unsigned char *>(h->scratch_slab);
+    unsigned char *prof = d_scratch + rt.prof_off;
+    uint32_t *side = reinterpret_cast<uint32_t *>(d_scratch + rt.side_off);
+    const size_t lay_lds = Layout(cc).bytes() + sw.feature_pad;
+    const unsigned groups = (unsigned)((cnt + ADH_WAVE / 16 - 1) / (ADH_WAVE / 16));
+    const unsigned list_blocks = (unsigned)std::min<int64_t>(cnt, 1024);  // (blocks that take the materialised tiles in turn)
+    if (rt.launch == ADH_IM_LAUNCH_FUSED4 || rt.launch == ADH_IM_LAUNCH_TILE4) {
+        const unsigned ob = (unsigned)((cnt + 255) / 256);
+        HIP_TRY(hipMemsetAsync(side, 0, featim4::SIDE_HEAD * 4, st));
+        hipLaunchKernelGGL(adh_im_order_hist_kernel, dim3(ob), dim3(256), 0, st, recs, (int32_t)cnt, d_scratch, side);
+        hipLaunchKernelGGL(adh_im_order_scatter_kernel, dim3(ob), dim3(256), 0, st, recs, (int32_t)cnt, d_scratch, side);
+    }
+    // (the kernels that take a whole class in one launch exist for one observation only)
+    const char *no_kernel = "ion-mobility launch: no kernel for this layout and launch kind";
+    switch (rt.launch) {
+        case ADH_IM_LAUNCH_FUSED4:
+            if constexpr (NO == 1) {
+                const size_t f4_lds = std::max({sizeof(featim4::WaveTile<Fc, Sc, 1>), sizeof(featim2::GroupLds<Fc, Sc, 1>) * (ADH_WAVE / 16),
+                                                lay_lds + ADH_IM_STATIC_LDS + 16});
+                hipLaunchKernelGGL((adh_feature_im_fused4_kernel<Fc, Sc, Layout>), dim3(groups + list_blocks), dim3(ADH_WAVE), f4_lds,
+                                   st, h->tims, recs, (int32_t)cnt, h->cs.iso, n_iso, *cfg, d_scratch, *out, side, cc,
+                                   (int32_t)list_blocks);
+                HIP_TRY(hipGetLastError());
+                return ADH_OK;
+            }
+            return fail(ADH_ERR_UNSUPPORTED, no_kernel);
+        case ADH_IM_LAUNCH_TILE4: {
+            const size_t t4_lds = std::max(sizeof(featim4::WaveTile<Fc, Sc, NO>), lay_lds + ADH_IM_STATIC_LDS + 16) +
+                                  (NO == 2 ? sw.tile4_two_pad : 0);
+            hipLaunchKernelGGL((adh_feature_im_tile4_kernel<Fc, Sc, NO, Layout>), dim3(groups + list_blocks), dim3(ADH_WAVE), t4_lds,
+                               st, h->tims, recs, (int32_t)cnt, h->cs.iso, n_iso, *cfg, d_scratch, *out, prof, side, cc,
+                               (int32_t)list_blocks, sw.stop4);
+            break;
+        }
+        case ADH_IM_LAUNCH_SPLIT1:
+            hipLaunchKernelGGL((adh_feature_im_kernel<Layout, true>), dim3((unsigned)cnt), dim3(ADH_WAVE), lay_lds, st, h->tims, recs,
+                               h->cs.iso, n_iso, *cfg, d_scratch, *out, cc, prof);
+            break;
+        case ADH_IM_LAUNCH_ONE:
+            if constexpr (NO == 1) {
+                hipLaunchKernelGGL(adh_feature_im_kernel<Layout>, dim3((unsigned)cnt), dim3(ADH_WAVE), lay_lds, st, h->tims, recs,
+                                   h->cs.iso, n_iso, *cfg, d_scratch, *out, cc);
+                HIP_TRY(hipGetLastError());
+                return ADH_OK;
+            }
+            return fail(ADH_ERR_UNSUPPORTED, no_kernel);
+        default: return fail(ADH_ERR_UNSUPPORTED, no_kernel);
+    }
+    hipLaunchKernelGGL((adh_feature_im_profiles_kernel<Fc, Sc, NO>), dim3(groups), dim3(ADH_WAVE), 0, st, h->tims, recs,
+                       (int32_t)cnt, *cfg, n_iso, d_scratch, prof, *out);
+    HIP_TRY(hipGetLastError());
+    return ADH_OK;
+}
+
+int launch_scoring_im(adh_handle *h, Plan &p, const adh_scoring_config_t *cfg, adh_output_t *out, hipStream_t st,
+                      const ImSwitches &sw) {
     if (cfg->collect_fragments && p.caps_all.k > out->top_k)
         return fail(ADH_ERR_INVALID_ARGUMENT, "output top_k smaller than config.top_k_fragments");
-    p.caps_all.stop_phase = 0;
-    if (const char *dbg = getenv("ADH_DEBUG_IM")) p.caps_all.stop_phase = atoi(dbg);
-    p.caps_all.dbg_drop_dense = 0;
-    if (const char *dbg = getenv("ADH_DEBUG_IM_DROP_DENSE")) p.caps_all.dbg_drop_dense = atoi(dbg);
-    size_t g_pad = 0, f_pad = 0;  // developer switches: extra LDS per block, to see what occupancy is worth
-    if (const char *dbg = getenv("ADH_DEBUG_IM_GATHER_LDS_PAD")) g_pad = (size_t)atoi(dbg);
-    if (const char *dbg = getenv("ADH_DEBUG_IM_FEATURE_LDS_PAD")) f_pad = (size_t)atoi(dbg);
-    const size_t g_lds = adh_gather_im_lds_bytes(p.caps_all) + g_pad;  // (within the LDS of a CU: refuse_im)
-    // Split feature path (adh_features_im2.hip): the one-observation classes with a fixed layout leave a profile
-    // record per candidate behind the scratch blocks, and a second kernel with four candidates per wavefront
-    // finishes them.  ADH_DEBUG_IM_NO_SPLIT=1: the one-kernel path for everything (the GPU suite holds both to
-    // identical bits); the developer ablations (ADH_DEBUG_IM stops, layout switch) belong to the one-kernel path.
+    p.caps_all.stop_phase = sw.stop_phase;
+    p.caps_all.dbg_drop_dense = sw.drop_dense;
+    const size_t g_lds = adh_gather_im_lds_bytes(p.caps_all) + sw.gather_pad;  // (within the LDS of a CU: refuse_im)
     const int32_t n_iso = h->cs.n_iso_cols;
-    const bool fixed_layouts = !getenv("ADH_DEBUG_IM_DYNAMIC_LAYOUT");
-    const bool split_cfg = fixed_layouts && cfg->experimental_xic && (p.caps_all.stop_phase == 0 || p.caps_all.stop_phase == 8) &&
-                           !getenv("ADH_DEBUG_IM_NO_SPLIT") &&  // (8: the gather's dense-tiles switch, no feature-kernel stop)
-                           std::min<uint32_t>(cfg->top_k_isotopes, (uint32_t)n_iso) <= 3;
-    auto class_caps = [&](int c) {
-        Caps cc = p.caps_all;
-        if (c == 0 || c == ADH_CLASS_IM_SMALL) cc.o = 1;
-        if (c == 1) cc.o = std::min(cc.o, 2);
-        if (c == ADH_CLASS_IM_SMALL) {  // (what the plan admitted to the class: adh_plan_rec_im_kernel)
-            cc.k = std::min(cc.k, ADH_IM_SMALL_K);
-            cc.s = std::min(cc.s, ADH_IM_SMALL_S);
-            cc.f = std::min(cc.f, ADH_IM_SMALL_F);
-        }
-        return cc;
-    };
-    typedef ImProfRec<featim::DimsCommon::Fc, featim::DimsCommon::Sc> ProfCommon;
-    typedef ImProfRec<featim::DimsSmall::Fc, featim::DimsSmall::Sc> ProfSmall;
-    const bool split_small = split_cfg && p.n_class[ADH_CLASS_IM_SMALL] > 0 && featim::DimsSmall::holds_axes(class_caps(ADH_CLASS_IM_SMALL));
-    const bool split_common = split_cfg && p.n_class[0] > 0 && featim::DimsCommon::holds(class_caps(0)) && class_caps(0).f >= 3;
-    typedef ImProfRec<featim::DimsCommon2::Fc, featim::DimsCommon2::Sc, 2> ProfCommon2;
-    const bool split_two = split_cfg && p.n_class[1] > 0 && featim::DimsCommon2::holds(class_caps(1)) && class_caps(1).f >= 3 &&
-                           !getenv("ADH_DEBUG_IM_NO_SPLIT2");
-    const uint64_t prof_base = (p.scratch_bytes + 255) / 256 * 256;
-    const uint64_t prof_small_off = prof_base + (split_common ? (uint64_t)p.n_class[0] * sizeof(ProfCommon) : 0);
-    const uint64_t prof_two_off = prof_small_off + (split_small ? (uint64_t)p.n_class[ADH_CLASS_IM_SMALL] * sizeof(ProfSmall) : 0);
-    const uint64_t prof_end = prof_two_off + (split_two ? (uint64_t)p.n_class[1] * sizeof(ProfCommon2) : 0);
-    // Round 6: the one-observation split classes go through adh_feature_im_tile4_kernel (four candidates per
-    // wavefront, adh_features_im4.hip); the candidates it leaves aside (materialised tiles) are listed behind the
-    // records - per class a counter and the plan positions - and taken by the first blocks of the same grid with the old body.
-    // ADH_DEBUG_IM_TILE1=1: the one-candidate-per-wavefront tile kernel everywhere.
-    const bool tile4 = !getenv("ADH_DEBUG_IM_TILE1");
-    const int32_t stop4 = getenv("ADH_DEBUG_IM4") ? atoi(getenv("ADH_DEBUG_IM4")) : 0;  // developer ablation (tile4_phase)
-    const uint64_t list_common_off = (prof_end + 255) / 256 * 256;
-    const uint64_t list_small_off = list_common_off + (tile4 && split_common ? featim4::side_bytes(p.n_class[0]) : 0);
-    const uint64_t list_two_off = list_small_off + (tile4 && split_small ? featim4::side_bytes(p.n_class[ADH_CLASS_IM_SMALL]) : 0);
-    const bool fuse4 = tile4 && !getenv("ADH_DEBUG_IM_NO_FUSE4") && stop4 == 0;  // (tile + profile phase in one kernel, one observation)
-    const bool tile4_two = tile4 && !getenv("ADH_DEBUG_IM_TILE1_TWO");  // (A/B: the two-observation class through the one-candidate kernel)
-    const uint64_t prof_bytes = list_two_off + (tile4_two && split_two ? featim4::side_bytes(p.n_class[1]) : 0);
-    int rc = ensure_scratch(h, prof_bytes);
+    const ImRoutes routes = im_launch_routes(p.caps_all, p.n_class, cfg, sw, p.scratch_bytes);
+    int rc = ensure_scratch(h, routes.scratch_bytes);
     if (rc != ADH_OK) return rc;
     unsigned char *d_scratch = static_cast<unsigned char *>(h->scratch_slab);
     adh_handle::Timed t;
@@ -619,150 +743,48 @@ int launch_scoring_im(adh_handle *h, Plan &p, const adh_scoring_config_t *cfg, a
     if (rc != ADH_OK) return rc;
     HIP_TRY(hipEventRecord(t.e0, st));
     DevTims run_view = h->tims;
-    if (getenv("ADH_DEBUG_IM_NO_TILES")) run_view.tile_ev = nullptr;  // A/B: the (window, TOF bin) ranges of the TOF-major events
+    if (sw.no_tiles) run_view.tile_ev = nullptr;
     hipLaunchKernelGGL(adh_gather_im_kernel, dim3((unsigned)p.n), dim3(ADH_WAVE), g_lds, st, run_view, h->d_lib,
                        p.d_recs_im, *cfg, n_iso, d_scratch, *out, p.caps_all);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(t.e1, st));
-    {
-        // one feature launch per observation class (adh_plan_rec_im_kernel): 1, 2, more
-        int64_t first = 0;
-        for (int c = 0; c < ADH_N_CLASSES; ++c) {
-            const int64_t cnt = p.n_class[c];
-            if (cnt > 0) {
-                const Caps cc = class_caps(c);
-                // (capacities fixed at compile time for the common shape: adh_features_im.hip, DimsFix)
-                const bool fixed_ok = fixed_layouts;
-                const bool common = featim::DimsCommon::holds(cc) && fixed_ok;
-                const unsigned groups = (unsigned)((cnt + ADH_WAVE / 16 - 1) / (ADH_WAVE / 16));
-                const unsigned list_blocks = (unsigned)std::min<int64_t>(cnt, 1024);  // (blocks that take the materialised tiles in turn)
-                if (c == ADH_CLASS_IM_SMALL && split_small) {
-                    unsigned char *prof = d_scratch + prof_small_off;
-                    if (tile4) {
-                        uint32_t *side = reinterpret_cast<uint32_t *>(d_scratch + list_small_off);
-                        const unsigned ob = (unsigned)((cnt + 255) / 256);
-                        HIP_TRY(hipMemsetAsync(side, 0, featim4::SIDE_HEAD * 4, st));
-                        hipLaunchKernelGGL(adh_im_order_hist_kernel, dim3(ob), dim3(256), 0, st, p.d_recs_im + first, (int32_t)cnt,
-                                           d_scratch, side);
-                        hipLaunchKernelGGL(adh_im_order_scatter_kernel, dim3(ob), dim3(256), 0, st, p.d_recs_im + first, (int32_t)cnt,
-                                           d_scratch, side);
-                        if (fuse4) {
-                            const size_t f4_lds = std::max({sizeof(featim4::WaveTile<featim::DimsSmall::Fc, featim::DimsSmall::Sc, 1>),
-                                                            sizeof(featim2::GroupLds<featim::DimsSmall::Fc, featim::DimsSmall::Sc, 1>) * (ADH_WAVE / 16),
-                                                            featim::LayoutSmall(cc).bytes() + f_pad + ADH_IM_STATIC_LDS + 16});
-                            hipLaunchKernelGGL((adh_feature_im_fused4_kernel<featim::DimsSmall::Fc, featim::DimsSmall::Sc, featim::LayoutSmall>),
-                                               dim3(groups + list_blocks), dim3(ADH_WAVE), f4_lds, st, h->tims, p.d_recs_im + first,
-                                               (int32_t)cnt, h->cs.iso, n_iso, *cfg, d_scratch, *out, side, cc, (int32_t)list_blocks);
-                            HIP_TRY(hipGetLastError());
-                            first += cnt;
-                            continue;
-                        }
-                        const size_t t4_lds = std::max(sizeof(featim4::WaveTile<featim::DimsSmall::Fc, featim::DimsSmall::Sc, 1>), featim::LayoutSmall(cc).bytes() + f_pad + ADH_IM_STATIC_LDS + 16);
-                        hipLaunchKernelGGL((adh_feature_im_tile4_kernel<featim::DimsSmall::Fc, featim::DimsSmall::Sc, 1, featim::LayoutSmall>),
-                                           dim3(groups + list_blocks), dim3(ADH_WAVE), t4_lds, st, h->tims, p.d_recs_im + first,
-                                           (int32_t)cnt, h->cs.iso, n_iso, *cfg, d_scratch, *out, prof, side, cc,
-                                           (int32_t)list_blocks, stop4);
-                    } else
-                    hipLaunchKernelGGL((adh_feature_im_kernel<featim::LayoutSmall, true>), dim3((unsigned)cnt), dim3(ADH_WAVE),
-                                       featim::LayoutSmall(cc).bytes() + f_pad, st, h->tims, p.d_recs_im + first, h->cs.iso, n_iso,
-                                       *cfg, d_scratch, *out, cc, prof);
-                    hipLaunchKernelGGL((adh_feature_im_profiles_kernel<featim::DimsSmall::Fc, featim::DimsSmall::Sc, 1>), dim3(groups),
-                                       dim3(ADH_WAVE), 0, st, h->tims, p.d_recs_im + first, (int32_t)cnt, *cfg, n_iso, d_scratch,
-                                       prof, *out);
-                } else if (c == 1 && split_two) {
-                    unsigned char *prof = d_scratch + prof_two_off;
-                    if (tile4_two) {
-                        uint32_t *side = reinterpret_cast<uint32_t *>(d_scratch + list_two_off);
-                        const unsigned ob = (unsigned)((cnt + 255) / 256);
-                        HIP_TRY(hipMemsetAsync(side, 0, featim4::SIDE_HEAD * 4, st));
-                        hipLaunchKernelGGL(adh_im_order_hist_kernel, dim3(ob), dim3(256), 0, st, p.d_recs_im + first, (int32_t)cnt,
-                                           d_scratch, side);
-                        hipLaunchKernelGGL(adh_im_order_scatter_kernel, dim3(ob), dim3(256), 0, st, p.d_recs_im + first, (int32_t)cnt,
-                                           d_scratch, side);
-                        // (ADH_DEBUG_IM_TILE4_TWO_LDS_PAD: extra LDS for this launch alone, to see what its occupancy is worth)
-                        const size_t t42_pad = getenv("ADH_DEBUG_IM_TILE4_TWO_LDS_PAD") ? (size_t)atoi(getenv("ADH_DEBUG_IM_TILE4_TWO_LDS_PAD")) : 0;
-                        const size_t t4_lds = std::max(sizeof(featim4::WaveTile<featim::DimsCommon2::Fc, featim::DimsCommon2::Sc, 2>),
-                                                       featim::LayoutCommon2(cc).bytes() + f_pad + ADH_IM_STATIC_LDS + 16) + t42_pad;
-                        hipLaunchKernelGGL((adh_feature_im_tile4_kernel<featim::DimsCommon2::Fc, featim::DimsCommon2::Sc, 2, featim::LayoutCommon2>),
-                                           dim3(groups + list_blocks), dim3(ADH_WAVE), t4_lds, st, h->tims, p.d_recs_im + first,
-                                           (int32_t)cnt, h->cs.iso, n_iso, *cfg, d_scratch, *out, prof, side, cc,
-                                           (int32_t)list_blocks, stop4);
-                    } else
-                    hipLaunchKernelGGL((adh_feature_im_kernel<featim::LayoutCommon2, true>), dim3((unsigned)cnt), dim3(ADH_WAVE),
-                                       featim::LayoutCommon2(cc).bytes() + f_pad, st, h->tims, p.d_recs_im + first, h->cs.iso, n_iso,
-                                       *cfg, d_scratch, *out, cc, prof);
-                    hipLaunchKernelGGL((adh_feature_im_profiles_kernel<featim::DimsCommon2::Fc, featim::DimsCommon2::Sc, 2>),
-                                       dim3(groups), dim3(ADH_WAVE), 0, st, h->tims, p.d_recs_im + first, (int32_t)cnt, *cfg, n_iso,
-                                       d_scratch, prof, *out);
-                } else if (c == 0 && split_common) {
-                    unsigned char *prof = d_scratch + prof_base;
-                    if (tile4) {
-                        uint32_t *side = reinterpret_cast<uint32_t *>(d_scratch + list_common_off);
-                        const unsigned ob = (unsigned)((cnt + 255) / 256);
-                        HIP_TRY(hipMemsetAsync(side, 0, featim4::SIDE_HEAD * 4, st));
-                        hipLaunchKernelGGL(adh_im_order_hist_kernel, dim3(ob), dim3(256), 0, st, p.d_recs_im + first, (int32_t)cnt,
-                                           d_scratch, side);
-                        hipLaunchKernelGGL(adh_im_order_scatter_kernel, dim3(ob), dim3(256), 0, st, p.d_recs_im + first, (int32_t)cnt,
-                                           d_scratch, side);
-                        if (fuse4) {
-                            const size_t f4_lds = std::max({sizeof(featim4::WaveTile<featim::DimsCommon::Fc, featim::DimsCommon::Sc, 1>),
-                                                            sizeof(featim2::GroupLds<featim::DimsCommon::Fc, featim::DimsCommon::Sc, 1>) * (ADH_WAVE / 16),
-                                                            featim::LayoutCommon(cc).bytes() + f_pad + ADH_IM_STATIC_LDS + 16});
-                            hipLaunchKernelGGL((adh_feature_im_fused4_kernel<featim::DimsCommon::Fc, featim::DimsCommon::Sc, featim::LayoutCommon>),
-                                               dim3(groups + list_blocks), dim3(ADH_WAVE), f4_lds, st, h->tims, p.d_recs_im + first,
-                                               (int32_t)cnt, h->cs.iso, n_iso, *cfg, d_scratch, *out, side, cc, (int32_t)list_blocks);
-                            HIP_TRY(hipGetLastError());
-                            first += cnt;
-                            continue;
-                        }
-                        const size_t t4_lds = std::max(sizeof(featim4::WaveTile<featim::DimsCommon::Fc, featim::DimsCommon::Sc, 1>), featim::LayoutCommon(cc).bytes() + f_pad + ADH_IM_STATIC_LDS + 16);
-                        hipLaunchKernelGGL((adh_feature_im_tile4_kernel<featim::DimsCommon::Fc, featim::DimsCommon::Sc, 1, featim::LayoutCommon>),
-                                           dim3(groups + list_blocks), dim3(ADH_WAVE), t4_lds, st, h->tims, p.d_recs_im + first,
-                                           (int32_t)cnt, h->cs.iso, n_iso, *cfg, d_scratch, *out, prof, side, cc,
-                                           (int32_t)list_blocks, stop4);
-                    } else
-                    hipLaunchKernelGGL((adh_feature_im_kernel<featim::LayoutCommon, true>), dim3((unsigned)cnt), dim3(ADH_WAVE),
-                                       featim::LayoutCommon(cc).bytes() + f_pad, st, h->tims, p.d_recs_im + first, h->cs.iso, n_iso,
-                                       *cfg, d_scratch, *out, cc, prof);
-                    hipLaunchKernelGGL((adh_feature_im_profiles_kernel<featim::DimsCommon::Fc, featim::DimsCommon::Sc, 1>), dim3(groups),
-                                       dim3(ADH_WAVE), 0, st, h->tims, p.d_recs_im + first, (int32_t)cnt, *cfg, n_iso, d_scratch,
-                                       prof, *out);
-                } else if (c == ADH_CLASS_IM_SMALL && featim::DimsSmall::holds_axes(cc) && fixed_ok)
-                    hipLaunchKernelGGL(adh_feature_im_kernel<featim::LayoutSmall>, dim3((unsigned)cnt), dim3(ADH_WAVE),
-                                       featim::LayoutSmall(cc).bytes() + f_pad, st, h->tims, p.d_recs_im + first, h->cs.iso, n_iso,
-                                       *cfg, d_scratch, *out, cc);
-                else if (common)
-                    hipLaunchKernelGGL(adh_feature_im_kernel<featim::LayoutCommon>, dim3((unsigned)cnt), dim3(ADH_WAVE),
-                                       featim::LayoutCommon(cc).bytes() + f_pad, st, h->tims, p.d_recs_im + first, h->cs.iso, n_iso,
-                                       *cfg, d_scratch, *out, cc);
-                else {
-                    // the dynamic route: one launch per group of own layouts, each with the LDS of its largest candidate
-                    // (the plan sorted the class by group); the last group keeps its profile regions in the spill blocks
-                    // of the scratch slab
-                    const int sl = c == ADH_CLASS_GENERIC ? ADH_IM_CLASS_SLOTS - 1 : c;
-                    int64_t at = 0;
-                    for (int g = 0; g < ADH_IM_GROUPS; ++g) {
-                        const int64_t ng = p.n_im[sl][g];
-                        if (ng == 0) continue;
-                        const size_t lds = (size_t)p.lds_im[sl][g];
-                        const size_t lds_pad = std::min<size_t>(lds + f_pad, ADH_IM_LDS_LIMIT);
-                        if (g == ADH_IM_GROUP_SPILL)
-                            hipLaunchKernelGGL(adh_feature_im_own_kernel<true>, dim3((unsigned)ng), dim3(ADH_WAVE), lds_pad, st, h->tims,
-                                               p.d_recs_im + first + at, h->cs.iso, n_iso, *cfg, d_scratch, d_scratch, *out, cc);
-                        else
-                            hipLaunchKernelGGL(adh_feature_im_own_kernel<false>, dim3((unsigned)ng), dim3(ADH_WAVE), lds_pad, st, h->tims,
-                                               p.d_recs_im + first + at, h->cs.iso, n_iso, *cfg, d_scratch, (unsigned char *)nullptr,
-                                               *out, cc);
-                        HIP_TRY(hipGetLastError());
-                        h->im_stats[g] += ng;
-                        h->im_stats[ADH_IM_GROUPS + g] = std::max<int64_t>(h->im_stats[ADH_IM_GROUPS + g], (int64_t)lds);
-                        at += ng;
-                    }
-                }
+    int64_t first = 0;
+    for (int c = 0; c < ADH_N_CLASSES; first += p.n_class[c], ++c) {
+        const int64_t cnt = p.n_class[c];
+        if (cnt <= 0) continue;
+        const ImRoute &rt = routes.of[c];
+        const Caps cc = im_class_caps(p.caps_all, c);
+        if (rt.layout == ADH_IM_LAYOUT_SMALL)
+            rc = launch_im_fixed<featim::DimsSmall, featim::LayoutSmall, 1>(h, p, cfg, out, st, sw, rt, cc, first, cnt);
+        else if (rt.layout == ADH_IM_LAYOUT_COMMON2)
+            rc = launch_im_fixed<featim::DimsCommon2, featim::LayoutCommon2, 2>(h, p, cfg, out, st, sw, rt, cc, first, cnt);
+        else if (rt.layout == ADH_IM_LAYOUT_COMMON)
+            rc = launch_im_fixed<featim::DimsCommon, featim::LayoutCommon, 1>(h, p, cfg, out, st, sw, rt, cc, first, cnt);
+        else {
+            // the dynamic route: one launch per group of own layouts, each with the LDS of its largest candidate
+            // (the plan sorted the class by group); the last group keeps its profile regions in the spill blocks
+            // of the scratch slab
+            const int sl = c == ADH_CLASS_GENERIC ? ADH_IM_CLASS_SLOTS - 1 : c;
+            int64_t at = 0;
+            for (int g = 0; g < ADH_IM_GROUPS; ++g) {
+                const int64_t ng = p.n_im[sl][g];
+                if (ng == 0) continue;
+                const size_t lds = (size_t)p.lds_im[sl][g];
+                const size_t lds_pad = std::min<size_t>(lds + sw.feature_pad, ADH_IM_LDS_LIMIT);
+                if (g == ADH_IM_GROUP_SPILL)
+                    hipLaunchKernelGGL(adh_feature_im_own_kernel<true>, dim3((unsigned)ng), dim3(ADH_WAVE), lds_pad, st, h->tims,
+                                       p.d_recs_im + first + at, h->cs.iso, n_iso, *cfg, d_scratch, d_scratch, *out, cc);
+                else
+                    hipLaunchKernelGGL(adh_feature_im_own_kernel<false>, dim3((unsigned)ng), dim3(ADH_WAVE), lds_pad, st, h->tims,
+                                       p.d_recs_im + first + at, h->cs.iso, n_iso, *cfg, d_scratch, (unsigned char *)nullptr,
+                                       *out, cc);
                 HIP_TRY(hipGetLastError());
+                h->im_stats[g] += ng;
+                h->im_stats[ADH_IM_GROUPS + g] = std::max<int64_t>(h->im_stats[ADH_IM_GROUPS + g], (int64_t)lds);
+                at += ng;
             }
-            first += cnt;
         }
+        if (rc != ADH_OK) return rc;
     }
     HIP_TRY(hipEventRecord(t.e2, st));
     h->timed.push_back(t);
@@ -783,12 +805,13 @@ int launch_scoring(adh_handle *h, Plan &p, const adh_scoring_config_t *cfg, adh_
                  (unsigned long long)(p.generic_over & 0xFFu), (int)ADH_GENERIC_LDS_LIMIT);
         return fail(ADH_ERR_UNSUPPORTED, buf);
     }
+    const ImSwitches im_sw = h->tims_staged ? im_switches_from_env() : ImSwitches{};
     if (h->tims_staged) {
-        const int rc = refuse_im(p);
+        const int rc = refuse_im(p, im_sw);
         if (rc != ADH_OK) return rc;
     }
     for (int c = 0; c < ADH_N_CLASSES; ++c) h->class_counts[c] += p.n_class[c];
-    if (h->tims_staged) return launch_scoring_im(h, p, cfg, out, st);
+    if (h->tims_staged) return launch_scoring_im(h, p, cfg, out, st, im_sw);
     if (cfg->collect_fragments && p.caps_all.k > out->top_k)
         return fail(ADH_ERR_INVALID_ARGUMENT, "output top_k smaller than config.top_k_fragments");
     int stop_phase = 0;
@@ -849,52 +872,19 @@ int launch_scoring(adh_handle *h, Plan &p, const adh_scoring_config_t *cfg, adh_
         }
         // tile width: 15 columns while lane 15 carries no isotope, 16 with four isotopes (adh_fused.hip)
         const bool wide = std::min<uint32_t>(cfg->top_k_isotopes, (uint32_t)n_iso) > 3;
-        // The launches of a chunk write disjoint rows and read nothing of each other, and the smaller ones (long rows,
-        // two observations: 10-20 % of a chunk each) keep the GPU for a wavefront lifetime or two (70-100 us) that
-        // they do not fill.  Running them side by side was measured in round 5 and is OFF: on side streams that fork
-        // from the caller's and join it again (ADH_FUSED_STREAMS=2 / 3) one side stream changes nothing (3 M rows:
-        // 14.77 against 14.79 ms of kernels, 375 000 rows in 9 chunks 3.46 against 3.61) and a second one doubles the
-        // kernel time (27.7 ms: its hardware queue is shared with the copy streams and its launches start ~250 us
-        // late, `rocprofv3 --kernel-trace`); without the barrier bit on one stream (hipExtAnyOrderLaunch) nothing
-        // changes on gfx950.  What did help: fewer launches (the two-observation classes in one, above).
-        int n_streams = 1;
-        if (const char *env = getenv("ADH_FUSED_STREAMS")) n_streams = std::min(std::max(atoi(env), 1), 3);
-        int n_launch = 0;
-        for (int w = 0; w < 4; ++w) n_launch += fblocks[w] > 0;
-        if (n_launch < 2) n_streams = 1;
-        for (int a = 0; a + 1 < n_streams; ++a) {
-            if (!h->stream_aux[a]) HIP_TRY(hipStreamCreateWithFlags(&h->stream_aux[a], hipStreamNonBlocking));
-            if (!h->ev_aux[a]) HIP_TRY(hipEventCreateWithFlags(&h->ev_aux[a], hipEventDisableTiming));
-        }
-        bool used[2] = {false, false};
-        int launched = 0;
-        hipStream_t lst = st;
-        if (n_streams > 1) HIP_TRY(hipEventRecord(h->ev_fork, st));
-#define ADH_LAUNCH_FUSED_TW(W, FM_MIN, FM_MAX, NO, TW)                                                                    \
-    hipLaunchKernelGGL((adh_fused_kernel<FM_MIN, FM_MAX, NO, TW>), dim3((unsigned)fblocks[W]), dim3(ADH_WAVE), 0, lst,   \
+        // (the launches of a chunk stay on ONE stream: side streams were measured and bring nothing)
+#define ADH_LAUNCH_FUSED_TW(W, FM_MIN, FM_MAX, NO, TW)                                                                   \
+    hipLaunchKernelGGL((adh_fused_kernel<FM_MIN, FM_MAX, NO, TW>), dim3((unsigned)fblocks[W]), dim3(ADH_WAVE), 0, st,    \
                        (FusedArgs{h->run, h->d_lib, p.d_recs, fcs[W], h->cs.iso, (int32_t)n_iso, *cfg, h->d_wtp, *out, (int32_t)stop_phase}))
 #define ADH_LAUNCH_FUSED(W, FM_MIN, FM_MAX, NO)                                                 \
     if (fblocks[W] > 0) {                                                                       \
-        lst = st;                                                                               \
-        if (n_streams > 1 && launched > 0) {                                                    \
-            const int a = std::min(launched - 1, n_streams - 2);                                \
-            lst = h->stream_aux[a];                                                             \
-            if (!used[a]) HIP_TRY(hipStreamWaitEvent(lst, h->ev_fork, 0));                      \
-            used[a] = true;                                                                     \
-        }                                                                                       \
         if (wide) ADH_LAUNCH_FUSED_TW(W, FM_MIN, FM_MAX, NO, 16);                               \
         else ADH_LAUNCH_FUSED_TW(W, FM_MIN, FM_MAX, NO, ADH_FUSED_TW3);                         \
         HIP_TRY(hipGetLastError());                                                             \
-        ++launched;                                                                             \
     }
         ADH_LAUNCH_FUSED(0, 8, ADH_FUSED_FM3, 1)
         ADH_LAUNCH_FUSED(1, ADH_FUSED_FM3 + 4, 32, 1)
         ADH_LAUNCH_FUSED(2, 8, 32, 2)
-        for (int a = 0; a < 2; ++a) {
-            if (!used[a]) continue;
-            HIP_TRY(hipEventRecord(h->ev_aux[a], h->stream_aux[a]));
-            HIP_TRY(hipStreamWaitEvent(st, h->ev_aux[a], 0));
-        }
 #undef ADH_LAUNCH_FUSED
 #undef ADH_LAUNCH_FUSED_TW
     }
@@ -1236,6 +1226,16 @@ int adh_im_launch_stats(adh_handle_t *h, int64_t *stats, int32_t reset) {
         stats[i] = h->im_stats[i];
         if (reset) h->im_stats[i] = 0;
     }
+    return ADH_OK;
+}
+
+int adh_im_launch_routes(int32_t k, int32_t o, int32_t s, int32_t f, int32_t i, const int64_t *n_class,
+                         const adh_scoring_config_t *config, int32_t *layout, int32_t *launch) {
+    if (!n_class || !config || !layout || !launch) return fail(ADH_ERR_INVALID_ARGUMENT, "NULL argument");
+    Caps caps{};
+    caps.k = k, caps.o = o, caps.s = s, caps.f = f, caps.i = i;
+    const ImRoutes routes = im_launch_routes(caps, n_class, config, im_switches_from_env(), 0);
+    for (int c = 0; c < ADH_N_CLASSES; ++c) layout[c] = routes.of[c].layout, launch[c] = routes.of[c].launch;
     return ADH_OK;
 }
 

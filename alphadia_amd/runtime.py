@@ -96,6 +96,21 @@ def chunk_cuts(n_rows: int, ion_mobility: bool = False, max_rows: int = 0, packe
     return list(cuts[: count.value])
 
 
+def im_launch_routes(caps: dict, n_class: dict, cfg) -> dict:
+    """The library's ``adh_im_launch_routes``: {plan class: (layout, launch)} of an ion-mobility launch with the maxima
+    ``caps`` (k, o, s, f and the isotopes i) and ``n_class`` candidates per plan class, for every class that holds any -
+    the rule the launches follow.  ``cfg``: a scoring config, or one ``_abi.pack_config`` packed already.  Reads the
+    ``ADH_DEBUG_IM*`` switches; needs no GPU."""
+    counts = (C.c_int64 * _abi.N_PLAN_CLASSES)()
+    for cls, n in n_class.items():
+        counts[cls] = int(n)
+    layout, launch = (C.c_int32 * _abi.N_PLAN_CLASSES)(), (C.c_int32 * _abi.N_PLAN_CLASSES)()
+    packed = cfg if isinstance(cfg, _abi.ScoringConfig) else _abi.pack_config(cfg)
+    _check(lib.adh_im_launch_routes(*(int(caps[a]) for a in "kosfi"), counts, C.byref(packed), layout, launch),
+           "adh_im_launch_routes")
+    return {c: (_abi.IM_LAYOUTS[layout[c]], _abi.IM_LAUNCHES[launch[c]]) for c in range(_abi.N_PLAN_CLASSES) if layout[c]}
+
+
 _pylib = None       # the same library through ctypes.PyDLL: calls keep the GIL (adh_host_take_objects needs that)
 _OBJ_TAKE = None    # None: not probed yet; True / False: the threaded object gather is usable
 

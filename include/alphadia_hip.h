@@ -495,6 +495,32 @@ int adh_generic_launch_stats(adh_handle_t *handle, int64_t *stats, int32_t reset
 #define ADH_IM_LAUNCH_STATS 6
 int adh_im_launch_stats(adh_handle_t *handle, int64_t *stats, int32_t reset);
 
+/*
+ * The route every plan class of an ion-mobility launch takes: the rule the launches themselves follow, as a call of
+ * its own.  In: the launch maxima - fragments kept k, observations o, scans s, cycles f - and the isotopes i of the
+ * call, the candidates per plan class (`n_class[37]`, the classes of adh_plan_class_counts) and the scoring config.
+ * Reads the ADH_DEBUG_IM* launch switches as a launch does.  Out, per plan class (`layout[37]`, `launch[37]`; both 0
+ * for a class without candidates):
+ *   layout  the capacities of the feature kernel: fixed at compile time for small tiles (1), for the common shape
+ *           with one observation (2) or two (3), or every block with its candidate's own (4: the dynamic route, whose
+ *           launch groups adh_im_launch_stats counts)
+ *   launch  tile and profile phase in one kernel with four candidates per wavefront (1), the tile phase so and then
+ *           the profile kernel (2), one candidate per wavefront and then the profile kernel (3), the one-kernel path (4)
+ * Every route computes the same bits: tests use this call to know which routes their inputs reach.  Needs no GPU.
+ */
+#define ADH_IM_LAYOUT_NONE 0
+#define ADH_IM_LAYOUT_SMALL 1
+#define ADH_IM_LAYOUT_COMMON 2
+#define ADH_IM_LAYOUT_COMMON2 3
+#define ADH_IM_LAYOUT_DYNAMIC 4
+#define ADH_IM_LAUNCH_NONE 0
+#define ADH_IM_LAUNCH_FUSED4 1
+#define ADH_IM_LAUNCH_TILE4 2
+#define ADH_IM_LAUNCH_SPLIT1 3
+#define ADH_IM_LAUNCH_ONE 4
+int adh_im_launch_routes(int32_t k, int32_t o, int32_t s, int32_t f, int32_t i, const int64_t *n_class,
+                         const adh_scoring_config_t *config, int32_t *layout, int32_t *launch);
+
 /* ------------------------------------------------------------------------
  * Multi-GPU: one process per GPU, candidates sharded by contiguous score-group ranges
  * (score groups are independent, search/scoring/containers/score_group.py:66-75), ONE RCCL

@@ -514,18 +514,21 @@ def _class_caps(caps: dict, cls: int) -> dict:
 
 
 def instantiation_of(caps: dict, n_class: dict, cfg, env: dict | None = None) -> dict:
-    """launch_scoring_im (adh_score_host.hip): per plan class of a launch the layout of the feature kernel ('small',
-    'common', 'common2', 'dynamic') and the launch ('fused4': tile and profile phase in one kernel, four candidates per
-    wavefront; 'tile4': the tile phase so, then the profile kernel; 'split1': one candidate per wavefront, then the
-    profile kernel; 'one': the one-kernel path).  ``caps``: the launch maxima k, o, s, f and the isotope count i;
-    ``n_class``: candidates per plan class; ``env``: the ADH_DEBUG_IM* switches that are set."""
+    """im_launch_routes (adh_score_host.hip), the rule launch_scoring_im follows, restated to be read: per plan class
+    of a launch the layout of the feature kernel ('small', 'common', 'common2', 'dynamic') and the launch ('fused4':
+    tile and profile phase in one kernel, four candidates per wavefront; 'tile4': the tile phase so, then the profile
+    kernel; 'split1': one candidate per wavefront, then the profile kernel; 'one': the one-kernel path).  ``caps``: the
+    launch maxima k, o, s, f and the isotope count i; ``n_class``: candidates per plan class; ``env``: the
+    ADH_DEBUG_IM* switches that are set.  The library exports the rule itself as ``adh_im_launch_routes``
+    (``runtime.im_launch_routes``); tests/test_kernel_classes_im.py holds this copy equal to it on both sides of
+    every limit and under every switch."""
     env = env or {}
     stop = int(env.get("ADH_DEBUG_IM", 0))
     fixed = "ADH_DEBUG_IM_DYNAMIC_LAYOUT" not in env
     split_cfg = (fixed and bool(cfg.experimental_xic) and stop in (0, 8) and "ADH_DEBUG_IM_NO_SPLIT" not in env
                  and min(int(cfg.top_k_isotopes), N_ISOTOPE_COLUMNS) <= 3)
     tile4 = "ADH_DEBUG_IM_TILE1" not in env
-    fuse4 = tile4 and "ADH_DEBUG_IM_NO_FUSE4" not in env
+    fuse4 = tile4 and "ADH_DEBUG_IM_NO_FUSE4" not in env and int(env.get("ADH_DEBUG_IM4", 0)) == 0  # (an ablation stop of tile4)
     tile4_two = tile4 and "ADH_DEBUG_IM_TILE1_TWO" not in env
     out = {}
     for cls, cnt in n_class.items():

@@ -1,6 +1,6 @@
 """The ion-mobility shape sweep of tests/box_sweep_im.py meets its coverage conditions with the ORACLE alone (no GPU):
 the boxes are what the specification says, the two restated routing rules are pinned on hand-written cases on both sides
-of every limit, every (plan class, layout, launch) a configuration can reach holds enough candidates the oracle scores as
+of every limit and the launch rule is held equal to the library's own (``adh_im_launch_routes``), every (plan class, layout, launch) a configuration can reach holds enough candidates the oracle scores as
 valid, the designed event counts of the density rows - counted from the run arrays - lie on the designed side of the
 capacities of the gather kernel, and no batch needs more LDS than a launch may have.  These are conditions on the
 inputs of tests/test_kernel_classes_im_gpu.py, not measurements of the kernels."""
@@ -153,10 +153,58 @@ def test_instantiation_rule_restated():
     assert t1[bi.CLASS_ONE] == ("common", "split1") and t1[bi.CLASS_SMALL] == ("small", "split1") and t1[bi.CLASS_TWO] == ("common2", "split1")
     nf = inst(env={"ADH_DEBUG_IM_NO_FUSE4": "1"})
     assert nf[bi.CLASS_ONE] == ("common", "tile4") and nf[bi.CLASS_SMALL] == ("small", "tile4") and nf[bi.CLASS_TWO] == ("common2", "tile4")
-    assert inst(env={"ADH_DEBUG_IM_TILE1_TWO": "1"}) == {**at, bi.CLASS_TWO: ("common2", "split1")}
+    assert inst(env={"ADH_DEBUG_IM4": "1"}) == nf                   # (an ablation stop of the tile4 kernel: not fused)
+    assert inst(env={"ADH_DEBUG_IM_TILE1_TWO": "1"}) =={**at, bi.CLASS_TWO: ("common2", "split1")}
     assert inst(env={"ADH_DEBUG_IM_NO_SPLIT2": "1"}) == {**at, bi.CLASS_TWO: ("dynamic", "one")}
     assert inst(env={"ADH_DEBUG_IM": "8"}) == at and inst(env={"ADH_DEBUG_IM": "14"}) == inst(cfg=no_xic)
     assert inst(n_class={bi.CLASS_TWO: 3}) == {bi.CLASS_TWO: ("common2", "tile4")}
+
+
+# every switch of the routing rule, each on its own: the launch switches of WAYS in test_kernel_classes_im_gpu.py, and the
+# ablation stop of the tile4 kernel
+ROUTING_SWITCHES = [("ADH_DEBUG_IM_NO_SPLIT", "1"), ("ADH_DEBUG_IM_TILE1", "1"), ("ADH_DEBUG_IM_NO_FUSE4", "1"),
+                    ("ADH_DEBUG_IM_TILE1_TWO", "1"), ("ADH_DEBUG_IM_NO_SPLIT2", "1"), ("ADH_DEBUG_IM_DYNAMIC_LAYOUT", "1"),
+                    ("ADH_DEBUG_IM", "8"), ("ADH_DEBUG_IM", "14"), ("ADH_DEBUG_IM4", "1")]
+
+
+def test_instantiation_rule_is_the_librarys(monkeypatch):
+    """``bi.instantiation_of`` - what ``routes_of`` and ``REACHES`` reason with - against the rule the launches follow
+    (``adh_im_launch_routes``, no GPU) on a grid that straddles every limit of the rule: 12 / 13 kept fragments, one,
+    two and more observations, the scan, cycle and plane limits of the small and the common layouts, f >= 3 of the
+    split path, with and without the split path, one, three and four isotopes, all four classes and each alone, no
+    switch and each routing switch on its own."""
+    from alphadia_amd import _abi, runtime
+
+    for name in {s for s, _ in ROUTING_SWITCHES}:
+        monkeypatch.delenv(name, raising=False)
+    classes = (bi.CLASS_ONE, bi.CLASS_TWO, bi.CLASS_SMALL, bi.CLASS_GENERIC)
+    populations = [{c: 5 for c in classes}] + [{c: 3} for c in classes]
+    configs = [(cfg, _abi.pack_config(cfg), max(min(int(cfg.top_k_isotopes), bi.N_ISOTOPE_COLUMNS), 1))
+               for cfg in (bi.config_of(n) for n in ("defaults", "no_xic", "isotopes1", "isotopes4"))]
+    assert sorted(i for _, _, i in configs) == [1, 3, 3, 4]
+    n, seen = 0, set()
+    for switch in [None] + ROUTING_SWITCHES:
+        with monkeypatch.context() as mp:
+            env = {}
+            if switch is not None:
+                mp.setenv(*switch)
+                env = dict([switch])
+            for cfg, packed, i in configs:
+                for k in (12, 13):
+                    for o in (1, 2, 3, 8):
+                        for s in (2, 32, 33, 36, 37, 40, 41, 48):
+                            for f in (2, 3, 24, 25, 28, 29, 32, 33, 36):
+                                caps = dict(k=k, o=o, s=s, f=f, i=i)
+                                for n_class in populations:
+                                    want = runtime.im_launch_routes(caps, n_class, packed)
+                                    assert bi.instantiation_of(caps, n_class, cfg, env) == want, (switch, caps, n_class)
+                                    seen.update(want.values())
+                                    n += 1
+    assert n == 10 * 4 * 2 * 4 * 8 * 9 * 5
+    # (the grid reaches every pair the rule can give)
+    assert seen == {("small", "fused4"), ("small", "tile4"), ("small", "split1"), ("small", "one"), ("common", "fused4"),
+                    ("common", "tile4"), ("common", "split1"), ("common", "one"), ("common2", "tile4"), ("common2", "split1"),
+                    ("dynamic", "one")}
 
 
 @pytest.mark.parametrize("name", list(bi.CONFIGS))
