@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <functional>
@@ -385,7 +386,7 @@ struct adh_handle {
     uint64_t im_scratch_budget = 0; // bytes the scratch of one ion-mobility chunk may reserve (0: not asked yet)
     std::vector<float> h_rt;        // host copy of the run's rt_values (selection sizes its tiles with it)
     std::vector<double> h_rt_im, h_mobility_im;  // the same for an ion-mobility run
-    double last_select_ms = 0.0;    // duration of the last adh_select_kernel launch
+    double last_select_ms = 0.0;    // HIP-event time of the selection kernels of the last successful call (all batches)
     fragcomp::Stats last_fragcomp;  // of the last adh_fragcomp / adh_fdr_resident call
     // The runtime's DMA copies run at half the link rate (25-29 instead of 55 GB/s) from the moment this process has
     // freed a device buffer of 2 GB or more - the temporaries of staging a run do - until it page-locks 2 GB of host
@@ -403,7 +404,7 @@ struct adh_handle {
         const uint32_t *precursor_idx = nullptr, *frag_start = nullptr, *frag_stop = nullptr, *elution_group = nullptr;
         const uint8_t *charge = nullptr, *decoy = nullptr, *channel = nullptr;
         const float *mz = nullptr, *iso = nullptr;
-        const uint32_t *t_u32[9] = {nullptr};  // the candidate table, in the order of adh_candidate_table_t (1: u8, 2: f32)
+        DevCandTable table{};                  // the candidate table
         uint32_t longest = 0;                  // longest library slice of the assembled table
         int64_t im_cells = 1;                  // largest scans x cycles tile of the assembled table
         int32_t stats[4] = {0, 0, 0, 0};       // was_sorted, radix passes, score-group scans, rows flagged FLAG_SKIP
@@ -1271,505 +1272,19 @@ int adh_stage_fragments(adh_handle_t *h, const adh_fragments_t *f) {
 
 namespace {
 
-// the per-precursor id columns of adh_select_candidates_resident (host)
-struct SelIds {
-    const uint32_t *elution_group_idx;
-    const uint8_t *decoy, *channel;
-};
-
-// what a resident selection left in the slab, for adh_assemble_selected
-void note_selected(adh_handle *h, const adh_precursors_t *pc, const adh_selection_config_t *cfg, unsigned char *slab,
-                   const size_t *o_prec, const size_t *o_out) {
-    adh_handle::Selected &s = h->sel;
-    s = adh_handle::Selected();
-    s.n_prec = pc->n;
-    s.cand_count = cfg->candidate_count;
-    s.n_iso_cols = pc->n_isotope_cols;
-    s.precursor_idx = reinterpret_cast<const uint32_t *>(slab + o_prec[0]);
-    s.frag_start = reinterpret_cast<const uint32_t *>(slab + o_prec[1]);
-    s.frag_stop = reinterpret_cast<const uint32_t *>(slab + o_prec[2]);
-    s.charge = slab + o_prec[3];
-    s.mz = reinterpret_cast<const float *>(slab + o_prec[4]);
-    s.iso = reinterpret_cast<const float *>(slab + o_prec[5]);
-    s.elution_group = reinterpret_cast<const uint32_t *>(slab + o_prec[6]);
-    s.decoy = slab + o_prec[7];
-    s.channel = slab + o_prec[8];
-    for (int f = 0; f < 9; ++f) s.t_u32[f] = reinterpret_cast<const uint32_t *>(slab + o_out[f]);
-    s.stage = 1;
+// Two pieces of ion-mobility selection's host code (adh_select_host.hip) stay here, where its drivers were: a kernel
+// template is emitted where it is first named, and these name the scan kernels for 64-bit sums and
+// adh_select_smooth_im_kernel<> ahead of everything below, so the code object keeps its order.  The inclusive sums of
+// the precursors' scratch sizes (tmp == NULL asks for the bytes of temporary storage), and the tile kernels' LDS limit:
+hipError_t select_need_sums(void *tmp, size_t &bytes, unsigned long long *need, unsigned long long *cum, int64_t n, hipStream_t st) {
+    return hipcub::DeviceScan::InclusiveSum(tmp, bytes, need, cum, (int)n, st);
 }
-
-// Candidate selection on the staged ion-mobility run (see adh_select_im.hip); the caller has
-// validated the arguments and zero-filled the host table.  `ids` (adh_select_candidates_resident): the table stays in
-// the slab, with the id columns and the isotope columns beside it, and nothing is copied out.
-int select_candidates_im(adh_handle *h, const adh_precursors_t *pc, const adh_selection_config_t *cfg,
-                         const float *kernel, int32_t k0, int32_t k1, adh_candidate_table_t *out, const SelIds *ids) {
-    const int64_t n = pc->n;
-    const DevTims &T = h->tims;
-    const int L = T.cycle_len, SM = T.scan_max, z = T.zeroth;
-    if (!pc->mobility) return fail(ADH_ERR_INVALID_ARGUMENT, "precursor mobility column is NULL");
-    auto now = [] {
-        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-    };
-    const bool timing = getenv("ADH_DEBUG_TIMING") != nullptr;
-    const double t_0 = now();
-    // rank-1 factors of the kernel (it is an outer product up to float32 rounding of its entries)
-    std::vector<double> ku((size_t)k0), kv((size_t)k1);
-    {
-        const int a0 = k0 / 2, b0 = k1 / 2;
-        const double c = (double)kernel[a0 * k1 + b0];
-        if (!(c > 0)) return fail(ADH_ERR_UNSUPPORTED, "smoothing kernel without a positive centre");
-        for (int a = 0; a < k0; ++a) ku[(size_t)a] = (double)kernel[a * k1 + b0] / c;
-        for (int b = 0; b < k1; ++b) kv[(size_t)b] = (double)kernel[a0 * k1 + b];
-        for (int a = 0; a < k0; ++a)
-            for (int b = 0; b < k1; ++b)
-                if (std::fabs(ku[(size_t)a] * kv[(size_t)b] - (double)kernel[a * k1 + b]) > 1e-5 * c + 1e-30)
-                    return fail(ADH_ERR_UNSUPPORTED, "smoothing kernel is not separable (not an outer product)");
-    }
-    const int n_iso = (int)std::min<int64_t>(cfg->top_k_precursors, pc->n_isotope_cols);
-    // One grow-only slab of the handle: precursor columns, plan records, their scratch sizes, the candidate table.
-    // The plan (limits, validity, empty-query test) is a kernel (adh_select_plan_im_kernel); the host only cuts
-    // the batches.
-    void *host_out[] = {out->precursor_idx, out->rank, out->score, out->scan_center, out->scan_start,
-                        out->scan_stop, out->frame_center, out->frame_start, out->frame_stop};
-    const size_t width[] = {4, 1, 4, 4, 4, 4, 4, 4, 4};
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t at = off;
-        off += (bytes + 255) / 256 * 256;
-        return at;
-    };
-    const size_t o_idx = carve((size_t)n * 4), o_fs = carve((size_t)n * 4), o_fe = carve((size_t)n * 4), o_ch = carve((size_t)n),
-                 o_rt = carve((size_t)n * 4), o_mob = carve((size_t)n * 4), o_mz = carve((size_t)n * 4),
-                 o_recs = carve((size_t)n * sizeof(selim::PrecRec)), o_need = carve((size_t)n * 8), o_cum = carve((size_t)n * 8),
-                 o_red = carve(64), o_ku = carve((size_t)k0 * 8), o_kv = carve((size_t)k1 * 8), o_first = carve((size_t)(n + 2) * 8);
-    size_t scan_bytes = 0;
-    HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, (unsigned long long *)nullptr, (unsigned long long *)nullptr, (int)n,
-                                             h->stream));
-    const size_t o_tmp = carve(scan_bytes);
-    size_t o_iso = 0, o_eg = 0, o_dc = 0, o_chn = 0;
-    if (ids) {
-        o_iso = carve((size_t)n * pc->n_isotope_cols * 4);
-        o_eg = carve((size_t)n * 4), o_dc = carve((size_t)n), o_chn = carve((size_t)n);
-    }
-    size_t o_out[9];
-    for (int f = 0; f < 9; ++f) o_out[f] = carve((size_t)out->n * width[f]);
-    if (h->sel_slab_bytes < off) {
-        HIP_TRY(hipDeviceSynchronize());
-        if (h->sel_slab) (void)hipFree(h->sel_slab);
-        h->sel_slab = nullptr;
-        h->sel_slab_bytes = 0;
-        const hipError_t e = hipMalloc(&h->sel_slab, off);
-        if (e != hipSuccess) return fail(ADH_ERR_OUT_OF_MEMORY, std::string("hipMalloc(selection slab): ") + hipGetErrorString(e));
-        h->sel_slab_bytes = off;
-    }
-    unsigned char *slab = static_cast<unsigned char *>(h->sel_slab);
-    auto put = [&](size_t at, const void *src, size_t bytes) -> hipError_t {
-        return bytes ? hipMemcpyAsync(slab + at, src, bytes, hipMemcpyHostToDevice, h->stream) : hipSuccess;
-    };
-    hipError_t e = put(o_idx, pc->precursor_idx, (size_t)n * 4);
-    if (e == hipSuccess) e = put(o_fs, pc->frag_start_idx, (size_t)n * 4);
-    if (e == hipSuccess) e = put(o_fe, pc->frag_stop_idx, (size_t)n * 4);
-    if (e == hipSuccess) e = put(o_ch, pc->charge, (size_t)n);
-    if (e == hipSuccess) e = put(o_rt, pc->rt, (size_t)n * 4);
-    if (e == hipSuccess) e = put(o_mob, pc->mobility, (size_t)n * 4);
-    if (e == hipSuccess) e = put(o_mz, pc->mz, (size_t)n * 4);
-    if (e == hipSuccess) e = put(o_ku, ku.data(), (size_t)k0 * 8);
-    if (e == hipSuccess) e = put(o_kv, kv.data(), (size_t)k1 * 8);
-    if (ids) {
-        if (e == hipSuccess) e = put(o_iso, pc->isotope_intensity, (size_t)n * pc->n_isotope_cols * 4);
-        if (e == hipSuccess) e = put(o_eg, ids->elution_group_idx, (size_t)n * 4);
-        if (e == hipSuccess) e = put(o_dc, ids->decoy, (size_t)n);
-        if (e == hipSuccess) e = put(o_chn, ids->channel, (size_t)n);
-    }
-    if (e == hipSuccess) e = hipMemsetAsync(slab + o_red, 0, 64, h->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(slab + o_out[0], 0, off - o_out[0], h->stream);  // (rows without a candidate stay zero)
-    if (e != hipSuccess) return fail(ADH_ERR_HIP, std::string("selection upload: ") + hipGetErrorString(e));
-    SelPlanIn pin{};
-    pin.precursor_idx = reinterpret_cast<const uint32_t *>(slab + o_idx);
-    pin.frag_start = reinterpret_cast<const uint32_t *>(slab + o_fs);
-    pin.frag_stop = reinterpret_cast<const uint32_t *>(slab + o_fe);
-    pin.charge = slab + o_ch;
-    pin.rt = reinterpret_cast<const float *>(slab + o_rt);
-    pin.mobility = reinterpret_cast<const float *>(slab + o_mob);
-    pin.mz = reinterpret_cast<const float *>(slab + o_mz);
-    selim::PrecRec *d_recs = reinterpret_cast<selim::PrecRec *>(slab + o_recs);
-    unsigned long long *d_need = reinterpret_cast<unsigned long long *>(slab + o_need);
-    unsigned long long *d_cum = reinterpret_cast<unsigned long long *>(slab + o_cum);
-    int32_t *d_red = reinterpret_cast<int32_t *>(slab + o_red);
-    unsigned long long *d_biggest = reinterpret_cast<unsigned long long *>(slab + o_red + 32);
-    hipLaunchKernelGGL(adh_select_plan_im_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, T, pin, n, h->n_lib,
-                       n_iso, cfg->rt_tolerance, cfg->mobility_tolerance, cfg->kernel_size, (int)k0, (int)k1, d_recs, d_need, d_red,
-                       d_biggest);
-    e = hipGetLastError();
-    size_t tb = scan_bytes;
-    if (e == hipSuccess) e = hipcub::DeviceScan::InclusiveSum(slab + o_tmp, tb, d_need, d_cum, (int)n, h->stream);
-    struct {
-        int32_t red[8];
-        unsigned long long biggest, pad;
-    } meta;
-    unsigned long long all = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&meta, slab + o_red, 48, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&all, d_cum + (n - 1), 8, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) return fail(ADH_ERR_HIP, std::string("selection plan: ") + hipGetErrorString(e));
-    if (meta.red[0] & 1) return fail(ADH_ERR_INVALID_ARGUMENT, "fragment slice outside the staged library");
-    if (meta.red[0] & 2) return fail(ADH_ERR_INVALID_ARGUMENT, "precursor charge must be > 0");
-    if (meta.red[0] & 4) return fail(ADH_ERR_UNSUPPORTED, "more than 64 m/z windows per precursor");
-    int32_t cap_cells = std::max(meta.red[1], 1), cap_s = std::max(meta.red[2], 1), cap_f = std::max(meta.red[3], 1);
-    cap_cells = (cap_cells + 1) & ~1;  // the float64 kernel factors follow the float tiles in LDS
-    const int tap_budget = adh_select_tap_budget(cap_cells, cap_s, k0, k1);
-    const size_t lds_smooth = adh_select_smooth_im_lds_bytes(cap_cells, cap_s, k0, k1, tap_budget);
-    const size_t lds = std::max(lds_smooth, adh_select_score_im_lds_bytes(cap_cells, cap_s, cap_f));
-    if (lds > 150 * 1024 || cap_f > selim::SCORE_THREADS) {
-        char buf[200];
-        snprintf(buf, sizeof(buf), "selection tile of %d cells (scans x cycles, %d cycles) needs %zu bytes of LDS: exceeds 150 KiB",
-                 cap_cells, cap_f, lds);
-        return fail(ADH_ERR_UNSUPPORTED, buf);
-    }
-    // batches of precursors whose tiles fit a bounded scratch slab: the scratch slab of the handle is used (kept
-    // between calls; only reserved memory: a precursor's tiles are normally kept in sparse form and touch a few KB of
-    // their block); batches follow each other on the stream, so a batch may reuse the slab of the one before without
-    // the host waiting
-    uint64_t budget = 8ull << 30;
-    const char *budget_env = getenv("ADH_SELECT_SCRATCH_MB");
-    if (budget_env) budget = (uint64_t)atoll(budget_env) << 20;
-    budget = std::max<uint64_t>(std::min<uint64_t>(budget, all), meta.biggest);
-    // (a bigger slab is there already: fewer batches - unless the budget was set by hand, which is how the tests
-    // reach the cutting of batches)
-    if (!budget_env) budget = std::max<uint64_t>(budget, h->scratch_slab_bytes);
-    const double t_plan = now();
-    int rc = ADH_OK;
-    std::vector<int64_t> first{0};  // first precursor of every batch, then n
-    if (all > budget) {
-        // the longest prefixes that fit: the inclusive sums come back and are cut on the host
-        std::vector<unsigned long long> cum((size_t)n);
-        HIP_TRY(hipMemcpy(cum.data(), d_cum, (size_t)n * 8, hipMemcpyDeviceToHost));
-        while (first.back() < n) {
-            const int64_t f0 = first.back();
-            const unsigned long long base = f0 > 0 ? cum[(size_t)f0 - 1] : 0ull;
-            const int64_t last = std::upper_bound(cum.begin() + f0, cum.end(), base + budget) - cum.begin();
-            if (last == f0) return fail(ADH_ERR_UNSUPPORTED, "one precursor's tiles exceed the selection scratch budget");
-            first.push_back(last);
-        }
-    } else {
-        first.push_back(n);
-    }
-    const int n_batches = (int)first.size() - 1;
-    int64_t *d_first = reinterpret_cast<int64_t *>(slab + o_first);
-    HIP_TRY(hipMemcpyAsync(d_first, first.data(), first.size() * 8, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(adh_select_offsets_im_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, d_recs, d_cum, d_need,
-                       n, d_first, n_batches);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(h->stream));  // (first lives on this stack frame)
-    const double *d_ku = reinterpret_cast<const double *>(slab + o_ku), *d_kv = reinterpret_cast<const double *>(slab + o_kv);
-    DevCandTable dt{};
-    dt.precursor_idx = reinterpret_cast<uint32_t *>(slab + o_out[0]);
-    dt.rank = slab + o_out[1];
-    dt.score = reinterpret_cast<float *>(slab + o_out[2]);
-    dt.scan_center = reinterpret_cast<uint32_t *>(slab + o_out[3]);
-    dt.scan_start = reinterpret_cast<uint32_t *>(slab + o_out[4]);
-    dt.scan_stop = reinterpret_cast<uint32_t *>(slab + o_out[5]);
-    dt.frame_center = reinterpret_cast<uint32_t *>(slab + o_out[6]);
-    dt.frame_start = reinterpret_cast<uint32_t *>(slab + o_out[7]);
-    dt.frame_stop = reinterpret_cast<uint32_t *>(slab + o_out[8]);
-    unsigned char *d_scratch = nullptr;
-    if (h->scratch_slab_bytes < budget) {
-        // (exactly the budget: ensure_scratch's head-room is for scoring batches that grow from call to call)
-        e = hipDeviceSynchronize();
-        if (h->scratch_slab) (void)hipFree(h->scratch_slab);
-        h->scratch_slab = nullptr;
-        h->scratch_slab_bytes = 0;
-        if (e == hipSuccess) e = hipMalloc(&h->scratch_slab, budget);
-        if (e != hipSuccess) return fail(ADH_ERR_OUT_OF_MEMORY, std::string("hipMalloc(selection scratch): ") + hipGetErrorString(e));
-        h->scratch_slab_bytes = budget;
-    }
-    d_scratch = static_cast<unsigned char *>(h->scratch_slab);
-    double total_ms = 0.0;
-    const double t_alloc = now();
-    {
-        (void)hipFuncSetAttribute((const void *)adh_select_score_im_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  150 * 1024);
-        (void)hipFuncSetAttribute((const void *)adh_select_smooth_im_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  150 * 1024);
-        (void)hipFuncSetAttribute((const void *)adh_select_smooth_im_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  150 * 1024);
-        (void)hipGetLastError();
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        (void)hipEventCreate(&e0);
-        (void)hipEventCreate(&e1);
-        int32_t debug_dense = 0;
-        if (const char *dbg = getenv("ADH_DEBUG_SELECT_IM_DENSE")) debug_dense = atoi(dbg);
-        int32_t debug_abl = 0;
-        if (const char *dbg = getenv("ADH_DEBUG_SELECT_IM_ABL")) debug_abl = atoi(dbg);
-        e = hipEventRecord(e0, h->stream);
-        for (int b = 0; b < n_batches && e == hipSuccess; ++b) {
-            const int64_t b0 = first[(size_t)b];
-            const int32_t cnt = (int32_t)(first[(size_t)b + 1] - b0);
-            hipLaunchKernelGGL(adh_select_gather_im_kernel, dim3((unsigned)cnt), dim3(ADH_WAVE), 0, h->stream, T,
-                               h->d_lib, d_recs + b0, cnt, *cfg, (int32_t)n_iso, d_scratch, debug_dense);
-            if (debug_abl != 0)
-                hipLaunchKernelGGL(adh_select_smooth_im_kernel<true>, dim3((unsigned)cnt), dim3(selim::SMOOTH_THREADS), lds_smooth,
-                                   h->stream, d_recs + b0, cnt, d_ku, d_kv, k0, k1, cap_cells, cap_s, d_scratch, debug_abl,
-                                   (int32_t)tap_budget);
-            else
-                hipLaunchKernelGGL(adh_select_smooth_im_kernel<false>, dim3((unsigned)cnt), dim3(selim::SMOOTH_THREADS), lds_smooth,
-                                   h->stream, d_recs + b0, cnt, d_ku, d_kv, k0, k1, cap_cells, cap_s, d_scratch, debug_abl,
-                                   (int32_t)tap_budget);
-            hipLaunchKernelGGL(adh_select_score_im_kernel, dim3((unsigned)cnt), dim3(selim::SCORE_THREADS),
-                               adh_select_score_im_lds_bytes(cap_cells, cap_s, cap_f), h->stream, T, d_recs + b0, cnt, b0, *cfg,
-                               cap_cells, cap_s, cap_f, d_scratch, dt);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipEventRecord(e1, h->stream);
-        for (int f = 0; f < 9 && e == hipSuccess && !ids; ++f)
-            e = hipMemcpyAsync(host_out[f], slab + o_out[f], (size_t)out->n * width[f], hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) rc = fail(ADH_ERR_HIP, std::string("ion-mobility selection kernels: ") + hipGetErrorString(e));
-        if (rc == ADH_OK && !ids) h->d2h_bytes += (uint64_t)out->n * 33;
-        float ms = 0.0f;
-        if (rc == ADH_OK && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) total_ms += ms;
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-    }
-    const double t_kernels = now();
-    if (rc == ADH_OK) h->last_select_ms = total_ms;
-    if (rc == ADH_OK && ids) {
-        const size_t o_prec[9] = {o_idx, o_fs, o_fe, o_ch, o_mz, o_iso, o_eg, o_dc, o_chn};
-        note_selected(h, pc, cfg, slab, o_prec, o_out);
-    }
-    const double t_copy = now();
-    if (timing)
-        fprintf(stderr, "[adh] select_candidates_im n=%lld: upload + plan %.2f ms, batches %.2f, kernels + copy-out %.2f (kernels %.2f)\n",
-                (long long)n, t_plan - t_0, t_alloc - t_plan, t_kernels - t_alloc, total_ms);
-    (void)t_copy;
-    return rc;
+void select_im_raise_lds_limit() {
+    (void)hipFuncSetAttribute((const void *)adh_select_score_im_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    (void)hipFuncSetAttribute((const void *)adh_select_smooth_im_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    (void)hipFuncSetAttribute((const void *)adh_select_smooth_im_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    (void)hipGetLastError();
 }
-
-// adh_select_candidates (`ids` NULL: the table is copied into `out`) and adh_select_candidates_resident (`ids` set:
-// `out` only carries the row count; the table, the precursor columns and the id columns stay in the slab)
-int select_candidates_run(adh_handle_t *h, const adh_precursors_t *pc, const adh_selection_config_t *cfg,
-                          const float *kernel, int32_t k_rows, int32_t k_cols, adh_candidate_table_t *out, const SelIds *ids) {
-    if (!h || !pc || !cfg || !kernel || !out) return fail(ADH_ERR_INVALID_ARGUMENT, "NULL argument");
-    h->sel.stage = 0;  // (the slab is rewritten)
-    if (!h->run_staged && !h->tims_staged) return fail(ADH_ERR_NOT_STAGED, "no run staged");
-    if (!h->d_lib) return fail(ADH_ERR_NOT_STAGED, "no fragment library staged");
-    if (pc->n < 0 || cfg->candidate_count <= 0 || cfg->candidate_count > sel::MAX_CAND)
-        return fail(ADH_ERR_INVALID_ARGUMENT, "candidate_count must be in 1..16");
-    if (out->n != pc->n * cfg->candidate_count)
-        return fail(ADH_ERR_INVALID_ARGUMENT, "candidate table rows != precursors x candidate_count");
-    if (k_rows <= 0 || k_cols <= 0 || cfg->top_k_precursors <= 0 || pc->n_isotope_cols <= 0)
-        return fail(ADH_ERR_INVALID_ARGUMENT, "kernel / isotope dimensions must be positive");
-    HIP_TRY(hipSetDevice(h->device));
-    const bool tdbg = getenv("ADH_DEBUG_SELECT_TIMING") != nullptr;
-    auto t_now = [] { return std::chrono::steady_clock::now(); };
-    auto t_prev = t_now();
-    auto lap = [&](const char *what) {
-        if (!tdbg) return;
-        const auto t = t_now();
-        fprintf(stderr, "[select] %s %.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t_prev).count());
-        t_prev = t;
-    };
-    const int64_t n = pc->n;
-    void *host_out[] = {out->precursor_idx, out->rank, out->score, out->scan_center, out->scan_start,
-                        out->scan_stop, out->frame_center, out->frame_start, out->frame_stop};
-    const size_t width[] = {4, 1, 4, 4, 4, 4, 4, 4, 4};
-    for (int f = 0; f < 9 && !ids; ++f) {
-        if (!host_out[f]) return fail(ADH_ERR_INVALID_ARGUMENT, "candidate table buffer is NULL");
-        memset(host_out[f], 0, (size_t)out->n * width[f]);
-    }
-    lap("memset");
-    if (n == 0) {
-        if (ids) {  // (an empty selection: nothing in the slab is read)
-            h->sel = adh_handle::Selected();
-            h->sel.cand_count = cfg->candidate_count;
-            h->sel.n_iso_cols = pc->n_isotope_cols;
-            h->sel.stage = 1;
-        }
-        return ADH_OK;
-    }
-    if (h->tims_staged) return select_candidates_im(h, pc, cfg, kernel, k_rows, k_cols, out, ids);
-    // One grow-only slab of the handle holds the precursor columns, the tile limits and the candidate table of a
-    // call (19 allocations and as many frees cost more than the kernel).  The per-precursor limits - two searches
-    // over the retention times of 3e5 spectra each: 17 ms per 100 000 precursors on one host core - and the checks
-    // of the fragment slices are a kernel of their own; three words come back to size the LDS.
-    sel::SelCaps caps{};
-    caps.n_iso = (int32_t)std::min<int64_t>(cfg->top_k_precursors, pc->n_isotope_cols);
-    caps.k_rows = k_rows;
-    caps.k_cols = k_cols;
-    const int L = h->run.cycle_len;
-    // The kernel keeps sel::MAX_ROWS cycle rows per group (rows overlapping the isotope range, MS1 rows) and the
-    // reference sums every row: a cycle with more is refused here, before anything is launched, as scoring refuses
-    // more than ADH_MAX_OBS observations.  Rows overlapping [a, b] = #(lower <= b) - #(upper < a) for rows with
-    // lower <= upper (an MS1 row (-1, -1) counts in both terms): two searches per precursor.
-    {
-        if (h->run.n_ms1_obs > sel::MAX_ROWS)
-            return fail(ADH_ERR_UNSUPPORTED, "candidate selection: more than 16 cycle rows are MS1 rows");
-        std::vector<double> lower((size_t)L), upper((size_t)L);
-        for (int row = 0; row < L; ++row) {
-            lower[(size_t)row] = h->h_cycle[2 * (size_t)row];
-            upper[(size_t)row] = h->h_cycle[2 * (size_t)row + 1];
-            if (!(lower[(size_t)row] <= upper[(size_t)row])) return fail(ADH_ERR_INVALID_ARGUMENT, "cycle row with lower > upper m/z");
-        }
-        std::sort(lower.begin(), lower.end());
-        std::sort(upper.begin(), upper.end());
-        // a bound first, from the cycle alone: no range as wide as the widest isotope range (charge 1) overlaps more
-        // rows than the best one that starts at a row's upper edge.  Only a cycle that fails it is walked per precursor.
-        const double widest = (double)std::max(caps.n_iso - 1, 0) * 1.0033548350700006 + 0.01;
-        int64_t bound = 0;
-        for (int row = 0; row < L && L > sel::MAX_ROWS; ++row) {
-            const double a = upper[(size_t)row];
-            bound = std::max<int64_t>(bound, (std::upper_bound(lower.begin(), lower.end(), a + widest) - lower.begin()) -
-                                                 (std::lower_bound(upper.begin(), upper.end(), a) - upper.begin()));
-        }
-        for (int64_t i = 0; i < n && caps.n_iso > 0 && bound > sel::MAX_ROWS; ++i) {
-            if (pc->charge[i] == 0) continue;  // (refused below)
-            // the isotope range exactly as adh_select_kernel computes it (assemble_isotope_mz)
-            const double a = (double)pc->mz[i];
-            const double b = (double)(float)((double)pc->mz[i] + (double)(caps.n_iso - 1) * 1.0033548350700006 / (double)pc->charge[i]);
-            const int64_t hit = (std::upper_bound(lower.begin(), lower.end(), b) - lower.begin()) -
-                                (std::lower_bound(upper.begin(), upper.end(), a) - upper.begin());
-            if (hit > sel::MAX_ROWS)
-                return fail(ADH_ERR_UNSUPPORTED, "candidate selection: a precursor's isotope range overlaps more than 16 cycle rows");
-        }
-    }
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t at = off;
-        off += (bytes + 255) / 256 * 256;
-        return at;
-    };
-    const size_t o_idx = carve((size_t)n * 4), o_fs = carve((size_t)n * 4), o_fe = carve((size_t)n * 4), o_ch = carve((size_t)n),
-                 o_rt = carve((size_t)n * 4), o_mz = carve((size_t)n * 4), o_iso = carve((size_t)n * pc->n_isotope_cols * 4),
-                 o_cs = carve((size_t)n * 4), o_cc = carve((size_t)n * 4), o_red = carve(16),
-                 o_kern = carve((size_t)k_rows * k_cols * 4);
-    size_t o_eg = 0, o_dc = 0, o_chn = 0;
-    if (ids) o_eg = carve((size_t)n * 4), o_dc = carve((size_t)n), o_chn = carve((size_t)n);
-    size_t o_out[9];
-    for (int f = 0; f < 9; ++f) o_out[f] = carve((size_t)out->n * width[f]);
-    if (h->sel_slab_bytes < off) {
-        HIP_TRY(hipDeviceSynchronize());
-        if (h->sel_slab) (void)hipFree(h->sel_slab);
-        h->sel_slab = nullptr;
-        h->sel_slab_bytes = 0;
-        const hipError_t e = hipMalloc(&h->sel_slab, off);
-        if (e != hipSuccess) return fail(ADH_ERR_OUT_OF_MEMORY, std::string("hipMalloc(selection slab): ") + hipGetErrorString(e));
-        h->sel_slab_bytes = off;
-    }
-    unsigned char *slab = static_cast<unsigned char *>(h->sel_slab);
-    auto put = [&](size_t at, const void *src, size_t bytes) -> hipError_t {
-        return bytes ? hipMemcpyAsync(slab + at, src, bytes, hipMemcpyHostToDevice, h->stream) : hipSuccess;
-    };
-    hipError_t e = put(o_idx, pc->precursor_idx, (size_t)n * 4);
-    if (e == hipSuccess) e = put(o_fs, pc->frag_start_idx, (size_t)n * 4);
-    if (e == hipSuccess) e = put(o_fe, pc->frag_stop_idx, (size_t)n * 4);
-    if (e == hipSuccess) e = put(o_ch, pc->charge, (size_t)n);
-    if (e == hipSuccess) e = put(o_rt, pc->rt, (size_t)n * 4);
-    if (e == hipSuccess) e = put(o_mz, pc->mz, (size_t)n * 4);
-    if (e == hipSuccess) e = put(o_iso, pc->isotope_intensity, (size_t)n * pc->n_isotope_cols * 4);
-    if (e == hipSuccess) e = put(o_kern, kernel, (size_t)k_rows * k_cols * 4);
-    if (ids) {
-        if (e == hipSuccess) e = put(o_eg, ids->elution_group_idx, (size_t)n * 4);
-        if (e == hipSuccess) e = put(o_dc, ids->decoy, (size_t)n);
-        if (e == hipSuccess) e = put(o_chn, ids->channel, (size_t)n);
-    }
-    if (e == hipSuccess) e = hipMemsetAsync(slab + o_red, 0, 16, h->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(slab + o_out[0], 0, off - o_out[0], h->stream);  // (the candidate table: rows without a candidate stay zero)
-    if (e != hipSuccess) return fail(ADH_ERR_HIP, std::string("selection upload: ") + hipGetErrorString(e));
-    DevPrecursors dp{};
-    dp.n_iso_cols = pc->n_isotope_cols;
-    dp.precursor_idx = reinterpret_cast<const uint32_t *>(slab + o_idx);
-    dp.frag_start = reinterpret_cast<const uint32_t *>(slab + o_fs);
-    dp.frag_stop = reinterpret_cast<const uint32_t *>(slab + o_fe);
-    dp.charge = slab + o_ch;
-    dp.rt = reinterpret_cast<const float *>(slab + o_rt);
-    dp.mz = reinterpret_cast<const float *>(slab + o_mz);
-    dp.iso = reinterpret_cast<const float *>(slab + o_iso);
-    dp.cycle_start = reinterpret_cast<const int32_t *>(slab + o_cs);
-    dp.cycle_count = reinterpret_cast<const int32_t *>(slab + o_cc);
-    int32_t *d_red = reinterpret_cast<int32_t *>(slab + o_red);
-    hipLaunchKernelGGL(adh_select_limits_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->run.rt,
-                       h->run.n_spectra, L, dp, n, h->n_lib, cfg->rt_tolerance, cfg->kernel_size,
-                       reinterpret_cast<int32_t *>(slab + o_cs), reinterpret_cast<int32_t *>(slab + o_cc), d_red);
-    e = hipGetLastError();
-    int32_t red[3] = {0, 0, 0};
-    if (e == hipSuccess) e = hipMemcpyAsync(red, d_red, sizeof(red), hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) return fail(ADH_ERR_HIP, std::string("selection limits: ") + hipGetErrorString(e));
-    lap("uploads + limits");
-    if (red[2] & 1) return fail(ADH_ERR_INVALID_ARGUMENT, "fragment slice outside the staged library");
-    if (red[2] & 2) return fail(ADH_ERR_INVALID_ARGUMENT, "precursor charge must be > 0");
-    caps.n_lib = std::max(red[0], 1);
-    caps.f = std::max(red[1], 1);
-    const size_t lds = sel::lds_bytes(caps);
-    if (lds > 150 * 1024) {
-        char buf[200];
-        snprintf(buf, sizeof(buf), "selection tile needs %zu bytes of LDS (%d cycles, %d fragments): exceeds 150 KiB",
-                 lds, caps.f, caps.n_lib);
-        return fail(ADH_ERR_UNSUPPORTED, buf);
-    }
-    DevCandTable dt{};
-    dt.precursor_idx = reinterpret_cast<uint32_t *>(slab + o_out[0]);
-    dt.rank = slab + o_out[1];
-    dt.score = reinterpret_cast<float *>(slab + o_out[2]);
-    dt.scan_center = reinterpret_cast<uint32_t *>(slab + o_out[3]);
-    dt.scan_start = reinterpret_cast<uint32_t *>(slab + o_out[4]);
-    dt.scan_stop = reinterpret_cast<uint32_t *>(slab + o_out[5]);
-    dt.frame_center = reinterpret_cast<uint32_t *>(slab + o_out[6]);
-    dt.frame_start = reinterpret_cast<uint32_t *>(slab + o_out[7]);
-    dt.frame_stop = reinterpret_cast<uint32_t *>(slab + o_out[8]);
-    int rc = ADH_OK;
-    {
-        (void)hipFuncSetAttribute((const void *)adh_select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  150 * 1024);
-        (void)hipGetLastError();
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        (void)hipEventCreate(&e0);
-        (void)hipEventCreate(&e1);
-        (void)hipEventRecord(e0, h->stream);
-        sel::Taps taps{};  // (the non-zero columns of a two-row smoothing kernel as float64 scalar operands)
-        if (k_rows == 2) {
-            int lo = k_cols, hi = -1;
-            for (int b = 0; b < k_cols; ++b)
-                if (kernel[b] != 0.0f || kernel[k_cols + b] != 0.0f) lo = std::min(lo, b), hi = std::max(hi, b);
-            if (hi < lo) lo = hi = 0;
-            const int nb = hi - lo + 1;
-            taps.cols = nb <= sel::TAP_COLS ? sel::TAP_COLS : 0;
-            taps.col0 = lo;
-            for (int a = 0; a < 2 && taps.cols; ++a)
-                for (int b = 0; b < nb; ++b) taps.v[a * taps.cols + b] = (double)kernel[a * k_cols + lo + b];
-        }
-        if (const char *env = getenv("ADH_DEBUG_SELECT_STOP")) caps.stop = atoi(env);
-        if (getenv("ADH_DEBUG_SELECT_LDS_TAPS")) taps.cols = 0;  // A/B: the generic smoothing loop
-        hipLaunchKernelGGL(adh_select_kernel, dim3((unsigned)n), dim3(ADH_WAVE), lds, h->stream,
-                           (SelectArgs{h->run, h->d_lib, dp, (int64_t)n, *cfg, reinterpret_cast<const float *>(slab + o_kern), taps, caps, dt}));
-        e = hipGetLastError();
-        (void)hipEventRecord(e1, h->stream);
-        for (int f = 0; f < 9 && e == hipSuccess && !ids; ++f)
-            e = hipMemcpyAsync(host_out[f], slab + o_out[f], (size_t)out->n * width[f], hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) rc = fail(ADH_ERR_HIP, std::string("selection kernel: ") + hipGetErrorString(e));
-        if (rc == ADH_OK && !ids) h->d2h_bytes += (uint64_t)out->n * 33;
-        if (rc == ADH_OK && ids) {
-            const size_t o_prec[9] = {o_idx, o_fs, o_fe, o_ch, o_mz, o_iso, o_eg, o_dc, o_chn};
-            note_selected(h, pc, cfg, slab, o_prec, o_out);
-        }
-        float ms = 0.0f;
-        if (rc == ADH_OK && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) h->last_select_ms = ms;
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-    }
-    lap("kernel + copy out");
-    return rc;
-}
-
-}  // namespace
-
-int adh_select_candidates(adh_handle_t *h, const adh_precursors_t *pc, const adh_selection_config_t *cfg,
-                          const float *kernel, int32_t k_rows, int32_t k_cols, adh_candidate_table_t *out) {
-    return select_candidates_run(h, pc, cfg, kernel, k_rows, k_cols, out, nullptr);
-}
-
-namespace {
 
 // adh_transpose_timstof for runs of more events than one sort takes (see adh_transpose.hip): two passes over
 // slabs of whole pushes; the outputs are assembled in HBM (6 bytes per event) and copied out at the end.
@@ -1986,12 +1501,6 @@ int adh_transpose_timstof(adh_handle_t *h, const uint32_t *tof_indices, const in
     return rc;
 }
 
-int adh_select_time_ms(adh_handle_t *h, double *kernel_ms) {
-    if (!h || !kernel_ms) return fail(ADH_ERR_INVALID_ARGUMENT, "NULL argument");
-    *kernel_ms = h->last_select_ms;
-    return ADH_OK;
-}
-
 int adh_fragcomp(adh_handle_t *h, int64_t n_windows, const int64_t *window_start,
                  const int64_t *window_stop, int64_t n_psm, const float *rt,
                  const int64_t *frag_start_idx, const int64_t *frag_stop_idx, int64_t n_frag,
@@ -2093,6 +1602,7 @@ int adh_fragcomp_stats(adh_handle_t *h, double *kernel_ms, int64_t *pairs, int64
 #include "adh_take_rows.hip"
 #include "adh_resident_append.hip"
 #include "adh_session.h"  // behind fail, HIP_TRY and the hipMalloc / hipFree macros: its allocations go through the block cache
+#include "adh_select_host.hip"
 #include "adh_select_handover.hip"
 #include "adh_quant.hip"
 #include "adh_grouping.hip"

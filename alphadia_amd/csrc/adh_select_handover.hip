@@ -39,8 +39,8 @@ struct Prec {
 };
 
 Table table_of(const adh_handle::Selected &s) {
-    return Table{s.t_u32[0], reinterpret_cast<const uint8_t *>(s.t_u32[1]), reinterpret_cast<const float *>(s.t_u32[2]),
-                 s.t_u32[3], s.t_u32[4], s.t_u32[5], s.t_u32[6], s.t_u32[7], s.t_u32[8]};
+    const DevCandTable &t = s.table;
+    return Table{t.precursor_idx, t.rank, t.score, t.scan_center, t.scan_start, t.scan_stop, t.frame_center, t.frame_start, t.frame_stop};
 }
 
 Prec prec_of(const adh_handle::Selected &s) {
