@@ -1522,6 +1522,11 @@ int adh_debug_get_dense(adh_handle_t *h, int64_t frame_start, int64_t frame_stop
         return fail(ADH_ERR_INVALID_ARGUMENT, "NULL argument");
     if (!h->run_staged && !h->tims_staged) return fail(ADH_ERR_NOT_STAGED, "no run staged");
     if (n_query < 1 || n_query > 4096) return fail(ADH_ERR_INVALID_ARGUMENT, "n_query must be in 1..4096");
+    // The kernels sort a candidate's fragments by m/z before they build the windows, as scoring and selection do in
+    // the reference; get_dense itself walks the list as given and never steps back.  The two agree on ascending
+    // lists only, and no caller of the gather produces another one: refuse it instead of answering for another order.
+    for (int k = 1; k < n_query; ++k)
+        if (!(mz_query[k] >= mz_query[k - 1])) return fail(ADH_ERR_INVALID_ARGUMENT, "mz_query must ascend");
     HIP_TRY(hipSetDevice(h->device));
     const bool im = h->tims_staged;
     const int L = im ? h->tims.cycle_len : h->run.cycle_len;

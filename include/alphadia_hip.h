@@ -425,7 +425,8 @@ int adh_host_take_objects(void **dst, void *const *src, const int64_t *idx, int6
  * TimsTOFTransposeJIT.get_dense (search/jitclasses/bruker_jit.py:273-504) return with
  * absolute_masses=True: dense[2][n_query][O][S][F] (intensity plane, then m/z plane; S = 1 for an
  * AlphaRaw run, whose two scan slots are copies, alpharaw_jit.py:326-333) and the cycle rows
- * (`precursor_idx_list`) in obs[0..*n_obs).  mz_query must be ascending.  Runs the production
+ * (`precursor_idx_list`) in obs[0..*n_obs).  mz_query must be ascending (ADH_ERR_INVALID_ARGUMENT
+ * otherwise: the kernels sort by m/z, get_dense does not).  Runs the production
  * gather kernel on a one-candidate plan built from the query.
  */
 int adh_debug_get_dense(adh_handle_t *handle, int64_t frame_start, int64_t frame_stop, int64_t scan_start,

@@ -1302,6 +1302,59 @@ def golden_get_dense_cycles():
     print(path, "MS1 lists", sorted(set(ms1_lens)), "fragment lists", sorted(set(frag_lens)), f"{os.path.getsize(path)/2**20:.2f} MiB")
 
 
+def golden_get_dense_mz_edges():
+    """AlphaRawJIT.get_dense(absolute_masses=True) and TimsTOFTransposeJIT.get_dense on the designed-edge runs of
+    tests/mz_edges.py: peaks on the float32 bounds of the tolerance windows, on the edges of the transposed run's m/z
+    bins, on powers of two and on the ends of the run; TOF bins on the bounds and on the edges of the lookup buckets.
+    The runs' arrays, the queries and the dense outputs.  (The shim keeps ``float32 > 1e-26`` and ``float32 + 1e-36``
+    in float32 where Numba computes them in float64: float32(1e-26) lies below 1e-26, so the cut falls between the
+    same two float32 values either way, and in the E7 cells 1e-36 is the whole sum (intensity zeroed), or below half
+    an ulp of both sums in both types, or - intensity 1e-30 - moves the quotient alike: the oracle, which follows
+    Numba's typing, reproduces every cell bit for bit, tests/test_mz_edges.py.)"""
+    import mz_edges
+
+    d = {"caveat": np.asarray(CAVEAT)}
+    scan = np.array([[0, 1, 1]], dtype=np.uint64)
+    hits = 0
+    for run in mz_edges.RUNS:
+        dia, cases = mz_edges.build_alpharaw(0, run)
+        jit = to_jit(dia)
+        for k, v in dia_to_dict(dia).items():
+            d[f"{run}_{k}"] = v
+        d[f"{run}_cases"] = np.array([c.name for c in cases], dtype="U")
+        for c in cases:
+            dense, pidx = jit.get_dense(c.frame_limits, scan, c.mz_query, c.tol, c.quad, absolute_masses=True)
+            q = f"{run}_{c.name}_"
+            d[q + "frame_limits"] = c.frame_limits
+            d[q + "mz"] = c.mz_query
+            d[q + "tol"] = np.asarray(c.tol)
+            d[q + "quad"] = c.quad
+            d[q + "dense"] = dense
+            d[q + "pidx"] = np.asarray(pidx, dtype=np.int64)
+            hits += int((dense[0] > 0).sum())
+    dia, cases = mz_edges.build_timstof(0)
+    jit = timstof_to_jit(dia)
+    for c in TIMS_COLS:
+        d["tims_" + c] = getattr(dia, c)
+    d["tims_scan_max_index"] = np.asarray(dia.scan_max_index)
+    d["tims_zeroth_frame"] = np.asarray(dia.zeroth_frame)
+    d["tims_cases"] = np.array([c.name for c in cases], dtype="U")
+    for c in cases:
+        dense, pidx = jit.get_dense(c.frame_limits, c.scan_limits, c.mz_query, c.tol, c.quad, absolute_masses=True)
+        q = f"tims_{c.name}_"
+        d[q + "frame_limits"] = c.frame_limits
+        d[q + "scan_limits"] = c.scan_limits
+        d[q + "mz"] = c.mz_query
+        d[q + "tol"] = np.asarray(c.tol)
+        d[q + "quad"] = c.quad
+        d[q + "dense"] = dense
+        d[q + "pidx"] = np.asarray(pidx, dtype=np.int64)
+        hits += int((dense[0] > 0).sum())
+    path = os.path.join(OUT_DIR, "get_dense_mz_edges.npz")
+    np.savez_compressed(path, **d)
+    print(path, hits, "cells hit", f"{os.path.getsize(path)/2**20:.2f} MiB")
+
+
 def golden_selection_cycles():
     """CandidateSelection.__call__ (as golden_selection, same FFT stand-in) on staggered windows with two MS1 rows:
     every precursor sums two or three fragment rows and two MS1 rows per cycle."""
@@ -1574,6 +1627,9 @@ def golden_boxes_timstof():
 
 
 if __name__ == "__main__":
+    if "--mz-edges-only" in sys.argv:
+        golden_get_dense_mz_edges()
+        sys.exit(0)
     if "--boxes-timstof-only" in sys.argv:
         golden_boxes_timstof()
         sys.exit(0)
@@ -1653,3 +1709,4 @@ if __name__ == "__main__":
     golden_boxes_timstof()
     golden_selection_limits()
     golden_selection_timstof_limits()
+    golden_get_dense_mz_edges()

@@ -126,3 +126,20 @@ def test_regenerating_the_cycle_goldens_reproduces_the_committed_files(tmp_path)
         for key in golden.files:
             assert fresh[key].dtype == golden[key].dtype, (name, key)
             assert np.array_equal(fresh[key], golden[key], equal_nan=golden[key].dtype.kind == "f"), (name, key)
+
+
+@pytest.mark.skipif(not os.path.isdir(ref_shim.REFERENCE_ROOT), reason="the reference checkout is not on this machine")
+def test_regenerating_the_mz_edge_golden_reproduces_the_committed_file(tmp_path):
+    """get_dense_mz_edges.npz (tests/mz_edges.py through the reference's get_dense) takes seconds: every array as
+    committed, and the file itself byte for byte."""
+    p = subprocess.run([sys.executable, os.path.join(GOLDEN, "make_golden.py"), "--out", str(tmp_path), "--mz-edges-only"],
+                       capture_output=True, text=True, cwd=ROOT)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
+    name = "get_dense_mz_edges.npz"
+    fresh, golden = np.load(tmp_path / name), np.load(H.golden_path(name))
+    assert sorted(fresh.files) == sorted(golden.files)
+    for key in golden.files:
+        assert fresh[key].dtype == golden[key].dtype, key
+        assert np.array_equal(fresh[key], golden[key], equal_nan=golden[key].dtype.kind == "f"), key
+    with open(tmp_path / name, "rb") as f, open(H.golden_path(name), "rb") as g:
+        assert f.read() == g.read()
