@@ -370,12 +370,12 @@ struct adh_handle {
     void *slot_stage = nullptr;           // page-locked fragment_lib_slot staging when the caller passes none
     size_t slot_stage_bytes = 0;
     // compacted copy-out of the fragment tables (adh_copyout.hip): a block per chunk - per-row offsets + the filled
-    // slots of the six wire columns - on the device and in page-locked host memory; scan scratch; the chunks' totals
-    void *cmp_dev = nullptr, *cmp_host = nullptr, *cmp_scan = nullptr;
-    size_t cmp_dev_bytes = 0, cmp_host_bytes = 0, cmp_scan_bytes = 0;
+    // slots of the six wire columns - on the device and in page-locked host memory; the chunks' totals
+    void *cmp_dev = nullptr, *cmp_host = nullptr;
+    size_t cmp_dev_bytes = 0, cmp_host_bytes = 0;
     uint32_t *cmp_tot_pinned = nullptr;     // filled slots of up to 4096 chunks, page-locked (the sparse-slot wire: four
                                             // words per chunk - slots, non-zero intensity / correlation words, format)
-    void *cmp_cnt = nullptr;                // the sparse-slot wire: per-row counts / their scan (SlotCnt) of one chunk
+    void *cmp_cnt = nullptr;                // per-row counts and per-workgroup totals (SlotCnt) of one chunk, either wire
     size_t cmp_cnt_bytes = 0;
     // adh_score_candidates_compact: per-row counts / offsets on the device, scan scratch, page-locked staging block
     void *cop_cnt = nullptr, *cop_scan = nullptr, *cop_stage = nullptr, *cop_dev = nullptr;
@@ -708,7 +708,6 @@ int adh_destroy(adh_handle_t *h) {
         }
     if (h->cop_scan) (void)hipFree(h->cop_scan);
     if (h->cmp_dev) (void)hipFree(h->cmp_dev);
-    if (h->cmp_scan) (void)hipFree(h->cmp_scan);
     if (h->cmp_cnt) (void)hipFree(h->cmp_cnt);
     for (DevTables &t : h->tables)
         if (t.base) (void)hipFree(t.base);

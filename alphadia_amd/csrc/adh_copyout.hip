@@ -6,23 +6,11 @@
 // ---- compacted copy-out of the fragment tables of the padded path.  A candidate fills the first K of its top_k fragment
 // slots (K = fragments with signal: 4.6 of 12 on the headline) and 58 % of the 264 bytes per candidate that the five
 // computed fragment tables + fragment_lib_slot put on PCIe are zeros.  Per chunk of the pipeline, behind its scoring
-// kernels: K per row, an exclusive scan, and a pack kernel that writes the filled slots of the six columns into ONE
-// block (PadBlock) and stores the chunk's total straight into page-locked memory - the host sizes the block's single
+// kernels, two launches (adh_pack_count_kernel, adh_pack_rows_kernel) write the filled slots of the six columns into ONE
+// block (PadBlock) and store the chunk's total straight into page-locked memory - the host sizes the block's single
 // copy from it without a round trip behind the copy-out backlog (see adh_cop_pack_kernel for why no copy fetches it).
 // The host team expands the block into the caller's padded tables and fills the library / id columns in the same pass
 // (fill_host_rows).
-__global__ void adh_slot_count_kernel(const uint16_t *__restrict__ lib_slot, int64_t row0, int64_t n, int top_k,
-                                      uint32_t *__restrict__ cnt) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i > n) return;
-    uint32_t k = 0;
-    if (i < n) {
-        const uint16_t *s = lib_slot + (row0 + i) * (int64_t)top_k;
-        while (k < (uint32_t)top_k && s[k]) ++k;  // (filled slots are the leading ones: candidate.py:403-442)
-    }
-    cnt[i] = k;  // (entry n: 0, so that the scan's last entry is the total)
-}
-
 #include "adh_fill_host.h"  // PadBlock, SparseBlock, fill_host_rows
 
 // where the block of the chunk that starts at row a sits in the staging buffers (device and host alike): room for every
@@ -39,129 +27,179 @@ struct PadLayout {
     }
 };
 
-// one thread per (row, slot) of the chunk; the offsets (block + 0) are the scanned counts
-__global__ void adh_pad_pack_kernel(DevOut t, int64_t row0, int64_t n, int top_k, unsigned char *__restrict__ block,
-                                    uint32_t *__restrict__ total) {
-    const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t *off = reinterpret_cast<const uint32_t *>(block);
-    const uint32_t S = off[n];
-    if (id == 0) *total = S;  // (page-locked host memory)
-    if (id >= n * top_k) return;
-    const int64_t i = id / top_k;
-    const int j = (int)(id - i * top_k);
-    const uint32_t a = off[i], k = off[i + 1] - a;
-    if ((uint32_t)j >= k) return;
-    const PadBlock L(n, S);
-    const int64_t src = (row0 + i) * (int64_t)top_k + j;
-    const size_t dst = (size_t)a + (size_t)j;
-    reinterpret_cast<uint16_t *>(block + L.slot)[dst] = t.fragment_lib_slot[src];
-    reinterpret_cast<float *>(block + L.f[0])[dst] = t.fragment_mz_observed[src];
-    reinterpret_cast<float *>(block + L.f[1])[dst] = t.fragment_height[src];
-    reinterpret_cast<float *>(block + L.f[2])[dst] = t.fragment_intensity[src];
-    reinterpret_cast<float *>(block + L.f[3])[dst] = t.fragment_mass_error[src];
-    reinterpret_cast<float *>(block + L.f[4])[dst] = t.fragment_correlation[src];
-}
-
 // ---- the sparse-slot wire of the same block (SparseBlock, adh_fill_host.h): fragment_intensity and
-// fragment_correlation travel as streams of their non-zero words.  Per row the count kernel also counts those words
-// among the row's filled slots (and the slot values that leave no room for the flags), ONE exclusive scan of the four
-// counts gives a row's place in the slot columns and in both streams, and the pack kernel writes offsets, anchors,
-// flagged slot words, the three dense columns and the two streams - count, scan, pack, as on the dense wire.
+// fragment_correlation travel as streams of their non-zero words, so a row has four counts: its filled slots, the
+// non-zero words of either stream among them, and the slot values that leave no room for the flags.
 struct alignas(16) SlotCnt {
     uint32_t s, i, c, big;  // filled slots, non-zero intensity words, non-zero correlation words, slot values >= big_from
-};
-struct SlotCntSum {
-    __host__ __device__ SlotCnt operator()(const SlotCnt &a, const SlotCnt &b) const {
-        return SlotCnt{a.s + b.s, a.i + b.i, a.c + b.c, a.big + b.big};
+    __device__ SlotCnt &operator+=(const SlotCnt &b) {
+        s += b.s, i += b.i, c += b.c, big += b.big;
+        return *this;
     }
 };
 
-// one thread per row, as adh_slot_count_kernel: 0.048 - 0.052 ms per 500 000-row chunk against that kernel's 0.009 (three
-// columns walked at 24- and 48-byte strides).  Measured and dropped: one thread per slot with the lanes of a row voting
-// and the lane of slot 0 counting the votes - coalesced loads, but of all 12 slots of a row where 4.6 are filled:
-// 0.069 - 0.071 ms (profiles/sparse_slots.json, `count_by_votes`).
-__global__ void adh_slot_count_nz_kernel(const uint16_t *__restrict__ lib_slot, const uint32_t *__restrict__ intensity,
-                                         const uint32_t *__restrict__ correlation, int64_t row0, int64_t n, int top_k,
-                                         uint32_t big_from, SlotCnt *__restrict__ cnt) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i > n) return;
+// ---- count and pack, two launches of kPackRows-thread workgroups, one workgroup per kPackRows rows of the chunk, on
+// either wire (kSparseWire: SparseBlock, else PadBlock, which only uses the count of filled slots).  No workgroup waits
+// for another: what a workgroup of the second launch needs of the others - the counts of the rows in front of its own
+// and the chunk's totals - it sums itself from the per-workgroup totals the first launch left (a 524 288-row chunk has
+// 2048 of them, 32 KB).  Before: a count kernel, hipcub::DeviceScan (its own launches) and a pack kernel per chunk.
+constexpr int kPackRows = 256;
+
+// the sum of v over the workgroup, in every thread (`lds`: one SlotCnt per wavefront)
+__device__ inline SlotCnt pack_wg_sum(SlotCnt v, SlotCnt *lds) {
+    for (int d = ADH_WAVE / 2; d > 0; d >>= 1) {
+        v.s += __shfl_xor(v.s, d), v.i += __shfl_xor(v.i, d), v.c += __shfl_xor(v.c, d), v.big += __shfl_xor(v.big, d);
+    }
+    const int lane = (int)(threadIdx.x & (ADH_WAVE - 1)), wave = (int)(threadIdx.x / ADH_WAVE);
+    if (lane == 0) lds[wave] = v;
+    __syncthreads();
+    SlotCnt sum{0, 0, 0, 0};
+    for (int w = 0; w < kPackRows / ADH_WAVE; ++w) sum += lds[w];
+    __syncthreads();  // (lds may be written again)
+    return sum;
+}
+
+// (A) one thread per row: cnt[i] for the chunk's n rows, wg_tot[w] for its (n + kPackRows - 1) / kPackRows workgroups.
+// One thread per row walks three columns at 24- and 48-byte strides.  Measured and dropped: one thread per slot with
+// the lanes of a row voting and the lane of slot 0 counting the votes - coalesced loads, but of all 12 slots of a row
+// where 4.6 are filled: 0.069 - 0.071 ms per 500 000-row chunk against 0.048 - 0.052 (profiles/sparse_slots.json,
+// `count_by_votes`).
+template <bool kSparseWire>
+__global__ __launch_bounds__(kPackRows) void adh_pack_count_kernel(const uint16_t *__restrict__ lib_slot,
+                                                                   const uint32_t *__restrict__ intensity,
+                                                                   const uint32_t *__restrict__ correlation, int64_t row0,
+                                                                   int64_t n, int top_k, uint32_t big_from,
+                                                                   SlotCnt *__restrict__ cnt, SlotCnt *__restrict__ wg_tot) {
+    __shared__ SlotCnt s_sum[kPackRows / ADH_WAVE];
+    const int64_t i = (int64_t)blockIdx.x * kPackRows + threadIdx.x;
     SlotCnt v{0, 0, 0, 0};
     if (i < n) {
         const int64_t r0 = (row0 + i) * (int64_t)top_k;
         const uint16_t *s = lib_slot + r0;
         for (; v.s < (uint32_t)top_k && s[v.s]; ++v.s) {  // (filled slots are the leading ones: candidate.py:403-442)
-            v.i += intensity[r0 + v.s] != 0u;
-            v.c += correlation[r0 + v.s] != 0u;
-            v.big += s[v.s] >= big_from;
-        }
-    }
-    cnt[i] = v;  // (entry n: zeros, so that the scan's last entry holds the totals)
-}
-
-// one thread per (row, slot) of the chunk; `scan`: the scanned counts.  Thread 0 stores the totals and the block's
-// format into page-locked memory (totals[0 .. 3]) and into the block's header.  A slot's place in a stream comes from
-// the votes of the lanes below it: 0.054 - 0.060 ms per 500 000-row chunk, against 0.066 - 0.068 with every thread reading the
-// row's slots in front of its own (profiles/sparse_slots.json, `pack_by_loop`) and the 0.032 of adh_pad_pack_kernel.
-__global__ void adh_pad_pack_sparse_kernel(DevOut t, int64_t row0, int64_t n, int top_k, const SlotCnt *__restrict__ scan,
-                                           unsigned char *__restrict__ block, uint32_t *__restrict__ totals) {
-    const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const SlotCnt tot = scan[n];
-    const bool sparse = tot.big == 0;
-    const SparseBlock L((uint64_t)row0, (uint64_t)n, tot.s, tot.i, tot.c, sparse);
-    uint32_t *const off = reinterpret_cast<uint32_t *>(block + L.off);
-    if (id == 0) {
-        const uint32_t head[4] = {sparse ? kWireSparse : kWireDense, tot.s, tot.i, tot.c};
-        for (int q = 0; q < 4; ++q) reinterpret_cast<uint32_t *>(block)[q] = head[q], totals[q] = head[q];  // (totals: page-locked host memory)
-        off[n] = tot.s;
-    }
-    const bool in_table = id < n * top_k;
-    const int64_t i = in_table ? id / top_k : 0;
-    const int j = in_table ? (int)(id - i * top_k) : 0;
-    SlotCnt a{0, 0, 0, 0};
-    uint32_t k = 0;
-    if (in_table) {
-        a = scan[i];
-        k = scan[i + 1].s - a.s;
-        if (j == 0) {
-            off[i] = a.s;
-            if (sparse && (row0 + i) % kAnchorRows == 0) {  // (anchors sit on the table's row numbers)
-                uint32_t *anchor = reinterpret_cast<uint32_t *>(block + L.anchor) +
-                                   2 * ((row0 + i) / kAnchorRows - (int64_t)SparseBlock::anchor_row0((uint64_t)row0));
-                anchor[0] = a.i, anchor[1] = a.c;
+            if (kSparseWire) {
+                v.i += intensity[r0 + v.s] != 0u;
+                v.c += correlation[r0 + v.s] != 0u;
+                v.big += s[v.s] >= big_from;
             }
         }
+        cnt[i] = v;
     }
-    const bool filled = in_table && (uint32_t)j < k;
-    const int64_t src = (row0 + i) * (int64_t)top_k + j;
+    const SlotCnt sum = pack_wg_sum(v, s_sum);
+    if (threadIdx.x == 0) wg_tot[blockIdx.x] = sum;
+}
+
+// (B) the workgroup of rows [w * kPackRows, (w + 1) * kPackRows) of the chunk: the counts in front of its rows and the
+// chunk's totals from wg_tot, an exclusive scan of its rows' counts in LDS, then every thread writes its row's offset
+// (and anchor), and the threads share the rows' filled slots - consecutive threads take consecutive slots of a row, of
+// as many slots per row as the fullest row of the workgroup has.  The last workgroup stores the totals into page-locked
+// memory (`totals`: one word on the dense wire; format, S, NI, NC on the sparse one, as in the block's header).  On the
+// sparse wire a slot's place in a stream comes from the votes of the lanes below it: 0.054 - 0.060 ms per 500 000-row
+// chunk with one thread per slot, against 0.066 - 0.068 with every thread reading the row's slots in front of its own
+// (profiles/sparse_slots.json, `pack_by_loop`).
+template <bool kSparseWire>
+__global__ __launch_bounds__(kPackRows) void adh_pack_rows_kernel(DevOut t, int64_t row0, int64_t n, int top_k,
+                                                                  const SlotCnt *__restrict__ cnt,
+                                                                  const SlotCnt *__restrict__ wg_tot,
+                                                                  unsigned char *__restrict__ block, uint32_t *__restrict__ totals) {
+    __shared__ SlotCnt s_sum[kPackRows / ADH_WAVE];
+    __shared__ SlotCnt s_at[kPackRows + 1];  // where the workgroup's rows start in the slot columns and the streams
+    __shared__ uint32_t s_kmax;
+    const int tid = (int)threadIdx.x, lane = tid & (ADH_WAVE - 1), wave = tid / ADH_WAVE;
+    const int64_t wg = blockIdx.x, n_wg = gridDim.x;
+    if (tid == 0) s_kmax = 0;
+    SlotCnt before{0, 0, 0, 0}, tot{0, 0, 0, 0};
+    for (int64_t q = tid; q < n_wg; q += kPackRows) {
+        const SlotCnt r = wg_tot[q];
+        tot += r;
+        if (q < wg) before += r;
+    }
+    before = pack_wg_sum(before, s_sum);
+    tot = pack_wg_sum(tot, s_sum);
+    // the rows' counts, scanned: in the wavefront, then over the wavefronts in front
+    const int64_t i = wg * kPackRows + tid;
+    SlotCnt v{0, 0, 0, 0};
+    if (i < n) v = cnt[i];
+    SlotCnt at = v;  // (inclusive)
+    for (int d = 1; d < ADH_WAVE; d <<= 1) {
+        const uint32_t ps = __shfl_up(at.s, d), pi = __shfl_up(at.i, d), pc = __shfl_up(at.c, d);
+        if (lane >= d) at.s += ps, at.i += pi, at.c += pc;
+    }
+    if (lane == ADH_WAVE - 1) s_sum[wave] = at;
+    if (v.s) atomicMax(&s_kmax, v.s);
+    __syncthreads();
+    for (int w = 0; w < wave; ++w) at.s += s_sum[w].s, at.i += s_sum[w].i, at.c += s_sum[w].c;
+    at.s += before.s, at.i += before.i, at.c += before.c;
+    s_at[tid + 1] = at;
+    at.s -= v.s, at.i -= v.i, at.c -= v.c;  // (exclusive)
+    if (tid == 0) s_at[0] = at;
+    __syncthreads();
+
+    const bool sparse = kSparseWire && tot.big == 0;
+    const SparseBlock LS((uint64_t)row0, (uint64_t)n, tot.s, tot.i, tot.c, sparse);
+    const PadBlock LP((uint64_t)n, tot.s);
+    uint32_t *const off = reinterpret_cast<uint32_t *>(block + (kSparseWire ? LS.off : 0));
+    const size_t o_slot = kSparseWire ? LS.slot : LP.slot;
+    size_t o_f[5];
+    for (int q = 0; q < 5; ++q) o_f[q] = kSparseWire ? LS.f[q] : LP.f[q];
+    if (wg == n_wg - 1 && tid == 0) {
+        if (kSparseWire) {
+            const uint32_t head[4] = {sparse ? kWireSparse : kWireDense, tot.s, tot.i, tot.c};
+            for (int q = 0; q < 4; ++q) reinterpret_cast<uint32_t *>(block)[q] = head[q], totals[q] = head[q];  // (totals: page-locked host memory)
+        } else {
+            totals[0] = tot.s;  // (page-locked host memory)
+        }
+        off[n] = tot.s;
+    }
+    if (i < n) {
+        off[i] = at.s;
+        if (sparse && (row0 + i) % kAnchorRows == 0) {  // (anchors sit on the table's row numbers)
+            uint32_t *anchor = reinterpret_cast<uint32_t *>(block + LS.anchor) +
+                               2 * ((row0 + i) / kAnchorRows - (int64_t)SparseBlock::anchor_row0((uint64_t)row0));
+            anchor[0] = at.i, anchor[1] = at.c;
+        }
+    }
     const uint32_t *const intensity = reinterpret_cast<const uint32_t *>(t.fragment_intensity);
     const uint32_t *const correlation = reinterpret_cast<const uint32_t *>(t.fragment_correlation);
-    const uint32_t vi = filled ? intensity[src] : 0u, vc = filled ? correlation[src] : 0u;
-    // (every lane of the wavefront votes: a row's slots sit in consecutive lanes)
-    const uint64_t nz_i = __ballot(vi != 0u), nz_c = __ballot(vc != 0u);
-    if (!filled) return;
-    const size_t dst = (size_t)a.s + (size_t)j;
-    uint16_t word = t.fragment_lib_slot[src];
-    size_t di = dst, dc = dst;
-    if (sparse) {
-        // the slot's place in a stream: the row's, plus the non-zero words of the row's j slots in front of this one -
-        // the votes of the j lanes below this one, or, where the row began in the wavefront before, the words themselves
-        uint32_t pi = a.i, pc = a.c;
-        const int lane = (int)(threadIdx.x & (ADH_WAVE - 1));
-        if (j <= lane) {
-            const uint64_t before = ((1ull << j) - 1ull) << (lane - j);
-            pi += (uint32_t)__popcll(nz_i & before), pc += (uint32_t)__popcll(nz_c & before);
-        } else {
-            for (int q = 0; q < j; ++q) pi += intensity[src - j + q] != 0u, pc += correlation[src - j + q] != 0u;
+    const int64_t kmax = s_kmax;
+    const int64_t span = std::min<int64_t>(kPackRows, n - wg * kPackRows) * kmax;  // (the same for every thread)
+    for (int64_t first = 0; first < span; first += kPackRows) {
+        const int64_t id = first + tid;
+        const bool in_rows = id < span;
+        const int r = in_rows ? (int)(id / kmax) : 0;
+        const int j = in_rows ? (int)(id - (int64_t)r * kmax) : 0;
+        const SlotCnt a = s_at[r];
+        const bool filled = in_rows && (uint32_t)j < s_at[r + 1].s - a.s;
+        const int64_t src = (row0 + wg * kPackRows + r) * (int64_t)top_k + j;
+        const uint32_t vi = filled ? intensity[src] : 0u, vc = filled ? correlation[src] : 0u;
+        // (every lane of the wavefront votes: a row's slots sit in consecutive lanes)
+        const uint64_t nz_i = __ballot(vi != 0u), nz_c = __ballot(vc != 0u);
+        if (filled) {
+            const size_t dst = (size_t)a.s + (size_t)j;
+            uint16_t word = t.fragment_lib_slot[src];
+            size_t di = dst, dc = dst;
+            if (sparse) {
+                // the slot's place in a stream: the row's, plus the non-zero words of the row's j slots in front of this
+                // one - the votes of the j lanes below this one, or, where the row began in the wavefront before, the
+                // words themselves
+                uint32_t pi = a.i, pc = a.c;
+                if (j <= lane) {
+                    const uint64_t below = ((1ull << j) - 1ull) << (lane - j);
+                    pi += (uint32_t)__popcll(nz_i & below), pc += (uint32_t)__popcll(nz_c & below);
+                } else {
+                    for (int q = 0; q < j; ++q) pi += intensity[src - j + q] != 0u, pc += correlation[src - j + q] != 0u;
+                }
+                di = pi, dc = pc;
+                word |= (vi ? kHasIntensity : 0u) | (vc ? kHasCorrelation : 0u);
+            }
+            reinterpret_cast<uint16_t *>(block + o_slot)[dst] = word;
+            reinterpret_cast<float *>(block + o_f[0])[dst] = t.fragment_mz_observed[src];
+            reinterpret_cast<float *>(block + o_f[1])[dst] = t.fragment_height[src];
+            reinterpret_cast<float *>(block + o_f[3])[dst] = t.fragment_mass_error[src];
+            if (!sparse || vi) reinterpret_cast<uint32_t *>(block + o_f[2])[di] = vi;
+            if (!sparse || vc) reinterpret_cast<uint32_t *>(block + o_f[4])[dc] = vc;
         }
-        di = pi, dc = pc;
-        word |= (vi ? kHasIntensity : 0u) | (vc ? kHasCorrelation : 0u);
     }
-    reinterpret_cast<uint16_t *>(block + L.slot)[dst] = word;
-    reinterpret_cast<float *>(block + L.f[0])[dst] = t.fragment_mz_observed[src];
-    reinterpret_cast<float *>(block + L.f[1])[dst] = t.fragment_height[src];
-    reinterpret_cast<float *>(block + L.f[3])[dst] = t.fragment_mass_error[src];
-    if (!sparse || vi) reinterpret_cast<uint32_t *>(block + L.f[2])[di] = vi;
-    if (!sparse || vc) reinterpret_cast<uint32_t *>(block + L.f[4])[dc] = vc;
 }
 
 // ---- compacted, column-major copy-out of the operator path (round 5, adh_score_candidates_compact).  What the
@@ -491,14 +529,6 @@ int grow_scan_scratch(void **p, size_t *bytes, int64_t items, hipStream_t st) {
     HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, (Word *)nullptr, (Word *)nullptr, (int)items, st));
     return grow_device(p, bytes, need, 256);
 }
-// ... and of the scan over the four counts of the sparse-slot wire
-int grow_slot_cnt_scratch(void **p, size_t *bytes, int64_t items, hipStream_t st) {
-    size_t need = 0;
-    HIP_TRY(hipcub::DeviceScan::ExclusiveScan(nullptr, need, (SlotCnt *)nullptr, (SlotCnt *)nullptr, SlotCntSum(),
-                                              SlotCnt{0, 0, 0, 0}, (int)items, st));
-    return grow_device(p, bytes, need, 256);
-}
-
 // has the caller passed every array of a compact output?
 bool compact_output_complete(const adh_compact_output_t *o) {
     return o->row && o->precursor_idx && o->rank && o->features && o->fragment_row && o->fragment_precursor_idx &&
@@ -544,6 +574,8 @@ struct PipelineTrace {
     hipEvent_t start = nullptr;        // on the copy-in stream, before the first column goes up
     double start_host = 0.0;           // the host's clock when `start` was recorded
     std::vector<hipEvent_t> marks;     // scoring stream, per chunk: before its kernels, behind them, behind its helpers
+    std::vector<hipEvent_t> plans;     // copy-in stream, per chunk: before and behind its plan
+    std::vector<double> plan_seen, enqueued;  // the host's clock, per chunk: its plan read, its kernels and helpers enqueued
     // the hand-off of every packed block on the host's clock (ms after the call began): its total seen by the enqueue
     // thread, the team told that it has landed, every thread of the team done with its stripe (one entry per chunk
     // and thread: each thread writes its own)
@@ -558,6 +590,7 @@ struct PipelineTrace {
     ~PipelineTrace() {  // (the events go on every way out of the call)
         for (hipEvent_t e : spans) (void)hipEventDestroy(e);
         for (hipEvent_t e : marks) (void)hipEventDestroy(e);
+        for (hipEvent_t e : plans) (void)hipEventDestroy(e);
         if (start) (void)hipEventDestroy(start);
     }
     void expect_blocks(int64_t n_chunks, int threads) {
@@ -574,6 +607,9 @@ struct PipelineTrace {
     }
     void mark_start(hipStream_t si) { start = stamp(si), start_host = since(); }
     void mark(hipStream_t sk) { if (events) marks.push_back(stamp(sk)); }
+    void mark_plan(hipStream_t si) { if (events) plans.push_back(stamp(si)); }
+    void plan_read() { if (events) plan_seen.push_back(since()); }
+    void chunk_enqueued() { if (events) enqueued.push_back(since()); }
     void span_begin(hipStream_t so, uint64_t d2h_bytes) { if (events) spans.push_back(stamp(so)), span_bytes.push_back(d2h_bytes); }
     void span_end(hipStream_t so, uint64_t d2h_bytes) {
         if (events) spans.push_back(stamp(so)), span_bytes.back() = d2h_bytes - span_bytes.back();
@@ -642,6 +678,17 @@ struct PipelineTrace {
             k_sum += (double)k_ms + (double)help_ms;
             fprintf(stderr, "[adh]   chunk %zu: kernels start %.2f ms after the call's first copy-in, last %.2f ms, helpers %.3f ms, "
                             "scoring stream idle before them %.2f ms\n", i / 3, at, k_ms, help_ms, idle_ms);
+            // what the kernels waited for: the chunk's plan on the copy-in stream, and the host that reads it and
+            // enqueues the kernels (the host's clock, put on the copy-in stream's as `start` was recorded)
+            const size_t ci = i / 3;
+            if (start && 2 * ci + 1 < plans.size() && ci < plan_seen.size() && ci < enqueued.size()) {
+                float p0 = 0.f, p1 = 0.f;
+                (void)hipEventElapsedTime(&p0, start, plans[2 * ci]);
+                (void)hipEventElapsedTime(&p1, start, plans[2 * ci + 1]);
+                fprintf(stderr, "[adh]   chunk %zu: plan runs %.2f - %.2f ms after the call's first copy-in, read by the host at %.2f, "
+                                "kernels and helpers enqueued by %.2f\n", ci, p0, p1, plan_seen[ci] - start_host,
+                        enqueued[ci] - start_host);
+            }
         }
         if (marks.size() >= 3) {
             float span = 0.f;
@@ -839,12 +886,10 @@ struct PackedCopyOut : PlainCopyOut {
                 const long v = strtol(env, &end, 0);
                 if (end != env && *end == '\0' && v >= 1 && v <= (long)kSlotFlagFrom) big_from = (uint32_t)v;
             }
-            const size_t cnt_bytes = (size_t)(longest_chunk() + 1) * sizeof(SlotCnt);
-            rc = grow_device(&h->cmp_cnt, &h->cmp_cnt_bytes, cnt_bytes, cnt_bytes / 8);
-            if (rc == ADH_OK) rc = grow_slot_cnt_scratch(&h->cmp_scan, &h->cmp_scan_bytes, longest_chunk() + 1, h->stream);
-        } else {
-            rc = grow_scan_scratch<uint32_t>(&h->cmp_scan, &h->cmp_scan_bytes, longest_chunk() + 1, h->stream);
         }
+        // a chunk's per-row counts and, behind them, its per-workgroup totals
+        const size_t cnt_bytes = (size_t)(longest_chunk() + longest_chunk() / kPackRows + 1) * sizeof(SlotCnt);
+        rc = grow_device(&h->cmp_cnt, &h->cmp_cnt_bytes, cnt_bytes, cnt_bytes / 8);
         if (rc != ADH_OK) return rc;
         dev_blocks = static_cast<unsigned char *>(h->cmp_dev), host_blocks = static_cast<unsigned char *>(h->cmp_host);
         for (std::atomic<int64_t> &next : next_tile) next.store(0, std::memory_order_relaxed);
@@ -866,33 +911,27 @@ struct PackedCopyOut : PlainCopyOut {
     void start_team() override {
         (void)start_handoff_team(team, T, n_chunks, [this](int64_t ci, int w) { stripe(ci, w); });
     }
-    // filled slots per row, their offsets, the packed block: behind the chunk's kernels
-    int pack(int64_t ci) override {
+    // the rows' counts, then offsets and the packed block (adh_pack_count_kernel, adh_pack_rows_kernel): behind the
+    // chunk's kernels, on the scoring stream.  (Measured and dropped: both launches on a stream of their own that waits
+    // for the chunk's kernels, so that the next chunk's kernels follow directly.  They then run beside those kernels
+    // and slow them: the scoring stream's span went from 14.3 - 15.4 ms to 16.2 - 16.7, and to 17.4 - 17.6 on a stream
+    // of the highest priority - profiles/scoring_stream_chunks.json, `pack_stream`.)
+    template <bool kSparseWire>
+    void launch_pack(int64_t ci) {
         const int64_t a = cut[(size_t)ci], nr = cut[(size_t)ci + 1] - a;
-        hipStream_t sk = h->stream;
-        unsigned char *blk = dev_blocks + lay.base(a, ci);
-        if (sparse) {
-            SlotCnt *cnt = static_cast<SlotCnt *>(h->cmp_cnt);
-            hipLaunchKernelGGL(adh_slot_count_nz_kernel, dim3((unsigned)((nr + 256) / 256)), dim3(256), 0, sk, dev.fragment_lib_slot,
-                               reinterpret_cast<const uint32_t *>(dev.fragment_intensity),
-                               reinterpret_cast<const uint32_t *>(dev.fragment_correlation), a, nr, top_k, big_from, cnt);
-            size_t scan_bytes = h->cmp_scan_bytes;
-            HIP_TRY(hipcub::DeviceScan::ExclusiveScan(h->cmp_scan, scan_bytes, cnt, cnt, SlotCntSum(), SlotCnt{0, 0, 0, 0},
-                                                      (int)(nr + 1), sk));
-            hipLaunchKernelGGL(adh_pad_pack_sparse_kernel, dim3((unsigned)((nr * top_k + 255) / 256)), dim3(256), 0, sk, dev, a, nr,
-                               top_k, cnt, blk, h->cmp_tot_pinned + 4 * ci);
-            HIP_TRY(hipGetLastError());
-            return record(sk, tot_ready);  // (when the totals can be read)
-        }
-        uint32_t *d_off = reinterpret_cast<uint32_t *>(blk);
-        hipLaunchKernelGGL(adh_slot_count_kernel, dim3((unsigned)((nr + 256) / 256)), dim3(256), 0, sk, dev.fragment_lib_slot, a,
-                           nr, top_k, d_off);
-        size_t scan_bytes = h->cmp_scan_bytes;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(h->cmp_scan, scan_bytes, d_off, d_off, (int)(nr + 1), sk));
-        hipLaunchKernelGGL(adh_pad_pack_kernel, dim3((unsigned)((nr * top_k + 255) / 256)), dim3(256), 0, sk, dev, a, nr, top_k,
-                           blk, h->cmp_tot_pinned + ci);
+        const dim3 grid((unsigned)((nr + kPackRows - 1) / kPackRows)), wg(kPackRows);
+        SlotCnt *cnt = static_cast<SlotCnt *>(h->cmp_cnt), *wg_tot = cnt + longest_chunk();
+        hipLaunchKernelGGL(adh_pack_count_kernel<kSparseWire>, grid, wg, 0, h->stream, dev.fragment_lib_slot,
+                           reinterpret_cast<const uint32_t *>(dev.fragment_intensity),
+                           reinterpret_cast<const uint32_t *>(dev.fragment_correlation), a, nr, top_k, big_from, cnt, wg_tot);
+        hipLaunchKernelGGL(adh_pack_rows_kernel<kSparseWire>, grid, wg, 0, h->stream, dev, a, nr, top_k, cnt, wg_tot,
+                           dev_blocks + lay.base(a, ci), h->cmp_tot_pinned + (kSparseWire ? 4 : 1) * ci);
+    }
+    int pack(int64_t ci) override {
+        if (sparse) launch_pack<true>(ci);
+        else launch_pack<false>(ci);
         HIP_TRY(hipGetLastError());
-        return record(sk, tot_ready);  // (when the total can be read)
+        return record(h->stream, tot_ready);  // (when the totals can be read)
     }
     // the packed block of chunk ci: wait for its pack kernel (an event on the scoring stream - the next chunk's kernels
     // are already queued; never a copy behind the copy-out backlog), ONE copy of its used bytes, then the event behind

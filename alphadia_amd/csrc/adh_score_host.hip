@@ -1366,7 +1366,7 @@ int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring
 
     // rebuildable columns: not copied back, rebuilt on the host from fragment_lib_slot (see kOutFields)
     const bool rebuild = !cop && !resident && h->h_lib.size() == (size_t)h->n_lib && !getenv("ADH_DEBUG_COPY_ALL") && host_rebuild_pays();
-    // compacted copy-out of the fragment tables (see adh_slot_count_kernel, compact_copy_out_pays)
+    // compacted copy-out of the fragment tables (see adh_pack_rows_kernel, compact_copy_out_pays)
     const bool compact_wanted = rebuild && top_k <= 65535 && compact_copy_out_pays(n);
     // chunk boundaries: at most max_rows rows per chunk
     int64_t max_rows = 0;
@@ -1407,9 +1407,17 @@ int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring
     // for all of it: with the burst behind plan(1) the kernels of chunk 2 started 1.4 - 1.7 ms after those of chunk 1
     // had ended and the copy-out had a hole of 1.15 ms (profiles/headline_pipeline.json, `before`).  The burst
     // overlaps the copy-out of chunks 0 and 1 in both orders: that copy runs at 47 - 49 instead of 56 GB/s.
+    // plan(3) is such a plan, too: on the headline the burst (2.25 M rows, 2.8 ms) ends and plan(3) (0.3 ms) starts as
+    // the kernels of chunk 2 end, and in most calls the scoring stream then idles 0.5 - 0.8 ms in front of chunk 3.
+    // Measured and dropped: only the columns of chunk 3 in front of plan(3) and the rows of chunks 4 .. last on a
+    // stream of their own, behind plan(2).  The scoring stream's hole closes (span 14.4 - 14.5 ms instead of 14.4 -
+    // 15.0), but the block of chunk 1 then waits for that upload on the copy engines - its copy starts 1.5 ms later -
+    // and the step takes 18.8 - 21.5 ms instead of 18.3 - 19.6 (profiles/scoring_stream_chunks.json, `split_burst`).
     trace.mark_start(si);
     rc = cand_upload(0, cut[1], si);
+    trace.mark_plan(si);
     if (rc == ADH_OK) rc = plan_enqueue(h, h->slots[0], cfg, 0, cut[1], si);
+    trace.mark_plan(si);
     if (rc == ADH_OK && n_chunks > 1) rc = cand_upload(cut[1], cut[2], si);
     if (rc != ADH_OK) return rc;
     // the host teams start now that the device has work: started in front of the first copy-in, the 16 threads made
@@ -1422,7 +1430,9 @@ int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring
             // plan of the next chunk: the other plan slot is free once the kernels of chunk ci - 1 are done
             const int64_t a2 = b, b2 = cut[(size_t)ci + 2];
             if (ci >= 1) HIP_TRY(hipStreamWaitEvent(si, h->ev_k[ps ^ 1], 0));
+            trace.mark_plan(si);  // (behind the wait: the plan's own time)
             rc = plan_enqueue(h, h->slots[ps ^ 1], cfg, a2, b2 - a2, si);
+            trace.mark_plan(si);
             // (the rows of chunk 2 behind the plan of chunk 1, ALL later rows behind the plan of chunk 2: see above)
             if (rc == ADH_OK && ci == 0 && n_chunks > 2) rc = cand_upload(cut[2], cut[3], si);
             if (rc == ADH_OK && ci == 1 && n_chunks > 3) rc = cand_upload(cut[3], n, si);
@@ -1430,12 +1440,14 @@ int score_pipeline(adh_handle_t *h, const adh_candidates_t *c, const adh_scoring
         }
         Plan p;
         rc = plan_finish(h, h->slots[ps], cfg, a, b - a, p);
+        trace.plan_read();
         trace.mark(sk);
         if (rc == ADH_OK) rc = launch_scoring(h, p, cfg, &dev_k, sk);
         trace.mark(sk);
         if (rc == ADH_OK) rc = copy_out->pack(ci);
         if (rc != ADH_OK) return rc;
         trace.mark(sk);
+        trace.chunk_enqueued();
         HIP_TRY(hipEventRecord(h->ev_k[ps], sk));
         rc = copy_out->copy_out(ci);
         if (rc != ADH_OK) return rc;
