@@ -925,10 +925,19 @@ PROTOTYPES = {
 }
 
 
-def declare(lib) -> None:
-    """Set ``restype`` and ``argtypes`` of every export on ``lib`` (a ``CDLL`` or ``PyDLL`` of the library) from
-    PROTOTYPES.  Nothing else assigns them: a call that disagrees with the header raises ``ctypes.ArgumentError``."""
-    for name, (restype, argtypes) in PROTOTYPES.items():
+# Every export of include/alphadia_hip_lfq.h (label-free quantification, adlfq_*), in that header's order and by the
+# same rule; tests/test_abi_lfq.py derives every entry from the header's text.
+LFQ_EXPORTS = {
+    "adlfq_run": (_i32, [_vp, _i32, _u8p, _i32p, _i32, _i32, _i32, _i32, _i64p]),
+    "adlfq_result": (_i32, [_vp, _i32p, _f64p]),
+    "adlfq_time_ms": (_i32, [_vp, _f64p, _f64p, _f64p]),
+}
+
+
+def declare(lib, table=PROTOTYPES) -> None:
+    """Set ``restype`` and ``argtypes`` of every export of ``table`` on ``lib`` (a ``CDLL`` or ``PyDLL`` of the
+    library).  Nothing else assigns them: a call that disagrees with the header raises ``ctypes.ArgumentError``."""
+    for name, (restype, argtypes) in table.items():
         fn = getattr(lib, name)
         fn.restype = restype
         fn.argtypes = argtypes

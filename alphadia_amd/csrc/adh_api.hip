@@ -14,6 +14,7 @@
 #include <thread>
 #include <string>
 #include <vector>
+#include <memory>
 #include <mutex>
 #include <unordered_map>
 
@@ -1604,6 +1605,7 @@ int adh_fragcomp_stats(adh_handle_t *h, double *kernel_ms, int64_t *pairs, int64
 #include "adh_select_host.hip"
 #include "adh_select_handover.hip"
 #include "adh_quant.hip"
+#include "adh_lfq.hip"
 #include "adh_grouping.hip"
 #include "adh_protein_fdr.hip"
 #include "adh_transfer_library.hip"

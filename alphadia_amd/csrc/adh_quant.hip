@@ -38,6 +38,7 @@ struct adh_quant {
     sess::DevArray<uint32_t> flag;  // one u32 on the device: a run holds a key twice
     sess::EventPair ev;
     double build_ms = 0.0, filter_ms = 0.0;
+    std::shared_ptr<void> lfq;  // the state of label-free quantification over these matrices (adh_lfq.hip)
 };
 
 namespace quant {

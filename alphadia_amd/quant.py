@@ -289,4 +289,11 @@ def filter_frag_df(intensity_df: pd.DataFrame, quality_df: pd.DataFrame, min_cor
                                      _threshold(min_correlation))
     quality_df["total"] = total
     quality_df["rank"] = rank
-    return intensity_df[mask], quality_df[mask]
+    kept_intensity = intensity_df[mask]
+    ires = _resident(intensity_df, run_columns)
+    if res is not None and ires is not None and ires.quant is quant:
+        # (alphadia_amd.lfq.direct_lfq quantifies this frame from the matrix in HBM)
+        from alphadia_amd import lfq
+
+        lfq.remember_filtered(kept_intensity, quant, ires.column, run_columns, mask)
+    return kept_intensity, quality_df[mask]

@@ -69,6 +69,7 @@ def _load():
         )
     lib = C.CDLL(LIB_PATH)
     _abi.declare(lib)
+    _abi.declare(lib, _abi.LFQ_EXPORTS)
     return lib
 
 
@@ -1532,6 +1533,27 @@ class DeviceQuant(_DeviceSession):
     def time_ms(self):
         """HIP-event times (ms) of the build and of the last filter."""
         return self._times(2, lambda *t: lib.adh_quant_time_ms(self._s, *t))
+
+    def lfq(self, column: int, keep, group, n_groups: int, min_nonan: int, num_samples_quadratic: int,
+            normalize: bool):
+        """Label-free quantification over matrix ``column`` (include/alphadia_hip_lfq.h: adlfq_run): ``keep`` a mask
+        over the key rows or None, ``group`` one code per key row.  Returns the kept group codes (ascending) and
+        their ``(n_kept, n_runs)`` float64 table."""
+        g = _abi.as_c(group, np.int32)
+        k = None if keep is None else _abi.as_c(np.asarray(keep) != 0, np.uint8)
+        if g.shape != (self.n_keys,) or (k is not None and k.shape != g.shape):
+            raise ValueError("lfq: one group code (and one mask value) per key row")
+        n = C.c_int64(0)
+        _check(lib.adlfq_run(self._s, int(column), _p(k, C.c_uint8), _p(g, C.c_int32), int(n_groups), int(min_nonan),
+                             int(num_samples_quadratic), int(bool(normalize)), C.byref(n)), "adlfq_run")
+        groups = np.empty(n.value, dtype=np.int32)
+        table = np.empty((n.value, self.n_runs), dtype=np.float64)
+        _check(lib.adlfq_result(self._s, _p(groups, C.c_int32), _p(table, C.c_double)), "adlfq_result")
+        return groups, table
+
+    def lfq_time_ms(self):
+        """HIP-event times (ms) of the last ``lfq``: prepare, sample normalisation, group kernels."""
+        return self._times(3, lambda *t: lib.adlfq_time_ms(self._s, *t))
 
 
 class DeviceProteinGroups(_DeviceSession):
