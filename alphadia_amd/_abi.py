@@ -934,6 +934,14 @@ LFQ_EXPORTS = {
 }
 
 
+# Every export of include/alphadia_hip_flatten.h (the device flatten, adfl_*), in that header's order and by the same
+# rule; tests/test_abi_flatten.py derives every entry from the header's text.
+FLATTEN_EXPORTS = {
+    "adfl_flatten": (_i32, [_vp, _i64, _i64p, _i64p, _i64p, _u8p, _i64, _i32, _f32p, _f32p, _u8p, _i32, _f32, _i32,
+                            _i64, _u32p, _u32p, _f32p, _f32p, _u8p, _i64p, _i64p, _f64p, _u64p]),
+}
+
+
 def declare(lib, table=PROTOTYPES) -> None:
     """Set ``restype`` and ``argtypes`` of every export of ``table`` on ``lib`` (a ``CDLL`` or ``PyDLL`` of the
     library).  Nothing else assigns them: a call that disagrees with the header raises ``ctypes.ArgumentError``."""

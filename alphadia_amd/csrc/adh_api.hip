@@ -1610,3 +1610,4 @@ int adh_fragcomp_stats(adh_handle_t *h, double *kernel_ms, int64_t *pairs, int64
 #include "adh_protein_fdr.hip"
 #include "adh_transfer_library.hip"
 #include "adh_mbr_library.hip"
+#include "adh_flatten.hip"

@@ -70,6 +70,7 @@ def _load():
     lib = C.CDLL(LIB_PATH)
     _abi.declare(lib)
     _abi.declare(lib, _abi.LFQ_EXPORTS)
+    _abi.declare(lib, _abi.FLATTEN_EXPORTS)
     return lib
 
 
@@ -777,6 +778,52 @@ class Context:
         out = np.empty(getattr(self, "_n_lib", 0), dtype=_abi.LIB_RECORD_DTYPE)
         _check(lib.adh_staged_fragments_read(self._h, int(bool(host_mirror)), _p(out), out.shape[0]),
                "adh_staged_fragments_read")
+        return out
+
+    def flatten_library(self, frag_start, frag_stop, elution_group, decoy, mz, intensity, column_codes, top_k: int,
+                        min_intensity: float, stage: bool = False) -> dict:
+        """The device flatten (include/alphadia_hip_flatten.h: ``adfl_flatten``): int64 precursor columns (``decoy``
+        uint8 or None), the two float32 matrices ``[n_rows, n_cols]`` and ``column_codes[4, n_cols]`` (type,
+        loss_type, charge, counts-from-the-N-terminus) in; ``flat_frag_start_idx`` / ``flat_frag_stop_idx`` per
+        precursor and the eight flat columns out, with ``routes``, ``kernel_ms`` and the link bytes of the call.
+        ``stage``: the records are left staged on this context, as ``stage_fragments_columns`` of the returned
+        columns would leave them (``adopt_fragment_columns`` then names them).  A refused input raises ``ValueError``
+        and leaves the staged library and its bookkeeping as they were."""
+        start, stop, eg = (_abi.as_c(a, np.int64) for a in (frag_start, frag_stop, elution_group))
+        dec = _abi.as_c(decoy, np.uint8) if decoy is not None else None
+        mz, intensity = _abi.as_c(mz, np.float32), _abi.as_c(intensity, np.float32)
+        codes = _abi.as_c(column_codes, np.uint8)
+        n = start.shape[0]
+        if mz.ndim != 2 or mz.shape != intensity.shape or codes.shape != (4, mz.shape[1]):
+            raise ValueError("flatten_library: two matrices of one shape and four codes per column")
+        if stop.shape != (n,) or eg.shape != (n,) or (dec is not None and dec.shape != (n,)):
+            raise ValueError("flatten_library: precursor columns differ in length")
+        n_rows, n_cols = mz.shape
+        capacity = int(np.minimum(np.clip(stop - start, 0, 255) * n_cols, max(int(top_k), 0)).sum())
+        flat_start, flat_stop = np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.uint32)
+        out_mz, out_int = np.empty(capacity, dtype=np.float32), np.empty(capacity, dtype=np.float32)
+        out_bytes = np.empty((6, capacity), dtype=np.uint8)
+        n_flat, routes, ms, link = C.c_int64(0), (C.c_int64 * 4)(), C.c_double(0.0), (C.c_uint64 * 2)()
+        rc = lib.adfl_flatten(self._h, n, _p(start, C.c_int64), _p(stop, C.c_int64), _p(eg, C.c_int64), _p(dec, C.c_uint8),
+                              n_rows, n_cols, _p(mz, C.c_float), _p(intensity, C.c_float), _p(codes, C.c_uint8), int(top_k),
+                              float(min_intensity), int(bool(stage)), capacity, _p(flat_start, C.c_uint32),
+                              _p(flat_stop, C.c_uint32), _p(out_mz, C.c_float), _p(out_int, C.c_float),
+                              _p(out_bytes, C.c_uint8), C.byref(n_flat), routes, C.byref(ms), link)
+        if rc == -1:  # ADH_ERR_INVALID_ARGUMENT: refused before anything was touched
+            msg = lib.adh_last_error()
+            raise ValueError(msg.decode() if msg else "adfl_flatten refused its input")
+        if stage:
+            self._lib_key = None
+            self.select_serial += 1
+        _check(rc, "adfl_flatten")
+        k = int(n_flat.value)
+        out = dict(flat_frag_start_idx=flat_start, flat_frag_stop_idx=flat_stop, mz=out_mz[:k], intensity=out_int[:k],
+                   routes=dict(zip(("card_wave", "card_block", "select_wave", "select_block"), (int(r) for r in routes))),
+                   kernel_ms=float(ms.value), h2d_bytes=int(link[0]), d2h_bytes=int(link[1]))
+        for j, name in enumerate(("type", "loss_type", "charge", "number", "position", "cardinality")):
+            out[name] = out_bytes[j, :k]
+        if stage:
+            self._staged_library((out["mz"],), k, None)
         return out
 
     # -- scoring ---------------------------------------------------------
