@@ -806,6 +806,9 @@ PROTOTYPES = {
     # test entry, stream, timers and launch counters
     "adh_debug_get_dense": (_i32, [_vp, _i64, _i64, _i64, _i64, _f32p, _i32, _f32, _f32, _f32, _f32p, _i64, _i32p,
                                    _i32p, _i32p, _i32p]),
+    "adh_debug_log_f32": (_i32, [_vp, _f32p, _i64, _i32, _f64p, _f32p]),
+    "adh_debug_log_f32_sweep": (_i32, [_vp, C.c_uint32, C.c_uint32, _i32, _i64p, _u32p, _i64, _f64p,
+                                       _u32p]),
     "adh_get_stream": (_i32, [_vp, _vpp]),
     "adh_synchronize": (_i32, [_vp]),
     "adh_kernel_time_ms": (_i32, [_vp, _f64p, _f64p, _i64p, _i32]),

@@ -1611,3 +1611,4 @@ int adh_fragcomp_stats(adh_handle_t *h, double *kernel_ms, int64_t *pairs, int64
 #include "adh_transfer_library.hip"
 #include "adh_mbr_library.hip"
 #include "adh_flatten.hip"
+#include "adh_debug_log.hip"

@@ -2,12 +2,22 @@
 #pragma once
 #include "adh_log_table.h"
 
-// log of a float32 x >= 1 in float64, error <= 1 ulp (the class of the library log; checked against an
-// 80-bit log, tools/gen_log_table.py): x = 2^e * m, the top 7 mantissa bits pick c = 1 + i / 128, and
+// log of a finite float32 x >= 1 in float64: x = 2^e * m, the top 7 mantissa bits pick c = 1 + i / 128, and
 // log(m) = -log(1 / c) + log1p(m / c - 1) with |m / c - 1| < 2^-7 and a degree-9 series.  All terms are
 // >= 0 (no cancellation) and entry 0 is exact, so values next to 1 keep their relative accuracy.  The
 // smoothing needs one log per non-zero output cell, 127 000 per precursor: this is about half the
 // instructions of the general routine.
+// Error: at most 2 ulp of float64 (the class of the library log), derived.  The result is
+// fl(e ln2_hi + fl(fl(T + p) + fl(e ln2_lo))) with e ln2_hi exact (ln2_hi has 32 bits); the table entry T, T + p
+// and the last sum are each within half an ulp of themselves, T and T + p lie below the result for e >= 1, and
+// what is left - the series' remainder, the roundings of r, of p and of e ln2_lo, all far below the result - is
+// under 2^-4 ulp there: 1.5 ulp + 2^-4.  At e = 0 nothing is added to T + p; the rounding of r counts against a
+// smaller result, but T or r lies a binade below it: under 1.1 ulp.
+// Measured on an MI355X against an 80-bit log (tests/test_log_f32_gpu.py): 1.023 ulp over all 2^23 mantissas of
+// e = 0 (at 0x3F93F8E9), 1.202 ulp over every 128th mantissa and the table edges of e = 1 ... 127 (at 0x40DAB000,
+// e = 2; under 0.6 ulp from e = 11 on), and (float) of the result equal to (float) of the 80-bit log on every one
+// of them.  Over all 2^30 arguments it stays within 1 ulp of the device library's log, and no float32 rounding
+// differs: what the selection depends on is that (float)adh_log_f32(x) == (float)log((double)x).
 // (`tab`: the table as 256 doubles - adh_log_tab itself, or a copy of it in LDS: a table look-up per log is a global load
 // in the middle of a dependent chain, and the smoothing kernel of the ion-mobility selection takes one log per cell)
 __device__ __forceinline__ double adh_log_f32(float x, const double *tab = &adh_log_tab[0][0]) {

@@ -563,6 +563,31 @@ class Context:
         K, O, S, F = q.shape[0], n_obs.value, n_s.value, n_f.value
         return buf[: 2 * K * O * S * F].reshape(2, K, O, S, F).copy(), obs[:O].astype(np.int64)
 
+    def debug_log_f32(self, x, lds_table: bool = False):
+        """The selection's table-driven log on the device (test entry): ``(out64, out32)`` for the float32 values
+        ``x`` - the float64 log where it is defined (1 <= x < inf, NaN elsewhere) and the float32 value the smoothing
+        kernels store (their three-way dispatch).  ``lds_table``: read the table from a copy in LDS."""
+        x = _abi.as_c(x, np.float32).reshape(-1)
+        out64, out32 = np.empty(x.shape[0], np.float64), np.empty(x.shape[0], np.float32)
+        _check(lib.adh_debug_log_f32(self._h, _p(x, C.c_float), x.shape[0], int(bool(lds_table)), _p(out64, C.c_double),
+                                     _p(out32, C.c_float)), "adh_debug_log_f32")
+        return out64, out32
+
+    def debug_log_f32_sweep(self, first_bits: int, last_bits: int, lds_table: bool = False, capacity: int = 4096) -> dict:
+        """The same log over every float32 bit pattern in ``[first_bits, last_bits]`` against the device library's
+        log (test entry): ``count`` arguments whose float32-rounded logs differ, the first ``capacity`` of them in
+        ``bits`` (ascending), and the largest float64 difference ``max_ulps`` at the argument ``max_bits``."""
+        for name, v in (("first_bits", first_bits), ("last_bits", last_bits)):
+            if not 0 <= int(v) <= 0xFFFFFFFF:
+                raise ValueError(f"{name} is no 32-bit pattern: {v!r}")
+        bits = np.zeros(max(int(capacity), 1), np.uint32)
+        count, ulps, at = C.c_int64(0), C.c_double(0.0), C.c_uint32(0)
+        _check(lib.adh_debug_log_f32_sweep(self._h, int(first_bits), int(last_bits), int(bool(lds_table)), C.byref(count),
+                                           _p(bits, C.c_uint32), int(capacity), C.byref(ulps), C.byref(at)),
+               "adh_debug_log_f32_sweep")
+        return {"count": int(count.value), "bits": bits[: min(int(count.value), max(int(capacity), 0))].copy(),
+                "max_ulps": float(ulps.value), "max_bits": int(at.value)}
+
     def d2h_bytes(self, reset: bool = False) -> int:
         """Bytes the library copied device -> host on this GPU since the last reset."""
         v = C.c_uint64(0)

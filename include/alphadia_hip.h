@@ -434,6 +434,29 @@ int adh_debug_get_dense(adh_handle_t *handle, int64_t frame_start, int64_t frame
                         float quad_lo, float quad_hi, float *dense, int64_t dense_capacity, int32_t *obs,
                         int32_t *n_obs, int32_t *n_scans, int32_t *n_cycles);
 
+/*
+ * Test entry: the table-driven log of candidate selection (csrc/adh_log_f32.h) on n host values, as the
+ * library's build compiles it.  out64[i] is the float64 log of x[i] for 1 <= x[i] < inf and NaN elsewhere;
+ * out32[i] is what the two smoothing kernels store by their three-way dispatch: 0 for x[i] == 1, the rounded
+ * table log inside [1, inf), the library routine's float32 log for everything else (below 1, NaN, +inf).
+ * lds_table != 0: every workgroup copies the table to LDS first and reads it there, as the ion-mobility
+ * smoothing kernel does.  n == 0 returns without a launch.
+ */
+int adh_debug_log_f32(adh_handle_t *handle, const float *x, int64_t n, int32_t lds_table, double *out64,
+                      float *out32);
+
+/*
+ * Test entry: the same log over every float32 bit pattern in [first_bits, last_bits], which must lie inside
+ * [0x3F800000, 0x7F7FFFFF] (1 <= x < inf), in one launch, against the device library's float64 log of the
+ * same argument.  *n_mismatch: arguments whose two logs round to different float32 values (never truncated);
+ * mismatch_bits[0 .. min(*n_mismatch, capacity)): their bit patterns, ascending when all of them fit;
+ * *max_ulps, *max_bits: the largest |table log - library log| in units of the library value's spacing, and
+ * the smallest argument that reaches it.
+ */
+int adh_debug_log_f32_sweep(adh_handle_t *handle, uint32_t first_bits, uint32_t last_bits, int32_t lds_table,
+                            int64_t *n_mismatch, uint32_t *mismatch_bits, int64_t capacity, double *max_ulps,
+                            uint32_t *max_bits);
+
 /* The handle's own (non-blocking) stream as a hipStream_t. */
 int adh_get_stream(adh_handle_t *handle, void **hip_stream);
 

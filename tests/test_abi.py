@@ -23,7 +23,7 @@ DECLS = [(ret, name, [] if params.strip() == "void" else [" ".join(p.split()) fo
 
 SCALARS = {"int": C.c_int32, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "float": C.c_float,
            "double": C.c_double, "uint8_t": C.c_uint8, "uint16_t": C.c_uint16, "uint32_t": C.c_uint32}
-BY_VALUE = ("int", "int32_t", "int64_t", "uint64_t", "float", "double")
+BY_VALUE = ("int", "int32_t", "int64_t", "uint32_t", "uint64_t", "float", "double")
 HANDLES = ("adh_handle_t", "adh_mlp_t", "adh_quant_t", "adh_pg_t", "adh_pfdr_t", "adh_tl_t", "adh_mbr_t")
 
 
@@ -57,7 +57,7 @@ def expected_ctype(c_type: str):
 
 def test_header_declares_what_the_table_lists_in_its_order():
     names = [name for _, name, _ in DECLS]
-    assert len(names) == len(set(names)) == 124
+    assert len(names) == len(set(names)) == 126
     assert set(names) == set(_abi.PROTOTYPES)
     assert names == list(_abi.PROTOTYPES)
     assert set(re.findall(r"\badh_\w+(?=\s*\()", CODE)) == set(names)  # no declaration the parse above missed

@@ -331,6 +331,24 @@ def test_log_table_header_matches_its_generator():
         assert abs(mine - ref) <= np.spacing(abs(ref)), x
         assert np.float32(mine) == np.float32(np.log(np.float64(x))), x
 
+    # The rest of the domain, up to the largest finite float32 (smoothed Orbitrap intensities have exponents 30 ... 33):
+    # the float32 identity, and the derived float64 bound (adh_log_f32.h): 2 ulp, 1.1 ulp at exponent 0 - measured
+    # against the unrounded 80-bit log, in units of the spacing of its float64 rounding.
+    assert np.finfo(ld).nmant >= 63
+
+    def ulps(x):
+        ref = np.log(ld(float(x)))
+        return float(abs(ld(log_f32(float(x))) - ref) / ld(np.spacing(abs(float(ref)))))
+
+    wide = np.concatenate([(((e + 127) << 23) | rng.integers(0, 1 << 23, 150)).astype(np.uint32).view(np.float32)
+                           for e in (20, 33, 64, 127)] + [np.array([np.finfo(np.float32).max], dtype=np.float32)])
+    assert wide.size == 601 and np.isfinite(wide).all() and wide.min() >= 2.0 ** 20
+    for x in wide:
+        assert np.float32(log_f32(float(x))) == np.float32(np.log(np.float64(x))), x
+        assert ulps(x) <= 2.0, x
+    for x in xs:
+        assert ulps(x) <= (1.1 if x < 2 else 2.0), x
+
 
 def test_threaded_object_gather_matches_numpy():
     """runtime.take_objects (adh_host_take_objects under the GIL) == NumPy's gather, reference counts included."""
